@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — train steps/sec of the DreamBooth LoRA step (BASELINE.json metric) on N MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" = one optimiser update of train_lora_dreambooth.py's loop (ref :816-888) on the workload
@@ -9,7 +9,9 @@ BASELINE.json's configs[1] names: SD1.5-shaped UNet (859.5 M params, random init
 checkpoints), reference-default LoRA injection (144 Linear sites in CrossAttention/GEGLU), rank 4,
 bf16 compute with f32 LoRA masters, batch 4 synthetic 64x64x4 latents (= 512x512 images) per GPU,
 DDPM noise, MSE, backward, flat-buffer all-reduce (RCCL), clip(1.0), AdamW(lr 1e-4, wd 1e-2).
-Rank 0 prints ONE JSON line (see DESIGN.md §Measurement for `roofline` and `cpu_baseline`).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints it; `--full` adds what
+takes runs of its own: the adapter-path profile, `roofline`, `cpu_baseline` and the
+`secondary` lines of the other BASELINE configurations.
 """
 from __future__ import annotations
 
@@ -642,6 +644,48 @@ def emit(out: dict) -> None:
     print(json.dumps(compact_record(out, path)), flush=True)
 
 
+DUMP_LIMIT = 64 << 20  # bytes: --dump-outputs writes at most this much
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: each tensor of ``arrays`` as ``dirname/<name>.npy`` in float32."""
+    import numpy as np
+
+    host = {name: t.detach().to(torch.float32).cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT})")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log(f"[bench] outputs of the last timed step: {', '.join(f'{n}{list(a.shape)}' for n, a in host.items())} -> {dirname}")
+
+
+MIOPEN_SEED_DB = os.path.join(REPO, "bench_tuning", "miopen")
+
+
+def private_miopen_db() -> None:
+    """Give MIOpen a private user database for this run, seeded with bench_tuning/miopen: the Find results and tuned
+    configurations of the step's convolutions, recorded on an MI355X with this ROCm.  A fresh box then skips the ~25 s
+    of Find at the first step, and the run neither reads nor writes the user's own MIOpen database (whose Find results
+    would otherwise also steer later processes' convolutions).  Problems the seed does not hold (another MIOpen version,
+    device or geometry) are found at run time as before; an explicit MIOPEN_USER_DB_PATH is left alone.  The seed holds
+    the solvers a live Find picks on this hardware, so the step runs the convolutions it ran before (DESIGN.md §6 on
+    their parity).  Called before the first convolution."""
+    if os.environ.get("MIOPEN_USER_DB_PATH"):
+        return
+    import atexit
+    import glob
+    import shutil
+    import tempfile
+
+    d = tempfile.mkdtemp(prefix="lora_amd_miopen_")
+    atexit.register(shutil.rmtree, d, True)
+    for f in glob.glob(os.path.join(MIOPEN_SEED_DB, "*.txt")):
+        shutil.copy(f, d)
+    os.environ["MIOPEN_USER_DB_PATH"] = d
+
+
 def self_launch(args) -> int:
     """`python bench.py --gpus N` with N > 1 and no launcher environment: start one process per GPU ourselves, the way
     the driver's documented command does (torch.distributed.run, 127.0.0.1 rendezvous), and relay rank 0's JSON line."""
@@ -712,16 +756,19 @@ def svd_bench(args) -> dict:
 
     def step():
         gen = torch.Generator(device=dev).manual_seed(1)
-        return S.distill_model(groups, rank, 0.99, gen, n_iter=n_iter)[-1]
+        return S.distill_model(groups, rank, 0.99, gen, n_iter=n_iter)
 
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        up, down = step()
+        res = step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:  # every site's factors, shape groups in sorted (N, K) order, sites in group order, row-major
+        dump_outputs(args.dump_outputs, {"svd_up": torch.cat([up.reshape(-1) for up, _ in res]),
+                                         "svd_down": torch.cat([down.reshape(-1) for _, down in res])})
     iters = n_iter if n_iter is not None else (S.LAST_ITERATIONS or 4)
     passes = 2 * iters + 2
     # the subspace-steering passes (sketch + power iterations) read the hi plane only (2 bytes / element), the pass that forms
@@ -751,7 +798,7 @@ def svd_bench(args) -> dict:
                         "note": "WHOLE-STEP figure (passes + forming the planes + ~70 small launches + one host sync per adaptive "
                                 "iteration from the 3rd on); per-kernel shares: profiles/r06_svd_kernel_trace_summary.txt.  "
                                 "LORA_AMD_SVD_ITERS=4 fixes the iteration count (rounds 2-4's iso-work figure)"}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         import subprocess
 
         threads = min(usable_cores(), 64)
@@ -818,7 +865,15 @@ def main():
     ap.add_argument("--svd", action="store_true", help="time BASELINE configs[4] (cli_svd distillation, 224 sites) "
                     "instead of the training step; prints its own JSON line")
     ap.add_argument("--svd-worker", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true", help="also take everything beyond the headline figure: the adapter-path "
+                    "profile, the rooflines, the CPU baseline and the secondary lines (each still subject to its --no-* "
+                    "switch).  Off: set up, warm up, time --steps steps, write --dump-outputs, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed "
+                    "step computed as DIR/<name>.npy (float32): the loss, the LoRA parameters and the AdamW moments (--svd: "
+                    "every site's up / down factors); the inputs are seeded, so two builds can be compared array by array.  With --full the "
+                    "adapter-path profile takes eager steps before the capture: compare --full runs with --full runs only")
     args = ap.parse_args()
+    t_main = time.perf_counter()
     global PATH_LOG_FILE
     PATH_LOG_FILE = args.path_log
     if args.cpu_worker:
@@ -844,6 +899,7 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))  # one process per GPU; rank 0 of the child job prints the JSON line
     if on_gpu:
+        private_miopen_db()
         torch.backends.cudnn.benchmark = bool(args.conv_find)
         if args.conv_find:
             # Find times every applicable solver once per convolution geometry; MIOpen's naive reference solvers
@@ -963,12 +1019,12 @@ def main():
         if on_gpu:
             torch.cuda.synchronize()
 
-    # which kernel runs which site, device time of the adapter kernels, adapter-path bytes: one eager profiled step,
+    # which kernel runs which site, device time of the adapter kernels, adapter-path bytes (--full): one eager profiled step,
     # BEFORE the capture (rank 0 of a 1-GPU run; its attention / MIOpen choices are the ones the graph then bakes in)
     adapter_path, kernel_choices = None, {}
     # world == 1 only: the eager steps below run the step's collectives (the flat-gradient all-reduce, the broadcast of rank
     # 0's attention choices) and must never be entered by one rank of several
-    if on_gpu and world == 1 and args.adapters == "hip" and not args.no_roofline:
+    if args.full and on_gpu and world == 1 and args.adapters == "hip" and not args.no_roofline:
         def eager_step():
             fwd_bwd(latents, ehs)
             state.step(state.all_reduce())
@@ -979,6 +1035,7 @@ def main():
             log(f"[bench] adapter-path profile failed: {type(e).__name__}: {e}")
     barrier()
 
+    t_setup = time.perf_counter()
     mode = args.mode
     runner = fwd_bwd
     if mode == "graph":
@@ -999,15 +1056,20 @@ def main():
         tail_host.append(time.perf_counter() - t_h)
         return loss
 
+    t_capture = time.perf_counter()
     for _ in range(args.warmup):
         step()
     barrier()
+    t_warm = time.perf_counter()
     tail_host.clear()
     if rank == 0 and on_gpu:  # which kernels the per-shape tuning settled on (stderr; the JSON line stays alone on stdout)
         from lora_amd.standin import attention as _att
 
         log("[bench] attention kernels:", {k: v for k, v in _att.choices().items()})
         log("[bench] adapter kernels per step:", kernel_choices)
+    if rank == 0:  # where the time outside the timed steps goes (first-use compilation and tuning land in capture / warm-up)
+        log(f"[bench] host seconds: setup {t_setup - t_main:.1f}, capture {t_capture - t_setup:.1f}, "
+            f"warm-up {t_warm - t_capture:.1f}")
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
@@ -1018,6 +1080,11 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
     loss_v = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step holds after the last timed one: its loss and the optimiser's updated state (the flat
+        # gradient is zeroed by the step itself; the first moment carries it)
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "lora_params": state.flat_p,
+                                         "adamw_exp_avg": state.exp_avg, "adamw_exp_avg_sq": state.exp_avg_sq})
     # the step's one collective on its real payload, timed on its own (HIP events, RCCL's stream ordering; host clock
     # around gloo on CPU)
     allreduce_us = None
@@ -1137,7 +1204,7 @@ def main():
                                                 % os.path.basename(pmc))
                 except (KeyError, ValueError):
                     pass
-        if on_gpu and not args.no_roofline:
+        if args.full and on_gpu and not args.no_roofline:
             out["roofline"] = merge_roofline(unet)
             if merged is not None and world == 1:
                 try:
@@ -1145,9 +1212,9 @@ def main():
                 except Exception as e:  # noqa: BLE001 - evidence, not the product
                     log(f"[bench] in-step roofline failed: {type(e).__name__}: {e}")
             out["roofline_fused_gemm"] = gemm_roofline()
-        if world == 1 and on_gpu and not args.no_cpu_baseline:
+        if args.full and world == 1 and on_gpu and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.lora_rank)
-        if world == 1 and on_gpu and headline and not args.no_secondary:
+        if args.full and world == 1 and on_gpu and headline and not args.no_secondary:
             out["secondary"] = run_secondaries(args.secondary_budget, steps=20)
             for rec in out["secondary"]:
                 if rec["tag"] == "frozen_only" and "value" in rec:

@@ -234,6 +234,67 @@ def example_lora_manifest():
         json.dump(man, f)
 
 
+def differential_cases():
+    """Random trees (H.random_tree_specs): the reference's injection names, factors, the tensors its load_safeloras reads
+    back from its own file, and every parameter after its collapse_lora (ref:255-304, 400-596, 820-830)."""
+    arrays, recs = {}, []
+    for trial, spec in enumerate(H.random_tree_specs(12)):
+        torch.manual_seed(trial)
+        a = H.build_tree(spec)
+        ext = trial % 2 == 1
+        torch.manual_seed(99)
+        if ext:
+            _, na = ref.inject_trainable_lora_extended(a, r=2)
+            tgt = ref.UNET_EXTENDED_TARGET_REPLACE
+        else:
+            _, na = ref.inject_trainable_lora(a, r=2, scale=0.5)
+            tgt = ref.DEFAULT_TARGET_REPLACE
+        rec = {"names": na}
+        recs.append(rec)
+        if not na:
+            continue
+        pairs = ref.extract_lora_ups_down(a, tgt)
+        for i, (up, down) in enumerate(pairs):
+            arrays[f"t{trial}_down{i}"] = H.t2n(down.weight)
+            up.weight.data.normal_(0, 0.1)
+            arrays[f"t{trial}_up{i}"] = H.t2n(up.weight)
+        rec["pairs"] = len(pairs)
+        path = os.path.join(OUT, "_differential_tmp.safetensors")
+        quiet(ref.save_safeloras, {"unet": (a, tgt)}, path)
+        weights, ranks = ref.load_safeloras(path)["unet"][:2]
+        os.remove(path)
+        rec["ranks"] = ranks
+        for i, w in enumerate(weights):
+            arrays[f"t{trial}_loaded{i}"] = H.t2n(w)
+        rec["loaded"] = len(weights)
+        quiet(ref.collapse_lora, a, 0.8)
+        rec["param_names"] = [n for n, _ in a.named_parameters()]
+        for i, (_, p) in enumerate(a.named_parameters()):
+            arrays[f"t{trial}_param{i}"] = H.t2n(p)
+    np.savez_compressed(os.path.join(OUT, "differential_cases.npz"), **arrays)
+    with open(os.path.join(OUT, "differential_cases.json"), "w") as f:
+        json.dump(recs, f, indent=1)
+
+
+def pti_train_signature():
+    """The argument names of the reference's cli_lora_pti.train and its literal defaults, read textually (the module
+    imports diffusers): [name, kind, value] with kind "set" for set literals (stored sorted), "value" otherwise."""
+    import ast
+
+    src = open(os.path.join(os.path.dirname(H.REFERENCE_LORA), "cli_lora_pti.py")).read()
+    fn = next(n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef) and n.name == "train")
+    names = [a.arg for a in fn.args.args]
+    defaults = []
+    for k, node in zip(names[len(names) - len(fn.args.defaults):], fn.args.defaults):
+        try:
+            v = ast.literal_eval(node)
+        except ValueError:
+            continue
+        defaults.append([k, "set", sorted(v)] if isinstance(v, set) else [k, "value", v])
+    with open(os.path.join(OUT, "pti_train_signature.json"), "w") as f:
+        json.dump({"names": names, "literal_defaults": defaults}, f, indent=1)
+
+
 def optimizer_cases():
     """torch.optim.AdamW + clip_grad_norm_ as driven by ref train_lora_dreambooth.py:651-676, 878-888."""
     torch.manual_seed(11)
@@ -369,6 +430,8 @@ if __name__ == "__main__":
     traversal_cases()
     injection_and_file_cases()
     example_lora_manifest()
+    differential_cases()
+    pti_train_signature()
     optimizer_cases()
     hostops_cases()
     pti_loss_cases()

@@ -8,10 +8,12 @@ OUT=gpurun_out
 export TMPDIR=/tmp
 export LORA_AMD_TUNE_CACHE=/tmp/lora_amd_tune_${TAG}.json   # the warm run times the candidates, the traced run re-uses them
 mkdir -p $OUT
-ARGS="--steps 5 --warmup 3 --no-cpu-baseline ${BENCH_EXTRA:-}"
+export MIOPEN_USER_DB_PATH=$(mktemp -d)   # one MIOpen database for both runs (bench.py keeps an explicit one)
+cp bench_tuning/miopen/*.txt $MIOPEN_USER_DB_PATH/
+ARGS="--full --steps 5 --warmup 3 --no-cpu-baseline ${BENCH_EXTRA:-}"
 ONLY=${2:-all}
 if [ "$ONLY" != "pmc" ]; then
-# 1. un-profiled run first: fills MIOpen's find cache (a cold MIOpen under the profiler falls back to naive convs)
+# 1. un-profiled run first: fills the shared MIOpen database above (a cold MIOpen under the profiler falls back to naive convs)
 python bench.py $ARGS > $OUT/${TAG}_bench_warm.json 2> $OUT/${TAG}_bench_warm.err
 # 2. kernel trace + stats of the same command
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -o bench -- python bench.py $ARGS > $OUT/${TAG}_bench_traced.json 2> $OUT/${TAG}_bench_traced.err

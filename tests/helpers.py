@@ -83,6 +83,27 @@ def oracle_spec(spec):
     return out
 
 
+def random_tree_specs(n: int, seed: int = 0):
+    """``n`` random module trees (Linear / 1x1 Conv2d leaves under target and non-target classes, depth <= 3) from one
+    seeded stream: the trees of the differential test against the reference (scripts/make_golden.py::differential_cases)."""
+    rng = np.random.default_rng(seed)
+
+    def rand_spec(depth):
+        kids = []
+        for i in range(int(rng.integers(1, 4))):
+            roll = rng.random()
+            if depth >= 3 or roll < 0.35:
+                kids.append([f"l{i}", {"cls": "Linear", "kind": "linear"}])
+            elif roll < 0.45:
+                kids.append([f"c{i}", {"cls": "Conv2d", "kind": "conv", "k": 1}])
+            else:
+                cls = ["CrossAttention", "GEGLU", "Attention", "ResnetBlock2D", "Other", "ModuleList"][int(rng.integers(0, 6))]
+                kids.append([f"m{i}", {"cls": cls, "children": rand_spec(depth + 1)["children"]}])
+        return {"cls": "Root", "children": kids}
+
+    return [rand_spec(0) for _ in range(n)]
+
+
 def reference_available() -> bool:
     return os.path.exists(REFERENCE_LORA)
 

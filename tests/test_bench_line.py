@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from tests import helpers as H
@@ -97,6 +98,32 @@ def test_cpu_run_prints_one_parseable_stdout_line_and_a_detail_file(tmp_path):
         assert json.load(f)["value"] == rec["value"]
     os.remove(detail)
     assert "[bench-detail] {" in r.stderr
+
+
+def test_dump_outputs_writes_what_the_last_timed_step_computed(tmp_path):
+    """`--dump-outputs DIR`: the loss, the LoRA parameters and the AdamW moments after the last timed step, float32 .npy;
+    the loss is the line's final_loss, the parameters its trainable_params; the inputs are seeded, so two single-threaded
+    runs write the same arrays."""
+    env = {**os.environ, "OMP_NUM_THREADS": "1", "LORA_AMD_BENCH_DETAIL_TAG": "cpudump"}
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(H.REPO, "bench.py"), "--device", "cpu", "--standin", "tiny", "--steps",
+                            "2", "--warmup", "1", "--batch", "1", "--res", "64", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+        arrays = {f[:-len(".npy")]: np.load(d / f) for f in os.listdir(d)}
+        assert set(arrays) == {"loss", "lora_params", "adamw_exp_avg", "adamw_exp_avg_sq"}
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert arrays["lora_params"].shape == arrays["adamw_exp_avg"].shape == (rec["config"]["trainable_params"],)
+        assert abs(float(arrays["loss"][0]) - rec["config"]["final_loss"]) <= 1e-4
+        assert float(np.abs(arrays["adamw_exp_avg"]).max()) > 0
+        runs.append(arrays)
+        if rec.get("detail"):  # the run's detail record, written next to the repository
+            os.remove(os.path.join(H.REPO, rec["detail"]))
+    for k, a in runs[0].items():
+        assert np.array_equal(a, runs[1][k]), k
 
 
 def test_eight_gloo_ranks_print_one_short_line_with_distinct_noise_streams_and_equal_replicas():

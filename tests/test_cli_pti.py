@@ -1,5 +1,6 @@
 """``lora_amd.cli_lora_pti`` (drop-in for the reference's lora_pti console script) end to end on CPU at toy size."""
 import inspect
+import json
 import os
 
 import torch
@@ -24,21 +25,14 @@ def test_keyword_surface_matches_reference():
     sig = inspect.signature(pti.train).parameters
     assert sig["max_train_steps_ti"].default == 1000 and sig["lr_scheduler"].default == "linear"
     assert sig["weight_decay_lora"].default == 0.001 and sig["device"].default == "cuda:0"
-    if H.reference_available():  # defaults identical to the live reference signature, read textually (it cannot be imported)
-        import ast
-        import re
-
-        src = open("/root/reference/lora_diffusion/cli_lora_pti.py").read()
-        fn = next(n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef) and n.name == "train")
-        ref_names = [a.arg for a in fn.args.args]
-        assert ref_names == ref
-        defaults = dict(zip(ref_names[len(ref_names) - len(fn.args.defaults):], fn.args.defaults))
-        for k, node in defaults.items():
-            try:
-                want = ast.literal_eval(node)
-            except ValueError:
-                continue
-            assert sig[k].default == want, k
+    # defaults identical to the reference signature, read textually from it (it cannot be imported) into
+    # tests/golden/pti_train_signature.json by scripts/make_golden.py::pti_train_signature
+    with open(os.path.join(H.GOLDEN, "pti_train_signature.json")) as f:
+        rsig = json.load(f)
+    assert rsig["names"] == ref
+    assert len(rsig["literal_defaults"]) >= 50
+    for k, kind, want in rsig["literal_defaults"]:
+        assert sig[k].default == (set(want) if kind == "set" else want), k
 
 
 def test_parse_cli_shim():

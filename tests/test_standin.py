@@ -44,12 +44,26 @@ def test_clip_index_layout_matches_shipped_fixture():
         assert tensors[f"text_encoder:{i}:down"]["shape"] == [4, m.in_features]
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/example_loras/analog_svd_rank4.safetensors"),
-                    reason="shipped fixture not mounted")
+def _shipped_layout_file(fn: str, path: str) -> str:
+    """A .safetensors file with the layout of the reference's shipped ``fn`` as the manifest records it (keys in file order,
+    shapes, dtypes, metadata; the 3 MB original is not part of the repository): seeded values in place of the factors."""
+    from safetensors import safe_open
+    from safetensors.torch import save_file
+
+    ent = MAN[fn]
+    g = torch.Generator().manual_seed(0)
+    tensors = {k: (torch.randn(*ent["tensors"][k]["shape"], generator=g) * 0.01).to(getattr(torch, ent["tensors"][k]["dtype"]))
+               for k in ent["keys_in_file_order"]}
+    save_file(tensors, path, ent["metadata"])
+    f = safe_open(path, framework="pt", device="cpu")
+    assert list(f.keys()) == ent["keys_in_file_order"] and f.metadata() == ent["metadata"]
+    return path
+
+
 def test_patch_shipped_fixture_into_standin_and_resave(tmp_path):
     from safetensors import safe_open
 
-    path = "/root/reference/example_loras/analog_svd_rank4.safetensors"
+    path = _shipped_layout_file("analog_svd_rank4.safetensors", str(tmp_path / "analog_svd_rank4.safetensors"))
     with torch.device("meta"):
         unet, clip = sd15_unet(), clip_text_model()
 
@@ -60,6 +74,8 @@ def test_patch_shipped_fixture_into_standin_and_resave(tmp_path):
     pipe.unet, pipe.text_encoder = unet, clip
     parsed = L.load_safeloras(path)
     assert parsed["unet"][1] == [4] * 144 and parsed["text_encoder"][1] == [4] * 48
+    for k, want in MAN["analog_svd_rank4.safetensors"]["parsed"].items():  # the reference's parse of the shipped file
+        assert len(parsed[k][0]) == want["n"] and parsed[k][1] == want["ranks"] and sorted(parsed[k][2]) == want["targets"], k
     # keep real (CPU) factors: patch with the frozen weights on meta is fine for structure checks
     L.monkeypatch_or_replace_safeloras(pipe, safe_open(path, framework="pt", device="cpu"))
     ads = [m for m in unet.modules() if isinstance(m, L.LoraInjectedLinear)]
