@@ -179,6 +179,15 @@ int lora_amd_rank_update(void *y, int64_t ldy, const float *t, const void *facto
                          float scale, float dropout_p, uint64_t seed,
                          uint64_t offset, const uint64_t *offset_dev, void *stream);
 
+/* Per-sample multipliers (forward of a batch that carries one LoRA setting per sample): lora_amd_rank_update with row
+ * m's T row multiplied by row_scale[((m / rows_per_sample) % nsel) * r + j] (f32 [nsel, r], device) before it meets F:
+ * Y += scale * mask * (T o row_scale[sample]) @ F.  nsel >= 1, rows_per_sample >= 1, 1 <= r <= LORA_AMD_MAX_RANK.
+ * Dropout as lora_amd_rank_update (offset given by value). */
+int lora_amd_rank_update_rowscale(void *y, int64_t ldy, const float *t, const void *factor, int64_t M, int32_t N,
+                                  int32_t r, int32_t y_dtype, int32_t factor_dtype, int32_t factor_layout, float scale,
+                                  const float *row_scale, int32_t nsel, int64_t rows_per_sample, float dropout_p,
+                                  uint64_t seed, uint64_t offset, void *stream);
+
 /* As lora_amd_rowdot but X is first multiplied elementwise by the dropout mask
  * of (seed, offset, offset_dev, p): the backward of a dropped-out rank_update. */
 int lora_amd_rowdot_masked(const void *x, int64_t ldx, const void *factor,
@@ -507,6 +516,17 @@ int lora_amd_linear_gemm_fwd_heads(const void *x, int64_t ldx, const void *w, in
                                    int32_t factor_layout, int32_t tile, int32_t x_head_dim, int32_t x_head_pad,
                                    int32_t y_head_dim, int32_t y_head_pad, void *stream);
 
+/* lora_amd_linear_gemm_fwd (dense rows, down [r,K], up [N,r]) with per-sample multipliers: row m's T row is multiplied by
+ * row_scale[((m / rows_per_sample) % nsel) * r + j] (f32 [nsel, r], device) where T is rounded to the activation dtype;
+ * `scale` stays on up.  All multipliers 1.0 give the bits of lora_amd_linear_gemm_fwd at the same tile.  t_out may be
+ * NULL; if given it receives T = X down^T without the multipliers.  Same constraints as lora_amd_linear_gemm_fwd;
+ * nsel >= 1, rows_per_sample >= 1, 1 <= r <= 16 (LORA_AMD_ERANK otherwise). */
+int lora_amd_linear_gemm_fwd_rowscale(const void *x, int64_t ldx, const void *w, int64_t ldw, const void *bias, void *y,
+                                      int64_t ldy, const float *down, const float *up, float *t_out, int64_t M,
+                                      int32_t K, int32_t N, int32_t r, int32_t act_dtype, float scale,
+                                      const float *row_scale, int32_t nsel, int64_t rows_per_sample, int32_t tile,
+                                      void *stream);
+
 /* out (f32, [r,C] or [C,r]) = beta*out + scale * sum_p part[p][j][c], part laid out [nparts][RT][C].
  * ONE launch covers every descriptor: the trainer reduces all sites' partials into its flat gradient
  * buffer once per step.  `begin` = exclusive prefix sum of r*C over the table; total = its end. */
@@ -680,6 +700,14 @@ int lora_amd_conv_down_fwd(const void *x, const void *down, const float *sel, fl
 int lora_amd_conv_up_fwd(void *y, const float *t, const void *up, int32_t B, int32_t C_out, int32_t H, int32_t W,
                          int32_t r, int32_t act_dtype, int32_t factor_dtype, float scale, float dropout_p,
                          uint64_t seed, uint64_t offset, const uint64_t *offset_dev, void *stream);
+
+/* lora_amd_conv_up_fwd with per-sample multipliers: sample b's planes T[b, j] are multiplied by
+ * row_scale[((b / rows_per_sample) % nsel) * r + j] (f32 [nsel, r], device) as they are loaded.  nsel >= 1,
+ * rows_per_sample >= 1 (1: one row of the table per image). */
+int lora_amd_conv_up_fwd_rowscale(void *y, const float *t, const void *up, int32_t B, int32_t C_out, int32_t H,
+                                  int32_t W, int32_t r, int32_t act_dtype, int32_t factor_dtype, float scale,
+                                  const float *row_scale, int32_t nsel, int64_t rows_per_sample, float dropout_p,
+                                  uint64_t seed, uint64_t offset, void *stream);
 
 /* One pass over G[B, C_out, H, W]: gt_out[B, r, H, W] (f32) = S^T (scale * up^T (mask*G)) and
  * up_part[ngroups_out][rank_pad][C_out] = scale * sum over the group's pixels of (mask*G) T. */

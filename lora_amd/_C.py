@@ -58,6 +58,7 @@ SYMBOLS = (
     "lora_amd_layernorm_supported", "lora_amd_layernorm_fwd", "lora_amd_layernorm_bwd",
     "lora_amd_groupnorm_nhwc_workspace", "lora_amd_groupnorm_nhwc_fwd", "lora_amd_groupnorm_nhwc_bwd",
     "lora_amd_add_layernorm_fwd", "lora_amd_add_layernorm_bwd",
+    "lora_amd_linear_gemm_fwd_rowscale", "lora_amd_rank_update_rowscale", "lora_amd_conv_up_fwd_rowscale",
 )
 
 
@@ -351,6 +352,14 @@ def _declare(lib: C.CDLL) -> None:
     lib.lora_amd_linear_gemm_fwd.argtypes = [vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, i32,
                                              i32, vp]
     lib.lora_amd_linear_gemm_supported.restype = lib.lora_amd_linear_gemm_fwd.restype = C.c_int
+    lib.lora_amd_linear_gemm_fwd_rowscale.argtypes = [vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32,
+                                                      f32, vp, i32, i64, i32, vp]
+    lib.lora_amd_rank_update_rowscale.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32, i64, f32,
+                                                  u64, u64, vp]
+    lib.lora_amd_conv_up_fwd_rowscale.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, i32, i64, f32,
+                                                  u64, u64, vp]
+    for name in ("lora_amd_linear_gemm_fwd_rowscale", "lora_amd_rank_update_rowscale", "lora_amd_conv_up_fwd_rowscale"):
+        getattr(lib, name).restype = C.c_int
     lib.lora_amd_ws_config.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
     lib.lora_amd_ws_packed_elems.argtypes = [i32, i32]
     lib.lora_amd_ws_packed_elems.restype = i64
@@ -1613,6 +1622,67 @@ def linear_gemm_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.
                                                     float(scale), float(t_scale), int(factor_layout), int(tile),
                                                     xd, xD, yd, yD, _stream()), "lora_amd_linear_gemm_fwd")
     return y, t
+
+
+def _row_scale_check(row_scale: torch.Tensor, r: int, what: str) -> int:
+    if row_scale.dtype != torch.float32 or row_scale.dim() != 2 or row_scale.shape[1] != r or not row_scale.is_contiguous():
+        raise ValueError(f"{what}: row_scale must be a contiguous f32 [nsel, {r}] tensor, got "
+                         f"{row_scale.dtype} {tuple(row_scale.shape)}")
+    return row_scale.shape[0]
+
+
+def linear_gemm_fwd_rowscale(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], down: torch.Tensor,
+                             up: torch.Tensor, scale: float, row_scale: torch.Tensor, rows_per_sample: int,
+                             tile: int = 0, want_t: bool = False):
+    """y [M,N] (and T [M,r] f32 without the multipliers when ``want_t``) = the fused frozen GEMM + LoRA branch with row m's
+    T row multiplied by ``row_scale[(m // rows_per_sample) % nsel]`` (one launch, see include/lora_amd.h)."""
+    _dev_check(x, weight, down, up, row_scale)
+    M = x.shape[0]
+    N, K = weight.shape
+    r = down.shape[0]
+    nsel = _row_scale_check(row_scale, r, "linear_gemm_fwd_rowscale")
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    t = torch.empty((M, r), dtype=torch.float32, device=x.device) if want_t else None
+    _check(require().lora_amd_linear_gemm_fwd_rowscale(x.data_ptr(), x.stride(0), weight.data_ptr(), weight.stride(0),
+                                                       _ptr(bias), y.data_ptr(), y.stride(0), down.data_ptr(),
+                                                       up.data_ptr(), _ptr(t), M, K, N, r, dtype_code(x.dtype),
+                                                       float(scale), row_scale.data_ptr(), nsel, int(rows_per_sample),
+                                                       int(tile), _stream()), "lora_amd_linear_gemm_fwd_rowscale")
+    return (y, t) if want_t else y
+
+
+def rank_update_rowscale_(y: torch.Tensor, t: torch.Tensor, factor: torch.Tensor, layout: int, scale: float,
+                          row_scale: torch.Tensor, rows_per_sample: int, dropout_p: float = 0.0, seed: int = 0,
+                          offset: int = 0) -> torch.Tensor:
+    """Y[M,N] += scale * mask * (T[M,r] o row_scale[(m // rows_per_sample) % nsel]) @ F (in place)."""
+    lib = require()
+    _dev_check(y, t, factor, row_scale)
+    y = _as2d(y)
+    M, N = y.shape
+    factor = factor.contiguous()
+    r = factor.shape[0] if layout == FACTOR_RK else factor.shape[1]
+    if t.dtype != torch.float32 or t.shape != (M, r) or not t.is_contiguous():
+        raise ValueError(f"rank_update_rowscale: T must be contiguous f32 [{M},{r}]")
+    if factor.numel() != r * N:
+        raise ValueError(f"rank_update_rowscale: factor {tuple(factor.shape)} does not match N={N}")
+    nsel = _row_scale_check(row_scale, r, "rank_update_rowscale")
+    _check(lib.lora_amd_rank_update_rowscale(y.data_ptr(), y.stride(0), t.data_ptr(), factor.data_ptr(), M, N, r,
+                                             dtype_code(y.dtype), dtype_code(factor.dtype), layout, float(scale),
+                                             row_scale.data_ptr(), nsel, int(rows_per_sample), float(dropout_p),
+                                             int(seed), int(offset), _stream()), "lora_amd_rank_update_rowscale")
+    return y
+
+
+def conv_up_fwd_rowscale_(y: torch.Tensor, t: torch.Tensor, up: torch.Tensor, scale: float, row_scale: torch.Tensor,
+                          dropout_p: float = 0.0, seed: int = 0, offset: int = 0) -> None:
+    """y[B,Co,H,W] += scale * mask * conv_1x1(t[b] o row_scale[b % nsel]; up) in place (NCHW)."""
+    B, Co, H, W = y.shape
+    r = t.shape[1]
+    nsel = _row_scale_check(row_scale, r, "conv_up_fwd_rowscale")
+    _check(require().lora_amd_conv_up_fwd_rowscale(y.data_ptr(), t.data_ptr(), up.data_ptr(), B, Co, H, W, r,
+                                                   dtype_code(y.dtype), dtype_code(up.dtype), float(scale),
+                                                   row_scale.data_ptr(), nsel, 1, float(dropout_p), int(seed),
+                                                   int(offset), _stream()), "lora_amd_conv_up_fwd_rowscale")
 
 
 def linear_gemm_dx(g: torch.Tensor, weight_t: torch.Tensor, down: torch.Tensor, up: torch.Tensor, scale: float,

@@ -267,12 +267,16 @@ __global__ __launch_bounds__(kCT) void selector_mix_kernel(float *__restrict__ i
 
 // ============================================================================ Y += scale * mask * up T
 // grid (ngroups, split_out).  t: [B][r][HW] f32.
-template <class E, int RT, bool DROP>
+// RSC (lora_amd_conv_up_fwd_rowscale): sample b's T planes are multiplied by row_scale[((b / rps) % nsel) * r + j] in the
+// registers they are loaded into (a per-sample diagonal selector / alpha, no extra pass over T).
+template <class E, int RT, bool DROP, bool RSC = false>
 __global__ __launch_bounds__(kCT) void conv_up_fwd_kernel(typename E::storage *__restrict__ y,
                                                           const float *__restrict__ t,
                                                           const float *__restrict__ up, int B, int Co, int HW,
                                                           int r, int cpw, int64_t NP, int cps, float scale, float p,
-                                                          uint64_t seed, uint64_t offset, const uint64_t *offset_dev) {
+                                                          uint64_t seed, uint64_t offset, const uint64_t *offset_dev,
+                                                          const float *__restrict__ row_scale = nullptr, int nsel = 1,
+                                                          int64_t rps = 1) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int npix8 = HW >> 3;
@@ -283,6 +287,11 @@ __global__ __launch_bounds__(kCT) void conv_up_fwd_kernel(typename E::storage *_
   for (int j = 0; j < RT; ++j) {
     if (j < r) {
       ld8f(t + ((int64_t)cp.b * r + j) * HW + cp.p0, tt[j]);
+      if (RSC) {
+        const float m = row_scale[(((int64_t)cp.b / rps) % nsel) * r + j];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) tt[j][i] *= m;
+      }
     } else {
 #pragma unroll
       for (int i = 0; i < 8; ++i) tt[j][i] = 0.f;
@@ -709,6 +718,42 @@ extern "C" int lora_amd_conv_up_fwd(void *y, const float *t, const void *up, int
 #undef CU_RT
 #undef CU
   return check_launch("lora_amd_conv_up_fwd");
+}
+
+extern "C" int lora_amd_conv_up_fwd_rowscale(void *y, const float *t, const void *up, int32_t B, int32_t C_out,
+                                             int32_t H, int32_t W, int32_t r, int32_t act_dtype, int32_t factor_dtype,
+                                             float scale, const float *row_scale, int32_t nsel, int64_t rows_per_sample,
+                                             float dropout_p, uint64_t seed, uint64_t offset, void *stream) {
+  LORA_AMD_CHECK(nsel >= 1, LORA_AMD_EINVAL, "conv_up_fwd_rowscale: nsel %d < 1", nsel);
+  LORA_AMD_CHECK(rows_per_sample >= 1, LORA_AMD_EINVAL, "conv_up_fwd_rowscale: rows_per_sample %lld < 1",
+                 (long long)rows_per_sample);
+  const ConvGeo q = conv_geo(B, 0, C_out, H, W, 1, r);
+  CONV_COMMON("conv_up_fwd_rowscale", C_out);
+  LORA_AMD_CHECK(y && t && up && row_scale && al16(y) && al16(t), LORA_AMD_EINVAL,
+                 "conv_up_fwd_rowscale: null or unaligned pointer");
+  LORA_AMD_CHECK(dropout_p >= 0.f && dropout_p < 1.f, LORA_AMD_EINVAL, "conv_up_fwd_rowscale: dropout p=%f", dropout_p);
+  hipStream_t st = (hipStream_t)stream;
+  const int S = stream_split(q.ngroups_out, C_out);
+  const int cps = (C_out + S - 1) / S;
+  const dim3 grid((unsigned)q.ngroups_out, (unsigned)S);
+  const int RT = r <= 4 ? 4 : r <= 8 ? 8 : 16;
+  const bool drop = dropout_p > 0.f;
+  const int HW = H * W;
+#define CU(E, RTV, D)                                                                                              \
+  hipLaunchKernelGGL((conv_up_fwd_kernel<E, RTV, D, true>), grid, dim3(kCT), 0, st,                                 \
+                     reinterpret_cast<typename E::storage *>(y), t, reinterpret_cast<const float *>(up), B, C_out,   \
+                     HW, r, 64, q.NP, cps, scale, dropout_p, seed, offset, nullptr, row_scale, nsel, rows_per_sample)
+#define CU_RT(E, D) do { if (RT == 4) CU(E, 4, D); else if (RT == 8) CU(E, 8, D); else CU(E, 16, D); } while (0)
+#define CU_E(E) do { if (drop) CU_RT(E, true); else CU_RT(E, false); } while (0)
+  switch (act_dtype) {
+    case LORA_AMD_F32: CU_E(f32_t); break;
+    case LORA_AMD_F16: CU_E(f16_t); break;
+    default: CU_E(bf16_t); break;
+  }
+#undef CU_E
+#undef CU_RT
+#undef CU
+  return check_launch("lora_amd_conv_up_fwd_rowscale");
 }
 
 extern "C" int lora_amd_conv_bwd_g(const void *g, const float *t, const void *up, const float *sel, float *gt_part,

@@ -18,6 +18,10 @@
 //     into the accumulators; bias is added, the tile is transposed through LDS and leaves as 16-byte row stores.
 // Dropout (p > 0) and the selector keep the two-launch path (linear_fused.hip): the mask applies to the low-rank term
 // alone, which this kernel never materialises.
+// Per-sample multipliers (RSC, lora_amd_linear_gemm_fwd_rowscale): row m multiplies its T row by
+// row_scale[((m / rows_per_sample) % nsel) * r + j] in f32 where T is rounded into the LDS tile — a diagonal selector
+// (and / or an alpha) per sample of the batch at no extra pass.  RSC = false keeps the existing code path (same
+// registers, same occupancy; the extra arguments are unused).
 #include <algorithm>
 
 #include "common.hpp"
@@ -89,12 +93,13 @@ __device__ inline void raw_barrier() { asm volatile("s_barrier" ::: "memory"); }
 // operation of the K loop is an LDS-DMA (X, W and the f32 `down` slab), issued in the same number L per wave and
 // step, so "step i has landed" is the counted `s_waitcnt vmcnt((NS-2)*L)` of each wave followed by ONE raw s_barrier
 // per step (which also says that everybody is done reading the slot about to be refilled).
-template <class E, int RS, int CS, int NS, int RG>
+template <class E, int RS, int CS, int NS, int RG, bool RSC>
 __global__ __launch_bounds__(kGT) void linear_gemm_fwd_kernel(
     const typename E::storage *__restrict__ x, int64_t ldx, const typename E::storage *__restrict__ w, int64_t ldw,
     const typename E::storage *__restrict__ bias, typename E::storage *__restrict__ y, int64_t ldy,
     const float *__restrict__ down, const float *__restrict__ up, float *__restrict__ t_out, int64_t M, int K, int N,
-    int r, float scale, float t_scale, int flayout, int xhc, int xhp, int yhc, int yhp) {
+    int r, float scale, float t_scale, int flayout, int xhc, int xhp, int yhc, int yhp,
+    const float *__restrict__ row_scale, int nsel, int64_t rows_per_sample) {
   using S = typename E::storage;
   using F = typename MfmaT<E>::frag;
   constexpr int BM = 32 * RS, BN = 32 * CS;
@@ -155,7 +160,20 @@ __global__ __launch_bounds__(kGT) void linear_gemm_fwd_kernel(
   for (int p = 0; p < NS - 1; ++p)
     if (p < nk) ISSUE(p, p);
 
-  // operands of the epilogue, fetched while the first slabs fly: (scale * up) B fragments and the bias
+  // operands of the epilogue, fetched while the first slabs fly: (scale * up) B fragments and the bias (and with RSC the
+  // multipliers of the T elements this lane parks: rows row_base + i, rank l15 — one 32-bit division per row, here)
+  float rsv[TS][4];
+#pragma unroll
+  for (int q = 0; q < TS; ++q)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      rsv[q][i] = 1.f;
+      if (RSC && t_owner && 2 * q + wn < RS) {
+        const int64_t m = m0 + (wm * RS + 2 * q + wn) * 16 + lg * 4 + i;
+        const uint32_t mm = (uint32_t)(m < M ? m : M - 1);
+        rsv[q][i] = row_scale[((mm / (uint32_t)rows_per_sample) % (uint32_t)nsel) * r + (l15 < r ? l15 : r - 1)];
+      }
+    }
   F ub[CS];
   float bv[CS];
 #pragma unroll
@@ -256,8 +274,10 @@ __global__ __launch_bounds__(kGT) void linear_gemm_fwd_kernel(
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int rl = row_base + i;
-        reinterpret_cast<S *>(ts)[rl * 16 + l15] = E::from_f(tacc[q][i]);
-        if (blockIdx.x == 0 && l15 < r && m0 + rl < M) t_out[(m0 + rl) * r + l15] = t_scale * tacc[q][i];
+        // RSC: the sample's multiplier of rank l15 (rows past M / ranks past r: clamped reads, never stored)
+        reinterpret_cast<S *>(ts)[rl * 16 + l15] = E::from_f(RSC ? tacc[q][i] * rsv[q][i] : tacc[q][i]);
+        if ((!RSC || t_out != nullptr) && blockIdx.x == 0 && l15 < r && m0 + rl < M)
+          t_out[(m0 + rl) * r + l15] = t_scale * tacc[q][i];
       }
     }
   }
@@ -311,6 +331,48 @@ __global__ __launch_bounds__(kGT) void linear_gemm_fwd_kernel(
   }
 }
 
+// The launch of both entry points: tile = 10 * stages + shape;  shape: 1 = 64x320, 2 = 64x160, 3 = 32x160,
+// 4 = 128x160 output tile per workgroup, stages: 2 or 3 LDS ring slots (0 -> 2).  tile == 0: the largest tile that
+// still gives every CU a workgroup.
+template <bool RSC>
+static int launch_gemm_fwd(const void *x, int64_t ldx, const void *w, int64_t ldw, const void *bias, void *y,
+                           int64_t ldy, const float *down, const float *up, float *t_out, int64_t M, int32_t K,
+                           int32_t N, int32_t r, int32_t act_dtype, float scale, float t_scale, int32_t factor_layout,
+                           int32_t tile, int xhc, int xhp, int yhc, int yhp, const float *row_scale, int32_t nsel,
+                           int64_t rows_per_sample, void *stream, const char *what) {
+  int shape = tile % 10, stages = tile / 10;
+  if (stages != 3) stages = 2;
+  if (shape <= 0 || shape > 4) {
+    auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * (int64_t)((N + bn - 1) / bn); };
+    shape = blocks(128, 160) >= 512 ? 4 : blocks(64, 160) >= 256 ? 2 : 3;
+  }
+  const int rg = r <= 4 ? 1 : 4;
+  hipStream_t st = (hipStream_t)stream;
+#define GF(E, RSV, CSV, NSV, RGV)                                                                                  \
+  hipLaunchKernelGGL((linear_gemm_fwd_kernel<E, RSV, CSV, NSV, RGV, RSC>),                                         \
+                     dim3((unsigned)((N + 32 * CSV - 1) / (32 * CSV)), (unsigned)((M + 32 * RSV - 1) / (32 * RSV))), \
+                     dim3(kGT), 0, st, reinterpret_cast<const typename E::storage *>(x), ldx,                      \
+                     reinterpret_cast<const typename E::storage *>(w), ldw,                                        \
+                     reinterpret_cast<const typename E::storage *>(bias), reinterpret_cast<typename E::storage *>(y), \
+                     ldy, down, up, t_out, M, K, N, r, scale, t_scale, factor_layout, xhc, xhp, yhc, yhp, row_scale, \
+                     nsel, rows_per_sample)
+#define GF_R(E, RSV, CSV, NSV) do { if (rg == 1) GF(E, RSV, CSV, NSV, 1); else GF(E, RSV, CSV, NSV, 4); } while (0)
+#define GF_S(E, RSV, CSV) do { if (stages == 3) GF_R(E, RSV, CSV, 3); else GF_R(E, RSV, CSV, 2); } while (0)
+#define GF_T(E)                                                                        \
+  do {                                                                                 \
+    if (shape == 1) { if (stages == 3 && rg == 4) GF(E, 2, 10, 2, 4); else GF_S(E, 2, 10); } \
+    else if (shape == 2) GF_S(E, 2, 5);                                                \
+    else if (shape == 3) GF_S(E, 1, 5);                                                \
+    else GF_S(E, 4, 5);                                                                \
+  } while (0)
+  if (act_dtype == LORA_AMD_BF16) GF_T(bf16_t); else GF_T(f16_t);
+#undef GF_T
+#undef GF_S
+#undef GF_R
+#undef GF
+  return check_launch(what);
+}
+
 }  // namespace lora_amd
 
 using namespace lora_amd;
@@ -349,36 +411,28 @@ extern "C" int lora_amd_linear_gemm_fwd_heads(const void *x, int64_t ldx, const 
   auto al = [](const void *p, int64_t ld) { return ((uintptr_t)p % 16) == 0 && ld % 8 == 0; };
   LORA_AMD_CHECK(al(x, ldx) && al(w, ldw) && al(y, ldy) && ((uintptr_t)down % 16) == 0, LORA_AMD_EINVAL,
                  "linear_gemm_fwd: rows must be 16-byte aligned");
-  // tile = 10 * stages + shape;  shape: 1 = 64x320, 2 = 64x160, 3 = 32x160, 4 = 128x160 output tile per workgroup,
-  // stages: 2 or 3 LDS ring slots (0 -> 2).  tile == 0: the largest tile that still gives every CU a workgroup.
-  int shape = tile % 10, stages = tile / 10;
-  if (stages != 3) stages = 2;
-  if (shape <= 0 || shape > 4) {
-    auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * (int64_t)((N + bn - 1) / bn); };
-    shape = blocks(128, 160) >= 512 ? 4 : blocks(64, 160) >= 256 ? 2 : 3;
-  }
-  const int rg = r <= 4 ? 1 : 4;
-  hipStream_t st = (hipStream_t)stream;
-#define GF(E, RSV, CSV, NSV, RGV)                                                                                  \
-  hipLaunchKernelGGL((linear_gemm_fwd_kernel<E, RSV, CSV, NSV, RGV>),                                              \
-                     dim3((unsigned)((N + 32 * CSV - 1) / (32 * CSV)), (unsigned)((M + 32 * RSV - 1) / (32 * RSV))), \
-                     dim3(kGT), 0, st, reinterpret_cast<const typename E::storage *>(x), ldx,                      \
-                     reinterpret_cast<const typename E::storage *>(w), ldw,                                        \
-                     reinterpret_cast<const typename E::storage *>(bias), reinterpret_cast<typename E::storage *>(y), \
-                     ldy, down, up, t_out, M, K, N, r, scale, t_scale, factor_layout, xhc, xhp, yhc, yhp)
-#define GF_R(E, RSV, CSV, NSV) do { if (rg == 1) GF(E, RSV, CSV, NSV, 1); else GF(E, RSV, CSV, NSV, 4); } while (0)
-#define GF_S(E, RSV, CSV) do { if (stages == 3) GF_R(E, RSV, CSV, 3); else GF_R(E, RSV, CSV, 2); } while (0)
-#define GF_T(E)                                                                        \
-  do {                                                                                 \
-    if (shape == 1) { if (stages == 3 && rg == 4) GF(E, 2, 10, 2, 4); else GF_S(E, 2, 10); } \
-    else if (shape == 2) GF_S(E, 2, 5);                                                \
-    else if (shape == 3) GF_S(E, 1, 5);                                                \
-    else GF_S(E, 4, 5);                                                                \
-  } while (0)
-  if (act_dtype == LORA_AMD_BF16) GF_T(bf16_t); else GF_T(f16_t);
-#undef GF_T
-#undef GF_S
-#undef GF_R
-#undef GF
-  return check_launch("lora_amd_linear_gemm_fwd");
+  return launch_gemm_fwd<false>(x, ldx, w, ldw, bias, y, ldy, down, up, t_out, M, K, N, r, act_dtype, scale, t_scale,
+                                factor_layout, tile, xhc, xhp, yhc, yhp, nullptr, 1, 1, stream, "lora_amd_linear_gemm_fwd");
+}
+
+extern "C" int lora_amd_linear_gemm_fwd_rowscale(const void *x, int64_t ldx, const void *w, int64_t ldw,
+                                                 const void *bias, void *y, int64_t ldy, const float *down,
+                                                 const float *up, float *t_out, int64_t M, int32_t K, int32_t N,
+                                                 int32_t r, int32_t act_dtype, float scale, const float *row_scale,
+                                                 int32_t nsel, int64_t rows_per_sample, int32_t tile, void *stream) {
+  LORA_AMD_CHECK(nsel >= 1, LORA_AMD_EINVAL, "linear_gemm_fwd_rowscale: nsel %d < 1", nsel);
+  LORA_AMD_CHECK(rows_per_sample >= 1, LORA_AMD_EINVAL, "linear_gemm_fwd_rowscale: rows_per_sample %lld < 1",
+                 (long long)rows_per_sample);
+  LORA_AMD_CHECK(r >= 1 && r <= 16, LORA_AMD_ERANK, "linear_gemm_fwd_rowscale: rank %d outside [1,16]", r);
+  LORA_AMD_CHECK(M < ((int64_t)1 << 31), LORA_AMD_EINVAL, "linear_gemm_fwd_rowscale: M %lld >= 2^31", (long long)M);
+  LORA_AMD_CHECK(lora_amd_linear_gemm_supported(M, K, N, r, act_dtype), LORA_AMD_EINVAL,
+                 "linear_gemm_fwd_rowscale: needs bf16/f16 activations, K %% 64 == 0, N %% 8 == 0");
+  LORA_AMD_CHECK(x && w && y && down && up && row_scale, LORA_AMD_EINVAL, "linear_gemm_fwd_rowscale: null pointer");
+  auto al = [](const void *p, int64_t ld) { return ((uintptr_t)p % 16) == 0 && ld % 8 == 0; };
+  LORA_AMD_CHECK(al(x, ldx) && al(w, ldw) && al(y, ldy) && ((uintptr_t)down % 16) == 0 && ldx >= K && ldw >= K &&
+                     ldy >= N,
+                 LORA_AMD_EINVAL, "linear_gemm_fwd_rowscale: rows must be dense and 16-byte aligned");
+  return launch_gemm_fwd<true>(x, ldx, w, ldw, bias, y, ldy, down, up, t_out, M, K, N, r, act_dtype, scale, 1.f, 0,
+                               tile, 0, 0, 0, 0, row_scale, nsel, std::min<int64_t>(rows_per_sample, M), stream,
+                               "lora_amd_linear_gemm_fwd_rowscale");
 }

@@ -251,11 +251,14 @@ __global__ __launch_bounds__(kThreads) void rowdot_generic_kernel(
 // tile's T rows live in LDS; lanes walk the tile's 16-byte chunks in flat order
 // (perfectly coalesced when ldy == N), 4 chunks in flight per lane.
 // ---------------------------------------------------------------------------
-template <class EY, int RT, bool DROP>
+// RSC (lora_amd_rank_update_rowscale): row m's T row is multiplied by row_scale[((m / rps) % nsel) * r + j] as it is
+// staged (a per-sample diagonal selector / alpha); RSC = false keeps the existing code path.
+template <class EY, int RT, bool DROP, bool RSC = false>
 __global__ __launch_bounds__(kThreads) void rank_update_kernel(
     typename EY::storage *__restrict__ y, int64_t ldy, const float *__restrict__ t,
     const void *__restrict__ f, int fdt, int layout, int64_t M, int N, int r, int rows_per_tile,
-    int cols_per_tile, int tiles_n, float scale, float p, uint64_t seed, uint64_t offset, const uint64_t *offset_dev) {
+    int cols_per_tile, int tiles_n, float scale, float p, uint64_t seed, uint64_t offset, const uint64_t *offset_dev,
+    const float *__restrict__ row_scale = nullptr, int nsel = 1, int64_t rps = 1) {
   __shared__ __attribute__((aligned(16))) float s_f[kFactorLdsFloats];
   __shared__ __attribute__((aligned(16))) float s_t[kTLdsFloats];
   const int tid = threadIdx.x;
@@ -271,7 +274,9 @@ __global__ __launch_bounds__(kThreads) void rank_update_kernel(
   stage_factor_vec<RT>(s_f, f, fdt, layout, r, N, col0, ncols);
   for (int i = tid; i < nrows * RT; i += kThreads) {
     int rl = i / RT, j = i - rl * RT;
-    s_t[i] = j < r ? t[(row0 + rl) * r + j] : 0.f;
+    float v = j < r ? t[(row0 + rl) * r + j] : 0.f;
+    if (RSC && j < r) v *= row_scale[(((row0 + rl) / rps) % nsel) * r + j];
+    s_t[i] = v;
   }
   __syncthreads();
 
@@ -320,18 +325,22 @@ __global__ __launch_bounds__(kThreads) void rank_update_kernel(
   }
 }
 
-template <class EY, bool DROP>
+template <class EY, bool DROP, bool RSC = false>
 __global__ __launch_bounds__(kThreads) void rank_update_generic_kernel(
     typename EY::storage *__restrict__ y, int64_t ldy, const float *__restrict__ t,
     const void *__restrict__ f, int fdt, int layout, int64_t M, int N, int r, float scale, float p,
-    uint64_t seed, uint64_t offset, const uint64_t *offset_dev) {
+    uint64_t seed, uint64_t offset, const uint64_t *offset_dev, const float *__restrict__ row_scale = nullptr,
+    int nsel = 1, int64_t rps = 1) {
   const int64_t total = M * (int64_t)N;
   for (int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x; e < total; e += (int64_t)gridDim.x * kThreads) {
     const int64_t row = e / N;
     const int col = (int)(e - row * N);
     float a = 0.f;
-    for (int j = 0; j < r; ++j)
-      a = fmaf(t[row * r + j], ld_factor(f, fdt, layout == LORA_AMD_FACTOR_RK ? (int64_t)j * N + col : (int64_t)col * r + j), a);
+    const float *rs = RSC ? row_scale + ((row / rps) % nsel) * r : nullptr;
+    for (int j = 0; j < r; ++j) {
+      const float tj = RSC ? t[row * r + j] * rs[j] : t[row * r + j];
+      a = fmaf(tj, ld_factor(f, fdt, layout == LORA_AMD_FACTOR_RK ? (int64_t)j * N + col : (int64_t)col * r + j), a);
+    }
     if (DROP) {
       float mk[8];
       dropout_mult8(seed, dropout_offset(offset, offset_dev), (uint64_t)e >> 3, p, mk);
@@ -609,17 +618,17 @@ static int launch_rowdot(const void *x, int64_t ldx, const void *f, void *t_out,
   return check_launch("lora_amd_rowdot");
 }
 
-template <class EY, bool DROP>
+template <class EY, bool DROP, bool RSC = false>
 static int launch_rank_update(void *y, int64_t ldy, const float *t, const void *f, int64_t M, int N, int r,
                               int fdt, int layout, float scale, float p, uint64_t seed, uint64_t offset, const uint64_t *offset_dev,
-                              hipStream_t st) {
+                              hipStream_t st, const float *row_scale = nullptr, int nsel = 1, int64_t rps = 1) {
   using S = typename EY::storage;
   S *yp = reinterpret_cast<S *>(y);
   if (!vec_ok(y, ldy, N, EY::kCode)) {
     int64_t total = M * (int64_t)N;
     int grid = (int)std::min<int64_t>((total + kThreads - 1) / kThreads, 4096);
-    hipLaunchKernelGGL((rank_update_generic_kernel<EY, DROP>), dim3(grid), dim3(kThreads), 0, st, yp, ldy, t, f,
-                       fdt, layout, M, N, r, scale, p, seed, offset, offset_dev);
+    hipLaunchKernelGGL((rank_update_generic_kernel<EY, DROP, RSC>), dim3(grid), dim3(kThreads), 0, st, yp, ldy, t, f,
+                       fdt, layout, M, N, r, scale, p, seed, offset, offset_dev, row_scale, nsel, rps);
     return check_launch("lora_amd_rank_update(generic)");
   }
   const int RT = rank_tile(r);
@@ -634,8 +643,9 @@ static int launch_rank_update(void *y, int64_t ldy, const float *t, const void *
   const int tiles_n = (N + cols - 1) / cols;
   const int64_t tiles = tiles_n * ((M + rows - 1) / rows);
 #define RU(RTV)                                                                                            \
-  hipLaunchKernelGGL((rank_update_kernel<EY, RTV, DROP>), dim3((unsigned)tiles), dim3(kThreads), 0, st, yp, ldy, t, \
-                     f, fdt, layout, M, N, r, (int)rows, cols, tiles_n, scale, p, seed, offset, offset_dev)
+  hipLaunchKernelGGL((rank_update_kernel<EY, RTV, DROP, RSC>), dim3((unsigned)tiles), dim3(kThreads), 0, st, yp, ldy, \
+                     t, f, fdt, layout, M, N, r, (int)rows, cols, tiles_n, scale, p, seed, offset, offset_dev, row_scale, \
+                     nsel, rps)
   switch (RT) {
     case 4: RU(4); break;
     case 8: RU(8); break;
@@ -753,6 +763,35 @@ extern "C" int lora_amd_rank_update(void *y, int64_t ldy, const float *t, const 
   return drop ? launch_rank_update<E, true>(y, ldy, t, factor, M, N, r, factor_dtype, factor_layout, scale, \
                                             dropout_p, seed, offset, offset_dev, st)                                   \
               : launch_rank_update<E, false>(y, ldy, t, factor, M, N, r, factor_dtype, factor_layout, scale, 0.f, 0, 0, nullptr, st)
+  switch (y_dtype) {
+    case LORA_AMD_F32: GO(f32_t);
+    case LORA_AMD_F16: GO(f16_t);
+    default: GO(bf16_t);
+  }
+#undef GO
+}
+
+extern "C" int lora_amd_rank_update_rowscale(void *y, int64_t ldy, const float *t, const void *factor, int64_t M,
+                                             int32_t N, int32_t r, int32_t y_dtype, int32_t factor_dtype,
+                                             int32_t factor_layout, float scale, const float *row_scale, int32_t nsel,
+                                             int64_t rows_per_sample, float dropout_p, uint64_t seed, uint64_t offset,
+                                             void *stream) {
+  LORA_AMD_CHECK(nsel >= 1, LORA_AMD_EINVAL, "rank_update_rowscale: nsel %d < 1", nsel);
+  LORA_AMD_CHECK(rows_per_sample >= 1, LORA_AMD_EINVAL, "rank_update_rowscale: rows_per_sample %lld < 1",
+                 (long long)rows_per_sample);
+  COMMON_CHECKS("rank_update_rowscale", M, N, r, y_dtype);
+  LORA_AMD_CHECK(y && t && factor && row_scale, LORA_AMD_EINVAL, "rank_update_rowscale: null pointer");
+  LORA_AMD_CHECK(dtype_ok(factor_dtype), LORA_AMD_EINVAL, "rank_update_rowscale: bad factor dtype %d", factor_dtype);
+  LORA_AMD_CHECK(ldy >= N, LORA_AMD_EINVAL, "rank_update_rowscale: ldy %lld < N %d", (long long)ldy, N);
+  LORA_AMD_CHECK(dropout_p >= 0.f && dropout_p < 1.f, LORA_AMD_EINVAL, "rank_update_rowscale: dropout p=%f", dropout_p);
+  hipStream_t st = (hipStream_t)stream;
+  const bool drop = dropout_p > 0.f;
+#define GO(E)                                                                                                       \
+  return drop ? launch_rank_update<E, true, true>(y, ldy, t, factor, M, N, r, factor_dtype, factor_layout, scale,   \
+                                                  dropout_p, seed, offset, nullptr, st, row_scale, nsel,            \
+                                                  rows_per_sample)                                                  \
+              : launch_rank_update<E, false, true>(y, ldy, t, factor, M, N, r, factor_dtype, factor_layout, scale,  \
+                                                   0.f, 0, 0, nullptr, st, row_scale, nsel, rows_per_sample)
   switch (y_dtype) {
     case LORA_AMD_F32: GO(f32_t);
     case LORA_AMD_F16: GO(f16_t);

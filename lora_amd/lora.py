@@ -80,6 +80,53 @@ class _Adapter(nn.Module):
     def _dropout_p(self) -> float:
         return float(self.dropout.p) if self.dropout.training else 0.0
 
+    # ---- per-sample tables (set_lora_diag_per_sample / tune_lora_scale_per_sample): plain attributes, never parameters
+    # or buffers, so state_dict and the file formats do not see them.  ``_ps_rows`` [n, r] f32 is what the kernels
+    # multiply T by: the diag rows (ones without them) times the alphas (when set, ``scale`` is then 1).
+    def _per_sample(self):
+        """(rows [n, r] f32, diag [n, r] or None, alphas [n] or None) when a per-sample table is set, else None."""
+        rows = self.__dict__.get("_ps_rows")
+        if rows is None:
+            return None
+        return rows, self.__dict__.get("_ps_diag"), self.__dict__.get("_ps_alpha")
+
+    def _ps_rebuild(self) -> None:
+        diag, alpha = self.__dict__.get("_ps_diag"), self.__dict__.get("_ps_alpha")
+        if diag is None and alpha is None:
+            self.__dict__.pop("_ps_rows", None)
+            return
+        if diag is None:
+            rows = alpha[:, None].expand(alpha.shape[0], self.r)
+        else:
+            rows = diag if alpha is None else diag * alpha[:, None]
+        self.__dict__["_ps_rows"] = rows.contiguous()
+
+    def _ps_sample_index(self, x: torch.Tensor, n: int) -> torch.Tensor:
+        B = x.shape[0]
+        if x.dim() < 2 or B % n:
+            raise ValueError(f"per-sample LoRA table of {n} rows: the input's leading dimension {B} must be a multiple "
+                             f"of {n}")
+        return torch.arange(B, device=x.device) % n
+
+    def _ps_branch_cpu(self, x: torch.Tensor, rank_dim: int) -> torch.Tensor:
+        """The plain-torch per-sample branch: sample b as if ``set_lora_diag(diag[b % n])`` / ``tune_lora_scale(
+        alpha[b % n])`` had been called (the reference op sequence, the rows applied where the selector / scale act)."""
+        rows, diag, alpha = self._per_sample()
+        idx = self._ps_sample_index(x, rows.shape[0])
+        low = self.lora_down(x)
+        shape = [x.shape[0]] + [1] * (low.dim() - 1)
+        if diag is not None:
+            shape_r = list(shape)
+            shape_r[rank_dim] = self.r
+            low = low * diag.to(low.device)[idx.to(diag.device)].to(low.dtype).view(shape_r)
+        else:
+            low = self.selector(low)
+        low = self.dropout(self.lora_up(low))
+        if alpha is None:
+            return low * self.scale
+        a = alpha.to(low.device)[idx.to(alpha.device)].view(shape)
+        return low * a if low.dtype == torch.float32 else (low.float() * a).to(low.dtype)
+
     def _shadow(self, t: Optional[torch.Tensor], dt: torch.dtype, slot: str) -> Optional[torch.Tensor]:
         """Frozen tensor in the compute dtype, kept resident instead of re-cast every forward
         (the reference's autocast re-casts every fp32 weight every step, SURVEY.md §3.1 note b).
@@ -102,6 +149,7 @@ class _Adapter(nn.Module):
 
     def _apply(self, fn, *args, **kwargs):  # .to() / .cuda() / .half(): every derived layout is stale
         self.__dict__.pop("_shadow_cache", None)
+        self.__dict__.pop("_ps_cache", None)
         _C.invalidate_weight_caches()
         return super()._apply(fn, *args, **kwargs)
 
@@ -139,6 +187,8 @@ class LoraInjectedLinear(_Adapter):
     def forward(self, input):
         if input.is_cuda:
             return self._forward_device(input)
+        if self._per_sample() is not None:
+            return self.linear(input) + self._ps_branch_cpu(input, -1)
         # CPU plumbing path: the reference's op sequence (ref:53-58)
         low = self.lora_up(self.selector(self.lora_down(input)))
         return self.linear(input) + self.dropout(low) * self.scale
@@ -148,6 +198,13 @@ class LoraInjectedLinear(_Adapter):
         dt = _autocast_dtype(x, w)
         xc = x if x.dtype == dt else x.to(dt)
         wc, bc = self._shadow(w, dt, "w"), self._shadow(b, dt, "b")
+        ps = self._per_sample()
+        if ps is not None:  # one setting per sample (forward only): the rowscale kernels; never the merged / head routes
+            rows, diag, alpha = ps
+            with torch.autocast(device_type=x.device.type, enabled=False):
+                return ops.lora_linear_per_sample(xc, wc, bc, self.lora_down.weight, self.lora_up.weight,
+                                                  self._selector_matrix() if diag is None else None,
+                                                  1.0 if alpha is not None else self.scale, self._dropout_p(), rows)
         with torch.autocast(device_type=x.device.type, enabled=False):
             mw = self.__dict__.get("_merged")
             if mw is not None and ops.merged_ok(xc, wc, self.lora_down.weight, self.lora_up.weight,
@@ -168,8 +225,9 @@ class LoraInjectedLinear(_Adapter):
         say that the input arrives / the output leaves with every head's d columns padded to D, the layout the
         attention kernels want for head sizes 40 / 80.  On the device the fused kernels read and write that layout
         themselves (no pad / slice copies); everywhere else this is unpack -> forward -> pack."""
-        if input.is_cuda:
+        if input.is_cuda and self._per_sample() is None:
             return self._forward_device(input, in_heads, out_heads)
+        # per-sample tables take the dense detour (the rowscale kernels read dense rows)
         y = self.forward(ops.unpack_heads(input, in_heads) if in_heads else input)
         return ops.pack_heads(y, out_heads) if out_heads else y
 
@@ -189,6 +247,8 @@ def lora_linear_group(adapters, x: torch.Tensor, out_heads=None):
     ``forward`` on the fused path (same kernels, same rounding points)."""
     if not x.is_cuda or len(adapters) < 2 or not all(isinstance(a, LoraInjectedLinear) for a in adapters):
         return None
+    if any(a._per_sample() is not None for a in adapters):
+        return None  # per-sample tables: every adapter on its own rowscale route
     if all(a.__dict__.get("_merged") is not None for a in adapters):
         # merged-weight path: every site is a dense GEMM on its own merged weight; grouped so that the sites' input
         # gradients accumulate inside the GEMMs (``out_heads``: the outputs leave in the padded head layout)
@@ -263,6 +323,8 @@ class LoraInjectedConv2d(_Adapter):
     def forward(self, input):
         if input.is_cuda:
             return self._forward_device(input)
+        if self._per_sample() is not None:
+            return self.conv(input) + self._ps_branch_cpu(input, 1)
         low = self.lora_up(self.selector(self.lora_down(input)))  # ref:130-135
         return self.conv(input) + self.dropout(low) * self.scale
 
@@ -272,6 +334,14 @@ class LoraInjectedConv2d(_Adapter):
         xc = x if x.dtype == dt else x.to(dt)
         wc, bc = self._shadow(w, dt, "w"), self._shadow(b, dt, "b")
         c = self.conv
+        ps = self._per_sample()
+        if ps is not None:
+            rows, diag, alpha = ps
+            with torch.autocast(device_type=x.device.type, enabled=False):
+                return ops.lora_conv_per_sample(xc, wc, bc, self.lora_down.weight, self.lora_up.weight,
+                                                self._selector_matrix() if diag is None else None, c.stride, c.padding,
+                                                c.dilation, c.groups, 1.0 if alpha is not None else self.scale,
+                                                self._dropout_p(), rows, self.__dict__.setdefault("_ps_cache", {}))
         with torch.autocast(device_type=x.device.type, enabled=False):
             return ops.lora_conv(xc, wc, bc, self.lora_down.weight, self.lora_up.weight, self._selector_matrix(),
                                  c.stride, c.padding, c.dilation, c.groups, self.scale, self._dropout_p(),
@@ -653,6 +723,60 @@ def set_lora_diag(model, diag: torch.Tensor):  # ref:883-886
     for m in model.modules():
         if type(m).__name__ in _ADAPTER_NAMES:
             m.set_selector_from_diag(diag)
+
+
+def _all_adapters(model):
+    return [m for m in model.modules() if type(m).__name__ in _ADAPTER_NAMES]
+
+
+def _ps_table(values, what: str, ndim: int) -> torch.Tensor:
+    t = torch.as_tensor(values)
+    if t.dim() != ndim or t.shape[0] < 1 or t.numel() == 0:
+        raise ValueError(f"{what}: expected a {'[n, r]' if ndim == 2 else '[n]'} table, got shape {tuple(t.shape)}")
+    if not (t.is_floating_point() or t.dtype in (torch.int32, torch.int64)):
+        raise ValueError(f"{what}: expected a real-valued table, got {t.dtype}")
+    return t.detach()
+
+
+def _ps_install(model, attr: str, table: torch.Tensor, what: str) -> None:
+    adapters = _all_adapters(model)
+    n = table.shape[0]
+    for m in adapters:  # every check before anything changes
+        if attr == "_ps_diag" and table.shape[1] != m.r:
+            raise ValueError(f"{what}: table has {table.shape[1]} columns, an adapter has rank {m.r}")
+        other = m.__dict__.get("_ps_alpha" if attr == "_ps_diag" else "_ps_diag")
+        if other is not None and other.shape[0] != n:
+            raise ValueError(f"{what}: {n} rows, but the other per-sample table of this model has {other.shape[0]}")
+    copies = {}  # one device copy per (device, rank): built here, never in the forward
+    for m in adapters:
+        dev = m.lora_up.weight.device
+        key = (str(dev), table.shape[1] if table.dim() == 2 else 0)
+        if key not in copies:
+            copies[key] = table.to(device=dev, dtype=torch.float32).contiguous()
+        m.__dict__[attr] = copies[key]
+        m._ps_rebuild()
+
+
+def set_lora_diag_per_sample(model, diags) -> None:
+    """Per-sample selectors: sample ``b`` of any batch (``b`` = the input's leading index) runs every adapter of
+    ``model`` as if ``set_lora_diag(model, diags[b % n])`` had been called.  ``diags``: [n, r].  The ``b % n`` rule keeps a
+    classifier-free-guidance batch ``[uncond x n, cond x n]`` on the same setting in both halves; the batch must be a
+    multiple of ``n``.  The table is a plain attribute (not in ``state_dict`` / saved files); device forwards run the
+    rowscale kernels and are forward-only.  :func:`clear_lora_per_sample` undoes it."""
+    _ps_install(model, "_ps_diag", _ps_table(diags, "set_lora_diag_per_sample", 2), "set_lora_diag_per_sample")
+
+
+def tune_lora_scale_per_sample(model, alphas) -> None:
+    """Per-sample alphas: sample ``b`` runs as if ``tune_lora_scale(model, alphas[b % n])`` had been called (``alphas``:
+    [n]).  Combines with :func:`set_lora_diag_per_sample` (both rows apply to the sample); same batch rule."""
+    _ps_install(model, "_ps_alpha", _ps_table(alphas, "tune_lora_scale_per_sample", 1), "tune_lora_scale_per_sample")
+
+
+def clear_lora_per_sample(model) -> None:
+    """Drop every per-sample table: the adapters compute exactly what they did before one was set."""
+    for m in _all_adapters(model):
+        for attr in ("_ps_diag", "_ps_alpha", "_ps_rows", "_ps_cache"):
+            m.__dict__.pop(attr, None)
 
 
 # legacy names used by the reference's notebooks (SURVEY.md §2 #22)

@@ -8,7 +8,8 @@ from typing import List
 
 import torch
 
-from .lora import (apply_learned_embed_in_clip, monkeypatch_or_replace_safeloras, parse_safeloras_embeds, set_lora_diag)
+from .lora import (apply_learned_embed_in_clip, monkeypatch_or_replace_safeloras, parse_safeloras_embeds, set_lora_diag,
+                   set_lora_diag_per_sample)
 
 try:
     from safetensors import safe_open
@@ -99,6 +100,16 @@ class LoRAManager:
         assert len(scales) == len(self.ranklist), "Scale list should be the same length as ranklist"
         diag = torch.repeat_interleave(torch.as_tensor(scales, dtype=torch.float32), torch.as_tensor(self.ranklist))
         set_lora_diag(self.pipe.unet, diag)
+
+    def tune_per_sample(self, scales):
+        """One member mix per sample: ``scales`` [n, n_members]; sample ``b`` of a UNet batch runs as after
+        ``tune(scales[b % n])`` (each row repeated over the members' rank slices, as ``tune`` does).  One-hot rows serve
+        n different member LoRAs in one batched call.  UNet only, like ``tune``; forward-only on the device."""
+        s = torch.as_tensor(scales, dtype=torch.float32)
+        if s.dim() != 2 or s.shape[1] != len(self.ranklist):
+            raise ValueError(f"tune_per_sample: scales must be [n, {len(self.ranklist)}], got {tuple(s.shape)}")
+        diags = torch.repeat_interleave(s, torch.as_tensor(self.ranklist), dim=1)
+        set_lora_diag_per_sample(self.pipe.unet, diags)
 
     def prompt(self, prompt):
         """``<1>``, ``<2>``, ... expand to the renamed learned tokens of member 1, 2, ..."""

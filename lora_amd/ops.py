@@ -1794,6 +1794,163 @@ def lora_conv_branch(x, y0, down_w, up_w, sel, stride, padding, dilation, groups
     return LoraConvUpFunction.apply(y0, t, up_w, float(scale), float(dropout_p))
 
 
+# --------------------------------------------------------------------------- per-sample tables (forward only)
+# A batch whose samples carry their own LoRA setting (lora.set_lora_diag_per_sample / tune_lora_scale_per_sample): row m
+# of a site multiplies its T = X down^T row by rows[(m // rows_per_sample) % n] before T meets `up`.  Two routes:
+#   * PS_RING: the LDS-ring kernel with the multiplier in its epilogue (lora_amd_linear_gemm_fwd_rowscale, one launch);
+#   * PS_LIB: library GEMM + rowdot (T, the module's selector if it keeps one) + lora_amd_rank_update_rowscale — any rank,
+#     dropout, the shapes the ring kernel refuses, and the channels-last conv sites (T from the 3x3 down-conv kernel).
+# NCHW conv sites: conv_down_fwd + lora_amd_conv_up_fwd_rowscale (the multiplier where the T planes are loaded).
+PS_LIB, PS_RING = 0, 1
+
+
+def static_rowscale_choice(M: int, K: int, N: int, ring_ok: bool) -> int:
+    """Route of a per-sample Linear site: a fixed function of the shape, like ``_C.static_fwd_choice``.  Table from
+    scripts/kbench_per_sample.py --what kernel on MI355X, batch 8, rank 4, us per call ring-rowscale / library route:
+        (32768,320,320) 24.7 / 41.7      (32768,320,2560) 145 / 172     (8192,640,640) 23.1 / 35.3
+        (8192,640,5120) 114 / 123        (2048,1280,1280) 31.8 / 43.0   (2048,1280,10240) 97.7 / 100
+        (512,1280,1280) 24.0 / 28.7      (616,768,320) 16.6 / 19.1      (616,768,1280) 17.0 / 24.4
+        (8,1280,320) 23.0 / 16.9         (8,1280,1280) 23.3 / 21.0
+    i.e. the ring kernel from a few hundred rows up (the weight-stationary kernel of today's table has no per-sample form;
+    the library route is one launch more than the two-launch path), the library GEMM for the time-embedding rows."""
+    return PS_RING if ring_ok and M >= 256 else PS_LIB
+
+
+def _ps_forward_only(*ts) -> None:
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise RuntimeError("lora_amd: per-sample LoRA tables are forward-only on the device; run under torch.no_grad() "
+                           "(or clear_lora_per_sample(model) to train)")
+
+
+def _ps_rows_per_sample(x: torch.Tensor, cols: int, n: int) -> int:
+    B = x.shape[0] if x.dim() >= 2 else 0
+    if B == 0 or B % n:
+        raise ValueError(f"per-sample LoRA table of {n} rows: the input's leading dimension {B if x.dim() else 0} must "
+                         f"be a multiple of {n}")
+    return x.numel() // (B * cols)
+
+
+def _ps_dropout(p: float):
+    """(seed, offset) of a forward-only mask: a host-side draw (no device tensor, no copy to the device)."""
+    if p <= 0.0:
+        return 0, 0
+    return int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF, int(torch.randint(0, 1 << 62, (1,)).item())
+
+
+def rank_update_rowscale_any_(y, t, f, layout, scale, rows, rows_per_sample, p=0.0, seed=0, off=0):
+    """``_C.rank_update_rowscale_`` for any rank: rank chunks of <= 64 with their columns of the table (no dropout beyond
+    64: the mask belongs to the sum over ranks)."""
+    r = t.shape[1]
+    if r <= _C.MAX_RANK:
+        return _C.rank_update_rowscale_(y, t, f, layout, scale, rows, rows_per_sample, p, seed, off)
+    if p > 0.0:
+        raise RuntimeError(f"lora_amd: per-sample route with dropout active needs rank <= {_C.MAX_RANK}, got {r}")
+    for a, b in _rank_chunks(r):
+        _C.rank_update_rowscale_(y, t[:, a:b].contiguous(), _slice_factor(f, layout, a, b), layout, scale,
+                                 rows[:, a:b].contiguous(), rows_per_sample)
+    return y
+
+
+def lora_linear_per_sample(x, weight, bias, down, up, sel, scale, dropout_p, rows):
+    """LoraInjectedLinear forward with a per-sample table ``rows`` [n, r] (f32, device) — forward only.  ``sel``: the
+    module's own selector where no per-sample diag replaces it; ``scale``: 1 when the rows carry the alphas."""
+    _C.require()
+    _ps_forward_only(x, weight, bias, down, up)
+    N, K = weight.shape
+    r = down.shape[0]
+    rps = _ps_rows_per_sample(x, K, rows.shape[0])
+    x2 = _rows2d(x, K)
+    M = x2.shape[0]
+    down_c, up_c = down.contiguous(), up.contiguous()
+    route = PS_LIB
+    if (sel is None and dropout_p == 0.0 and down_c.dtype == torch.float32 and up_c.dtype == torch.float32
+            and x2.dtype in (torch.bfloat16, torch.float16) and weight.dtype == x2.dtype):
+        route = static_rowscale_choice(M, K, N, _C.gemm_supported(x2, weight, N, r) and weight.stride(0) >= K)
+    if route == PS_RING:
+        y = _C.linear_gemm_fwd_rowscale(x2, weight, bias, down_c, up_c, scale, rows, rps)
+        _log("fwd", "ps_ring", M, K, N, r)
+    else:
+        y = F.linear(x2, weight, bias)  # frozen dense GEMM (hipBLASLt)
+        if not _C._rows_ok(y):
+            y = y.contiguous()
+        t = rowdot_any(x2, down_c, _C.FACTOR_RK, 1.0, sel, False)
+        seed, off = _ps_dropout(dropout_p)
+        rank_update_rowscale_any_(y, t, up_c, _C.FACTOR_KR, scale, rows, rps, dropout_p, seed, off)
+        _log("fwd", "ps_lib", M, K, N, r)
+    return y.view(*x.shape[:-1], N)
+
+
+def _ps_conv3_pack(cache: dict, down: torch.Tensor, dt: torch.dtype, plan) -> torch.Tensor:
+    """The 3x3 down factor in the NHWC kernel's fragment order, packed once per factor version (inference reuses it)."""
+    key = (down.data_ptr(), _C._tensor_version(down), dt, int(plan.pf_elems))
+    hit = cache.get("pf")
+    if hit is not None and hit[0] is down and hit[1] == key:
+        return hit[2]
+    pf = _C.conv3_nhwc_pack(down.detach().float().contiguous(), dt, plan)[0]
+    cache["pf"] = (down, key, pf)
+    return pf
+
+
+def lora_conv_per_sample(x, weight, bias, down_w, up_w, sel, stride, padding, dilation, groups, scale, dropout_p, rows,
+                         cache):
+    """LoraInjectedConv2d forward with a per-sample table (sample = the B index): channels-last 1x1 as the Linear route on
+    the pixel rows, channels-last 3x3 as down-conv kernel + rank_update_rowscale on the [B*H*W, C_out] rows, NCHW native
+    geometries as conv_down_fwd + conv_up_fwd_rowscale, anything else library down-conv + rank_update_rowscale per image."""
+    _C.require()
+    _ps_forward_only(x, weight, bias, down_w, up_w)
+    n = rows.shape[0]
+    B, Ci, H, W = x.shape
+    if B % n:
+        raise ValueError(f"per-sample LoRA table of {n} rows: the input's leading dimension {B} must be a multiple of {n}")
+    Co, r = weight.shape[0], down_w.shape[0]
+    up2 = up_w.reshape(Co, r).float().contiguous()
+    seed, off = _ps_dropout(dropout_p)
+    if down_w.dtype == up_w.dtype and conv_nhwc_ok(x, weight, r, stride, padding, dilation, groups):
+        if weight.shape[2] == 1:
+            y = lora_linear_per_sample(x.permute(0, 2, 3, 1), weight.reshape(Co, Ci), bias, down_w.reshape(r, Ci),
+                                       up_w.reshape(Co, r), sel, scale, dropout_p, rows)
+            return y.permute(0, 3, 1, 2)
+        y = F.conv2d(x, weight, bias, 1, 1)  # frozen dense conv (MIOpen)
+        if not y.is_contiguous(memory_format=torch.channels_last):
+            y = y.contiguous(memory_format=torch.channels_last)
+        plan = _C.conv3_nhwc_plan(B, Ci, H, W, r)
+        t = _C.conv3_nhwc_down_fwd(x, _ps_conv3_pack(cache, down_w, x.dtype, plan), r)
+        if sel is not None:
+            t = (t @ sel.float().t()).contiguous()
+        rank_update_rowscale_any_(y.permute(0, 2, 3, 1).view(B * H * W, Co), t, up2, _C.FACTOR_KR, scale, rows, H * W,
+                                  dropout_p, seed, off)
+        _log("fwd", "ps_conv3_nhwc", B * H * W, Ci * 9, Co, r)
+        return y
+    if down_w.dtype == up_w.dtype and r <= 16 and conv_native_ok(x, weight, r, stride, padding, dilation, groups):
+        ks = int(weight.shape[2])
+        x = x.contiguous()
+        y = F.conv2d(x, weight, bias, 1, (ks - 1) // 2)
+        if not y.is_contiguous():
+            y = y.contiguous()
+        plan = _C.conv_plan(B, Ci, Co, H, W, ks, r)
+        t_part = torch.empty(max(int(plan.t_part_floats), 1), dtype=torch.float32, device=x.device)
+        t = torch.empty((B, r, H, W), dtype=torch.float32, device=x.device)
+        sel_c = sel.to(torch.float32).contiguous() if sel is not None else None
+        _C.conv_down_fwd(x, down_w.float().contiguous(), sel_c, t_part, t, ks)
+        _C.conv_up_fwd_rowscale_(y, t, up2, scale, rows, dropout_p, seed, off)
+        _log("fwd", "ps_conv_nchw", B * H * W, Ci * ks * ks, Co, r)
+        return y
+    y = F.conv2d(x, weight, bias, stride, padding, dilation, groups)
+    if not y.is_contiguous():
+        y = y.contiguous()
+    t = F.conv2d(x, down_w if down_w.dtype == x.dtype else down_w.to(x.dtype), None, stride, padding, dilation, groups)
+    if sel is not None:
+        t = F.conv2d(t, sel.reshape(r, r, 1, 1).to(t.dtype))
+    t = t.float().contiguous()
+    Ho, Wo = y.shape[2], y.shape[3]
+    for b in range(B):  # Y_b [C_out, HW] += scale * (up o rows[b % n]) T_b: the rank_update roles of the NCHW branch
+        q = b % n
+        rank_update_rowscale_any_(y[b].view(Co, Ho * Wo), up2, t[b].view(r, Ho * Wo), _C.FACTOR_RK, scale,
+                                  rows[q:q + 1], Co, dropout_p, seed, off)
+    _log("fwd", "ps_conv_generic", B * Ho * Wo, Ci, Co, r)
+    return y
+
+
 def merge_sites(sites, alpha: float = 1.0, rounding: int = _C.ROUND_REFERENCE) -> None:
     """One launch per (weight dtype, factor dtype) group: w_out = w_in + alpha * up @ down."""
     groups = {}
