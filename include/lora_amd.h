@@ -99,7 +99,8 @@ typedef struct lora_amd_merge_summary {
 } lora_amd_merge_summary;
 
 /* Host-side planner: fills rows_per_tile/cols_per_tile/tiles_k/tile_begin/flags of
- * `sites_host[0..n_sites)` and *summary.  Pure CPU arithmetic: callable without a GPU. */
+ * `sites_host[0..n_sites)` and *summary.  Pure CPU arithmetic: callable without a GPU.  The column-owner kernel runs at
+ * the table's largest rank tile (summary->rank_tile_fast), so every column-owner site's rows_per_tile is capped by it. */
 int lora_amd_merge_plan(lora_amd_merge_site *sites_host, int32_t n_sites,
                         int32_t w_dtype, lora_amd_merge_summary *summary);
 
@@ -529,7 +530,9 @@ int lora_amd_linear_gemm_fwd_rowscale(const void *x, int64_t ldx, const void *w,
 
 /* out (f32, [r,C] or [C,r]) = beta*out + scale * sum_p part[p][j][c], part laid out [nparts][RT][C].
  * ONE launch covers every descriptor: the trainer reduces all sites' partials into its flat gradient
- * buffer once per step.  `begin` = exclusive prefix sum of r*C over the table; total = its end. */
+ * buffer once per step.  `begin` = exclusive prefix sum of r*C over the table; total = its end.
+ * Footprint: writes exactly the r*C elements at each descriptor's `out` and reads only rows j < r of its parts (rows
+ * r .. RT-1 of a partial slab may hold anything); descriptors may point at adjacent slices of one buffer. */
 typedef struct lora_amd_reduce_desc {
   const float *part;
   float *out;

@@ -630,8 +630,9 @@ def _as2d(x: torch.Tensor) -> torch.Tensor:
 
 def rowdot(x: torch.Tensor, factor: torch.Tensor, layout: int, scale: float = 1.0,
            sel: Optional[torch.Tensor] = None, sel_transposed: bool = False, dropout_p: float = 0.0,
-           seed: int = 0, offset: int = 0) -> torch.Tensor:
-    """T[M,r] (f32) = scale * (mask*X)[M,K] @ F^T (@ S^T | @ S)."""
+           seed: int = 0, offset: int = 0, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """T[M,r] (f32) = scale * (mask*X)[M,K] @ F^T (@ S^T | @ S).  ``out``: a contiguous f32 [M, r] to write instead of a
+    new tensor."""
     lib = require()
     _dev_check(x, factor, sel)
     x = _as2d(x)
@@ -644,7 +645,12 @@ def rowdot(x: torch.Tensor, factor: torch.Tensor, layout: int, scale: float = 1.
         sel = sel.to(torch.float32).contiguous()
         if sel.shape != (r, r):
             raise ValueError("rowdot: selector must be [r, r]")
-    t = torch.empty((M, r), dtype=torch.float32, device=x.device)
+    if out is None:
+        t = torch.empty((M, r), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (M, r) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"rowdot: out must be a contiguous f32 [{M}, {r}] tensor on {x.device}")
+    else:
+        t = out
     _check(lib.lora_amd_rowdot_masked(x.data_ptr(), x.stride(0), factor.data_ptr(), t.data_ptr(), M, K, r,
                                       dtype_code(x.dtype), dtype_code(factor.dtype), layout, float(scale),
                                       sel.data_ptr() if sel is not None else None, int(bool(sel_transposed)),
@@ -2136,12 +2142,17 @@ def groupnorm_bwd(x: torch.Tensor, gout: torch.Tensor, gamma: torch.Tensor, beta
     return dx
 
 
-def geglu_fwd(y: torch.Tensor) -> torch.Tensor:
-    """out [..., inner] = y[..., :inner] * gelu(y[..., inner:]) for a row-contiguous y [..., 2*inner]."""
-    _dev_check(y)
+def geglu_fwd(y: torch.Tensor, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [..., inner] = y[..., :inner] * gelu(y[..., inner:]) for a row-contiguous y [..., 2*inner].  ``out``: a
+    contiguous tensor of that shape and y's dtype to write instead of a new one."""
+    _dev_check(y, out)
     y2 = _as2d(y.reshape(-1, y.shape[-1]))
     inner = y2.shape[1] // 2
-    out = torch.empty(*y.shape[:-1], inner, dtype=y.dtype, device=y.device)
+    shape = (*y.shape[:-1], inner)
+    if out is None:
+        out = torch.empty(shape, dtype=y.dtype, device=y.device)
+    elif out.dtype != y.dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"geglu_fwd: out must be a contiguous {y.dtype} {list(shape)} tensor")
     _check(require().lora_amd_geglu_fwd(y2.data_ptr(), y2.stride(0), out.data_ptr(), inner, y2.shape[0], inner,
                                         dtype_code(y.dtype), _stream()), "lora_amd_geglu_fwd")
     return out
@@ -2163,13 +2174,23 @@ def layernorm_supported(K: int) -> bool:
     return bool(require().lora_amd_layernorm_supported(K))
 
 
-def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
-    """LayerNorm over the last dimension of a contiguous x; returns (y, stats [rows, 2] = mean, rstd)."""
-    _dev_check(x, gamma, beta)
+def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, *,
+                  out: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """LayerNorm over the last dimension of a contiguous x; returns (y, stats [rows, 2] = mean, rstd).  ``out`` /
+    ``stats``: contiguous tensors of those shapes to write instead of new ones."""
+    _dev_check(x, gamma, beta, out, stats)
     K = x.shape[-1]
     M = x.numel() // K
-    y = torch.empty_like(x)
-    stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
+    if out is None:
+        y = torch.empty_like(x)
+    elif out.dtype != x.dtype or out.shape != x.shape or not out.is_contiguous():
+        raise ValueError("layernorm_fwd: out must be a contiguous tensor of x's shape and dtype")
+    else:
+        y = out
+    if stats is None:
+        stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
+    elif stats.dtype != torch.float32 or tuple(stats.shape) != (M, 2) or not stats.is_contiguous():
+        raise ValueError(f"layernorm_fwd: stats must be a contiguous f32 [{M}, 2] tensor")
     _check(require().lora_amd_layernorm_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
                                             stats.data_ptr(), M, K, eps, dtype_code(x.dtype), _stream()),
            "lora_amd_layernorm_fwd")

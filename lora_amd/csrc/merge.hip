@@ -310,6 +310,17 @@ extern "C" int lora_amd_merge_plan(lora_amd_merge_site *sites, int32_t n_sites, 
   LORA_AMD_CHECK(sites && summary && n_sites >= 0, LORA_AMD_EINVAL, "merge_plan: null argument");
   int n_fast = 0, rt_fast = 4;
   LORA_AMD_CHECK(dtype_ok(w_dtype), LORA_AMD_EINVAL, "merge_plan: bad w_dtype %d", w_dtype);
+  // The column-owner kernel is instantiated for the LARGEST rank tile of the table and stages [rows_per_tile][RT] floats
+  // of `up` in LDS (kMergeLdsUpFloats): every such site's tile height is capped by that RT, not by its own rank tile (a
+  // rank-4 site planned for RT 4 next to a rank-16 site would stage 4x the LDS the kernel has).
+  for (int i = 0; i < n_sites; ++i) {
+    const lora_amd_merge_site &s = sites[i];
+    if (s.K <= 0 || s.K % 8 != 0 || s.r < 1 || s.r > 16 || (((uintptr_t)s.w_in | (uintptr_t)s.w_out) & 15u) != 0) continue;
+    if (!s.transposed && (((uintptr_t)s.down) & 31u) != 0) continue;
+    if ((s.K / 8) % 4 != 0) continue;  // ct8 >= 4
+    const int rt = s.r <= 4 ? 4 : s.r <= 8 ? 8 : 16;
+    if (rt > rt_fast) rt_fast = rt;
+  }
   int64_t acc = 0;
   for (int i = 0; i < n_sites; ++i) {
     lora_amd_merge_site &s = sites[i];
@@ -333,10 +344,9 @@ extern "C" int lora_amd_merge_plan(lora_amd_merge_site *sites, int32_t n_sites, 
     if (aligned && (ab_aligned || s.transposed) && s.K % 8 == 0 && ct8 >= 4 && s.r <= 16) {
       // column-owner tiles: (ct8*8) columns x rows_per_tile rows
       const int cols = ct8 * 8;
-      const int rt = s.r <= 4 ? 4 : s.r <= 8 ? 8 : 16;
       int64_t rows = g_merge_tile_elems / cols;
       const int nslots = kMergeThreads / ct8;
-      if (rows > kMergeLdsUpFloats / rt) rows = kMergeLdsUpFloats / rt;
+      if (rows > kMergeLdsUpFloats / rt_fast) rows = kMergeLdsUpFloats / rt_fast;
       if (rows < nslots) rows = nslots;
       if (rows > s.N) rows = s.N;
       s.cols_per_tile = cols;
@@ -344,7 +354,6 @@ extern "C" int lora_amd_merge_plan(lora_amd_merge_site *sites, int32_t n_sites, 
       s.tiles_k = s.K / cols;
       s.flags = 3;
       ++n_fast;
-      if (rt > rt_fast) rt_fast = rt;
     } else {
       int max_cols = (kMergeLdsDownFloats / s.r) & ~7;
       int k8 = (s.K + 7) & ~7;

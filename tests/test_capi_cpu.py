@@ -57,6 +57,25 @@ def test_merge_planner_is_pure_host_arithmetic():
     assert summ.n_fast_sites == 2 and sites[0].cols_per_tile * sites[0].r <= 8192
 
 
+def test_merge_plan_caps_every_column_owner_tile_by_the_largest_rank_tile():
+    """The column-owner kernel runs at the LARGEST rank tile of the table and stages [rows_per_tile][RT] floats of `up` in
+    2048 floats of LDS: a rank-4 site next to a rank-16 site must get a tile that fits RT 16, not RT 4 (it overflowed the
+    LDS and merged rows past 128 without their low-rank term)."""
+    lib = _C.require()
+    sites = (_C.MergeSite * 3)()
+    for s, (N, K, r, tr) in zip(sites, [(320, 160, 4, 1), (65, 96, 16, 0), (2560, 320, 3, 0)]):
+        s.N, s.K, s.r, s.transposed = N, K, r, tr
+        s.w_in = s.w_out = s.up = s.down = 4096
+    summ = _C.MergeSummary()
+    assert lib.lora_amd_merge_plan(sites, 3, _C.BF16, C.byref(summ)) == 0
+    assert summ.n_fast_sites == 3 and summ.rank_tile_fast == 16
+    for s in sites:
+        assert s.flags == 3 and s.rows_per_tile * summ.rank_tile_fast <= 2048, (s.N, s.K, s.r, s.rows_per_tile)
+    sites[1].r = 4   # one rank tile throughout: the tiles are as tall as before
+    assert lib.lora_amd_merge_plan(sites, 3, _C.BF16, C.byref(summ)) == 0
+    assert summ.rank_tile_fast == 4 and sites[0].rows_per_tile == 320 and sites[2].rows_per_tile * 4 <= 2048
+
+
 def test_workspace_queries():
     lib = _C.require()
     assert lib.lora_amd_colreduce_workspace(16384, 320, 4) == 256 * 4 * 320 * 4
@@ -306,3 +325,28 @@ def test_ws_head_layout_rules():
     assert not _C.ws_heads_ok(320, 320, None, (10, 32, 40))                # head more than twice the pad
     assert not _C.ws_heads_ok(320, 320, (8, 36, 64), None) and not _C.ws_heads_ok(320, 320, (4, 40, 64), None)
     assert C.sizeof(_C.WsSite) == 112 and _C.WsSite.y_heads.offset == 84
+
+
+def _header_launchers():
+    """Every entry point of include/lora_amd.h that takes a `void *stream` (the launchers)."""
+    src = open(os.path.join(REPO, "include", "lora_amd.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    decls = re.findall(r"\b(lora_amd_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src, flags=re.S)
+    return sorted({name for name, args in decls if re.search(r"\bvoid\s*\*\s*stream\b", args)})
+
+
+def test_every_launcher_has_a_footprint_case():
+    """tests/test_gpu_footprint.py has a case for every launcher of the header (or a listed exemption with a reason):
+    a new kernel cannot skip the guard / poison / written-set checks."""
+    from tests import test_gpu_footprint as FP
+
+    launchers = _header_launchers()
+    assert len(launchers) >= 71, f"header parse found only {len(launchers)} launchers"
+    covered, exempt = FP.covered(), dict(FP.EXEMPT)
+    missing = [s for s in launchers if s not in covered and s not in exempt]
+    assert not missing, f"launchers without a footprint case: {missing}"
+    stale = sorted((covered | set(exempt)) - set(launchers))
+    assert not stale, f"footprint cases / exemptions name entry points that are not launchers of the header: {stale}"
+    assert not covered & set(exempt), f"both covered and exempt: {sorted(covered & set(exempt))}"
+    for name, reason in exempt.items():
+        assert isinstance(reason, str) and reason.strip() and "\n" not in reason, f"{name}: exemption needs a one-line reason"
