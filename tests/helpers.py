@@ -296,6 +296,41 @@ def oracle_on_device():
 
 
 
+# ----------------------------------------------------------------------------- the SD1.5-size twins (whole-step parity)
+def sd15_twins(r=4, ref_device="cuda:0", dev="cuda:0"):
+    """SD1.5-size UNet twice: bf16 on the device exactly as bench.py builds it, and the f32 oracle twin with the same
+    (bf16-representable) frozen values and the reference-algorithm adapters; same factor values (up != 0).  The oracle twin
+    lives on ``ref_device``: the GPU by default (its steps are then evaluated inside ``H.oracle_on_device()``: library
+    kernels only, f32 — the host needs a minute per SD1.5-size step)."""
+    from bench import build_unet
+    import lora_amd as L
+    from lora_amd import trainer as T
+    from lora_amd.standin import sd15_unet
+    from oracle import torch_ref as TR
+
+    dev_unet = build_unet(torch.device(dev), torch.bfloat16, seed=0)
+    with torch.device("meta"):
+        ref = sd15_unet()
+    ref.to_empty(device=ref_device)
+    ref.load_state_dict({k: v.float().to(ref_device) for k, v in dev_unet.state_dict().items()})
+    ref.requires_grad_(False)
+    ref_params = TR.inject(ref, L.UNET_DEFAULT_TARGET_REPLACE, r=r)
+    g = torch.Generator().manual_seed(11)
+    for s_ in TR.sites_of(ref):
+        s_.up.data.copy_((torch.randn(s_.up.shape, generator=g) * 0.02).to(ref_device))
+        s_.down.data.copy_((torch.randn(s_.down.shape, generator=g) / r).to(ref_device))
+    L.inject_trainable_lora(dev_unet, r=r)
+    T.promote_lora_to_fp32(dev_unet)
+    ours = [m for m in dev_unet.modules() if isinstance(m, L.LoraInjectedLinear)]
+    theirs = TR.sites_of(ref)
+    assert len(ours) == len(theirs) == 144
+    for a, b in zip(ours, theirs):
+        a.lora_up.weight.data.copy_(b.up.data.to(dev))
+        a.lora_down.weight.data.copy_(b.down.data.to(dev))
+    ref.train(), dev_unet.train()
+    return ref, ref_params, dev_unet
+
+
 # ----------------------------------------------------------------------------- the bracket rule (whole-step parity)
 def oracle_step_on_device(ref, ref_params, lat, noise, ts, ehs, autocast: bool):
     """One step of oracle/torch_ref.dreambooth_step (plain ATen ops) on the GPU: f32, or under torch.autocast(bf16) — the

@@ -439,35 +439,7 @@ def test_ragged_svd_of_several_shape_groups_vs_exact_svd():
 
 
 # ----------------------------------------------------------------------------- the benchmarked configuration vs the oracle
-def _sd15_twins(r=4, ref_device=DEV):
-    """SD1.5-size UNet twice: bf16 on the device exactly as bench.py builds it, and the f32 oracle twin with the same
-    (bf16-representable) frozen values and the reference-algorithm adapters; same factor values (up != 0).  The oracle twin
-    lives on ``ref_device``: the GPU by default (its steps are then evaluated inside ``H.oracle_on_device()``: library
-    kernels only, f32 — the host needs a minute per SD1.5-size step)."""
-    sys.path.insert(0, H.REPO)
-    from bench import build_unet
-
-    dev_unet = build_unet(torch.device(DEV), torch.bfloat16, seed=0)
-    with torch.device("meta"):
-        ref = sd15_unet()
-    ref.to_empty(device=ref_device)
-    ref.load_state_dict({k: v.float().to(ref_device) for k, v in dev_unet.state_dict().items()})
-    ref.requires_grad_(False)
-    ref_params = TR.inject(ref, L.UNET_DEFAULT_TARGET_REPLACE, r=r)
-    g = torch.Generator().manual_seed(11)
-    for s_ in TR.sites_of(ref):
-        s_.up.data.copy_((torch.randn(s_.up.shape, generator=g) * 0.02).to(ref_device))
-        s_.down.data.copy_((torch.randn(s_.down.shape, generator=g) / r).to(ref_device))
-    L.inject_trainable_lora(dev_unet, r=r)
-    T.promote_lora_to_fp32(dev_unet)
-    ours = [m for m in dev_unet.modules() if isinstance(m, L.LoraInjectedLinear)]
-    theirs = TR.sites_of(ref)
-    assert len(ours) == len(theirs) == 144
-    for a, b in zip(ours, theirs):
-        a.lora_up.weight.data.copy_(b.up.data.to(DEV))
-        a.lora_down.weight.data.copy_(b.down.data.to(DEV))
-    ref.train(), dev_unet.train()
-    return ref, ref_params, dev_unet
+_sd15_twins = H.sd15_twins   # moved to tests/helpers.py (the ladder builds the same twins); other modules import this name
 
 
 @pytest.fixture(scope="module")
@@ -479,7 +451,7 @@ def sd15_reference_step():
     computes it — 0.973-0.976 on one `up` tensor in all three configurations, the ATen-normalised one included — so that
     fixture had gone back to batch 1; round 6 judges batch 4 by the bracket rule instead, tests/helpers.bracket.)"""
     H.lap("fixture start")
-    ref, ref_params, dev_unet = _sd15_twins()
+    ref, ref_params, dev_unet = H.sd15_twins()
     H.lap("fixture: twins built")
     g = torch.Generator().manual_seed(123)
     B = 4

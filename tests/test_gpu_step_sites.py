@@ -13,11 +13,16 @@ and grouped projections, the hostops passes, the merged-weight route that bench.
    Inf in the loss, ``flat_g`` or the scratch weights.
 4. The same checks in a child process under the benchmark's convolution picks (``bench.private_miopen_db``: a temporary copy
    of bench_tuning/miopen; the parent's ``MIOPEN_USER_DB_PATH`` removed from the child's environment).
+5. Check 1 on the per-site route (``bench.py --merged 0``, the r3 test's ``bench_fused_sites``): every site's (G, X) is
+   recorded where its autograd backward receives them (``ops.LoraLinearFunction``, ``LoraLinearHeadsFunction``,
+   ``LoraLinearGroupFunction``; a grouped q / k / v launch yields three sites) and judged by the same ``site_errors``; in the
+   pytest process and in the child of check 4.
 
 Run as a script (``python tests/test_gpu_step_sites.py [--seeded-db]``) it prints the measurements as one JSON line.
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 import subprocess
@@ -83,8 +88,49 @@ def _scratch_finite(merged) -> bool:
     return True
 
 
-def build_step():
-    """The device UNet as bench.py builds it, adapters with up != 0, the merged route's state, inputs; -> dict."""
+@contextlib.contextmanager
+def per_site_records(records):
+    """Record (G, X, down, up, scale, G's head layout, X's head layout) of every site where the per-site route's autograd
+    backward receives them, in the form ``site_errors`` takes.  A backward that detours through dense copies enters
+    ``LoraLinearFunction.backward`` a second time: that site is then recorded twice, padded and dense."""
+    from lora_amd import _C, ops
+
+    classes = (ops.LoraLinearFunction, ops.LoraLinearHeadsFunction, ops.LoraLinearGroupFunction)
+    orig = {c: c.__dict__["backward"] for c in classes}
+
+    def single(fn):
+        def backward(ctx, g):
+            x2, weight, down, up = ctx.saved_tensors[:4]
+            ih, oh = getattr(ctx, "in_heads", None), getattr(ctx, "out_heads", None)
+            g2 = ops._rows2d(g, _C.heads_width(weight.shape[0], oh))
+            records.append((g2.detach().clone(), x2.detach().clone(), down.detach(), up.detach(), float(ctx.scale), oh, ih))
+            return fn(ctx, g)
+        return staticmethod(backward)
+
+    def group(fn):
+        def backward(ctx, *grads):
+            saved, n = ctx.saved_tensors, ctx.n
+            x2, rest = saved[0].detach().clone(), saved[1 + n:]
+            for i in range(n):
+                weight, down, up = rest[3 * i:3 * i + 3]
+                if grads[i] is not None:
+                    g2 = ops._rows2d(grads[i], weight.shape[0])
+                    records.append((g2.detach().clone(), x2, down.detach(), up.detach(), float(ctx.meta[i][0]), None, None))
+            return fn(ctx, *grads)
+        return staticmethod(backward)
+
+    for c in classes:
+        c.backward = (group if c is ops.LoraLinearGroupFunction else single)(orig[c].__func__)
+    try:
+        yield records
+    finally:
+        for c in classes:
+            c.backward = orig[c]
+
+
+def build_step(merged=True):
+    """The device UNet as bench.py builds it, adapters with up != 0, the merged route's state (``merged=False``: the per-site
+    fused kernels, bench.py --merged 0), inputs; -> dict."""
     from bench import build_unet
     import lora_amd as L
     from lora_amd import trainer as T
@@ -104,7 +150,7 @@ def build_step():
     st = T.FlatLoraState([{"params": T.lora_params(unet), "lr": 1e-4, "weight_decay": 1e-2}], max_grad_norm=1.0,
                          device=torch.device(DEV))
     st.attach_direct_grads(unet)
-    merged = st.enable_merged_weights(unet)
+    merged = st.enable_merged_weights(unet) if merged else None
     g = torch.Generator().manual_seed(123)
     B = 4
     lat = (torch.randn(B, 4, 64, 64, generator=g) * 0.18215).to(DEV).to(torch.bfloat16)
@@ -188,6 +234,36 @@ def measure(s, mutate=None):
                 poisoned=poisoned, refreshes=merged.refreshes)
 
 
+def measure_per_site(s):
+    """Check 1 on the per-site route: one eager step after the warm-up, every site's (G, X) recorded at its backward."""
+    st, fwd_bwd, lat, ehs = s["st"], s["fwd_bwd"], s["lat"], s["ehs"]
+    assert s["merged"] is None
+    for _ in range(2):
+        fwd_bwd(lat, ehs)
+        st.zero_grad()
+    with per_site_records([]) as records:
+        loss = float(fwd_bwd(lat, ehs))
+        st.reduce_pending()
+    torch.cuda.synchronize()
+    worst = site_errors(records, s["mods"], st)
+    n_records = len(records)
+    # that the check can fail: one site's d_down 5 % too large must leave the bound (arithmetic on flat_g, no kernel changed).
+    # The tolerance is 1e-4 of the ABSOLUTE bound, about sqrt(M) = 128 x a typical element over 16384 rows: 1 % is borderline
+    m = s["mods"][len(s["mods"]) // 2]
+    st.grad_view(m.lora_down.weight).mul_(1.05)
+    negative = site_errors(records, s["mods"], st)[id(m)]
+    del records
+    st.zero_grad()
+    return dict(n_sites=len(worst), n_records=n_records, d1_worst=max(worst.values()),
+                d1_bad=sum(v > 1.0 for v in worst.values()), negative=negative, loss=loss)
+
+
+def assert_per_site(r):
+    assert r["n_sites"] == N_SITES, f"{r['n_sites']} of {N_SITES} sites recorded on the per-site route"
+    assert r["d1_bad"] == 0, f"{r['d1_bad']} sites outside 1e-4 of the bound (worst {r['d1_worst']:.3g} x the tolerance)"
+    assert r["negative"] > 1.0, f"a gradient 5 % too large passed the check ({r['negative']:.3g} x the tolerance)"
+
+
 def assert_measurements(r):
     assert r["n_sites"] == N_SITES, f"{r['n_sites']} of {N_SITES} sites recorded on the merged route"
     assert r["d1_bad"] == 0, f"{r['d1_bad']} sites outside 1e-4 of the bound (worst {r['d1_worst']:.3g} x the tolerance)"
@@ -219,6 +295,32 @@ def step():
             torch.cuda.empty_cache()
 
 
+def _release(s):
+    for m in s["unet"].modules():
+        m.__dict__.pop("_grad_sink", None)
+        m.__dict__.pop("_merged", None)
+
+
+@pytest.mark.gpu
+def test_per_site_route_site_by_site():
+    """Check 5: the fused per-site kernels' factor gradients at step level, all 144 sites."""
+    from lora_amd.standin import fused
+
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("LORA_AMD_HEAD_PAD", "1")
+        mp.setenv("LORA_AMD_GROUP_QKV", "1")
+        mp.setattr(fused, "_ENABLED", True)
+        s = build_step(merged=False)
+        try:
+            r = measure_per_site(s)
+        finally:
+            _release(s)
+            del s
+            torch.cuda.empty_cache()
+    print(json.dumps(r))
+    assert_per_site(r)
+
+
 @pytest.mark.gpu
 def test_timed_step_site_by_site_replay_and_poisoned_free_memory(step):
     r = measure(step)
@@ -226,19 +328,33 @@ def test_timed_step_site_by_site_replay_and_poisoned_free_memory(step):
     assert_measurements(r)
 
 
-@pytest.mark.gpu
-def test_the_same_under_the_benchmarks_convolution_picks():
-    """Check 4: a child process (never exec) without MIOPEN_USER_DB_PATH calls bench.private_miopen_db() before its first
-    convolution: MIOpen runs on a temporary copy of bench_tuning/miopen, the user's database is never written."""
+@pytest.fixture(scope="module")
+def seeded_child():
+    """Checks 4 and 5's child process (never exec) without MIOPEN_USER_DB_PATH: it calls bench.private_miopen_db() before its
+    first convolution, so MIOpen runs on a temporary copy of bench_tuning/miopen and the user's database is never written."""
     env = {k: v for k, v in os.environ.items() if k != "MIOPEN_USER_DB_PATH"}
     p = subprocess.run([sys.executable, os.path.abspath(__file__), "--seeded-db"], cwd=REPO, env=env, capture_output=True,
                        text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     line = [x for x in p.stdout.splitlines() if x.startswith("{")][-1]
-    r = json.loads(line)
     print(line)
+    return json.loads(line)
+
+
+@pytest.mark.gpu
+def test_the_same_under_the_benchmarks_convolution_picks(seeded_child):
+    """Check 4: the merged route's three checks on the benchmark's convolution picks."""
+    r = seeded_child
     assert r["seeded_db"], "the child did not run on the seeded database"
     assert_measurements(r)
+
+
+@pytest.mark.gpu
+def test_per_site_route_under_the_benchmarks_convolution_picks(seeded_child):
+    """Check 5 in the child of check 4."""
+    r = seeded_child
+    assert r["seeded_db"], "the child did not run on the seeded database"
+    assert_per_site(r["per_site"])
 
 
 def _main(argv):
@@ -250,7 +366,12 @@ def _main(argv):
     os.environ["LORA_AMD_GROUP_QKV"] = "1"
     from lora_amd.standin import fused
     fused._ENABLED = True
-    r = measure(build_step())
+    s = build_step()
+    r = measure(s)
+    _release(s)
+    del s
+    torch.cuda.empty_cache()
+    r["per_site"] = measure_per_site(build_step(merged=False))
     r["seeded_db"] = seeded and bool(os.environ.get("MIOPEN_USER_DB_PATH"))
     print(json.dumps(r), flush=True)
 
