@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "lora_amd.h"
 
 namespace lora_amd {
@@ -74,6 +76,43 @@ struct bf16_t {
   __device__ static float to_f(storage v) { return (float)v; }
   __device__ static storage from_f(float v) { return (__bf16)v; }  // v_cvt_pk_bf16_f32, RNE
 };
+
+// ---- host side: a runtime value becomes a template argument ---------------
+// A launcher nests these around its hipLaunchKernelGGL; the innermost lambda names its types
+// (`using E = decltype(e); constexpr int RT = decltype(rt)::value;`).  Every helper returns what f returns, and its
+// deduced return type makes the compiler instantiate f's cases where the launcher calls it, in the order listed.
+template <int V>
+constexpr std::integral_constant<int, V> int_c{};
+
+template <class F>
+inline auto by_dtype(int dt, F &&f) {  // anything that is neither f32 nor f16 runs as bf16 (callers check dtype_ok first)
+  switch (dt) {
+    case LORA_AMD_F32: return f(f32_t{});
+    case LORA_AMD_F16: return f(f16_t{});
+    default: return f(bf16_t{});
+  }
+}
+// Two-type form for kernels that exist for 16-bit rows only: A when dt is A's code, anything else runs as B.
+template <class A, class B, class F>
+inline auto by_dtype(int dt, F &&f) {
+  if (dt == A::kCode) return f(A{});
+  return f(B{});
+}
+// f(int_c<V>) for the first listed V == v; the LAST listed value takes every other v.
+template <int V, int... Vs, class F>
+inline auto by_int(int v, F &&f) {
+  if constexpr (sizeof...(Vs) == 0) {
+    return f(int_c<V>);
+  } else {
+    if (v == V) return f(int_c<V>);
+    return by_int<Vs...>(v, f);
+  }
+}
+template <class F>
+inline auto by_bool(bool b, F &&f) {
+  if (b) return f(std::true_type{});
+  return f(std::false_type{});
+}
 
 // A 16-byte (or 32-byte for f32) chunk of 8 elements, the unit every lane moves.
 template <class E>

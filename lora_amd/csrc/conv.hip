@@ -672,20 +672,40 @@ extern "C" int lora_amd_conv_down_fwd(const void *x, const void *down, const flo
   const bool direct = S == 1;  // single split: the partials ARE the result
   float *dst = direct ? t_out : t_part;
   const dim3 grid((unsigned)q.ngroups_in, (unsigned)S, (unsigned)((r + 3) / 4));
-#define CD(E, KSV)                                                                                                 \
-  hipLaunchKernelGGL((conv_down_fwd_kernel<E, KSV>), grid, dim3(kCT), 0, st,                                       \
-                     reinterpret_cast<const typename E::storage *>(x), reinterpret_cast<const float *>(down), dst, \
-                     B, C_in, H, W, r, q.cpw_in, q.NP, cps)
-#define CD_E(E) do { if (ks == 1) CD(E, 1); else CD(E, 3); } while (0)
-  switch (act_dtype) {
-    case LORA_AMD_F32: CD_E(f32_t); break;
-    case LORA_AMD_F16: CD_E(f16_t); break;
-    default: CD_E(bf16_t); break;
-  }
-#undef CD_E
-#undef CD
+  by_dtype(act_dtype, [&](auto e) {
+    by_int<1, 3>(ks, [&](auto k) {
+      using E = decltype(e);
+      hipLaunchKernelGGL((conv_down_fwd_kernel<E, decltype(k)::value>), grid, dim3(kCT), 0, st,
+                         reinterpret_cast<const typename E::storage *>(x), reinterpret_cast<const float *>(down), dst,
+                         B, C_in, H, W, r, q.cpw_in, q.NP, cps);
+    });
+  });
   launch_finalize(t_part, S, (int64_t)B * r * H * W, sel, 0, t_out, B, r, (int64_t)H * W, st);
   return check_launch("lora_amd_conv_down_fwd");
+}
+
+// The up projection of lora_amd_conv_up_fwd (RSC = false) and lora_amd_conv_up_fwd_rowscale (RSC = true).  The deduced
+// return type makes the compiler instantiate each form where it is called, so the kernels keep the callers' order.
+template <bool RSC>
+static auto launch_conv_up(void *y, const float *t, const void *up, int B, int C_out, int HW, int r, int act_dtype,
+                           const ConvGeo &q, float scale, float dropout_p, uint64_t seed, uint64_t offset,
+                           const uint64_t *offset_dev, const float *row_scale, int nsel, int64_t rows_per_sample,
+                           hipStream_t st) {
+  // the pass streams Y: no reduction across channels, so split purely for parallelism
+  const int S = stream_split(q.ngroups_out, C_out);
+  const int cps = (C_out + S - 1) / S;
+  const dim3 grid((unsigned)q.ngroups_out, (unsigned)S);
+  const int RT = r <= 4 ? 4 : r <= 8 ? 8 : 16;
+  by_dtype(act_dtype, [&](auto e) {
+    by_bool(dropout_p > 0.f, [&](auto d) {
+      by_int<4, 8, 16>(RT, [&](auto rt) {
+        using E = decltype(e);
+        hipLaunchKernelGGL((conv_up_fwd_kernel<E, decltype(rt)::value, decltype(d)::value, RSC>), grid, dim3(kCT), 0, st,
+                           reinterpret_cast<typename E::storage *>(y), t, reinterpret_cast<const float *>(up), B, C_out,
+                           HW, r, 64, q.NP, cps, scale, dropout_p, seed, offset, offset_dev, row_scale, nsel, rows_per_sample);
+      });
+    });
+  });
 }
 
 extern "C" int lora_amd_conv_up_fwd(void *y, const float *t, const void *up, int32_t B, int32_t C_out, int32_t H,
@@ -695,28 +715,8 @@ extern "C" int lora_amd_conv_up_fwd(void *y, const float *t, const void *up, int
   CONV_COMMON("conv_up_fwd", C_out);
   LORA_AMD_CHECK(y && t && up && al16(y) && al16(t), LORA_AMD_EINVAL, "conv_up_fwd: null or unaligned pointer");
   LORA_AMD_CHECK(dropout_p >= 0.f && dropout_p < 1.f, LORA_AMD_EINVAL, "conv_up_fwd: dropout p=%f", dropout_p);
-  hipStream_t st = (hipStream_t)stream;
-  // the pass streams Y: no reduction across channels, so split purely for parallelism
-  const int S = stream_split(q.ngroups_out, C_out);
-  const int cps = (C_out + S - 1) / S;
-  const dim3 grid((unsigned)q.ngroups_out, (unsigned)S);
-  const int RT = r <= 4 ? 4 : r <= 8 ? 8 : 16;
-  const bool drop = dropout_p > 0.f;
-  const int HW = H * W;
-#define CU(E, RTV, D)                                                                                            \
-  hipLaunchKernelGGL((conv_up_fwd_kernel<E, RTV, D>), grid, dim3(kCT), 0, st,                                     \
-                     reinterpret_cast<typename E::storage *>(y), t, reinterpret_cast<const float *>(up), B, C_out, \
-                     HW, r, 64, q.NP, cps, scale, dropout_p, seed, offset, offset_dev)
-#define CU_RT(E, D) do { if (RT == 4) CU(E, 4, D); else if (RT == 8) CU(E, 8, D); else CU(E, 16, D); } while (0)
-#define CU_E(E) do { if (drop) CU_RT(E, true); else CU_RT(E, false); } while (0)
-  switch (act_dtype) {
-    case LORA_AMD_F32: CU_E(f32_t); break;
-    case LORA_AMD_F16: CU_E(f16_t); break;
-    default: CU_E(bf16_t); break;
-  }
-#undef CU_E
-#undef CU_RT
-#undef CU
+  launch_conv_up<false>(y, t, up, B, C_out, H * W, r, act_dtype, q, scale, dropout_p, seed, offset, offset_dev, nullptr, 1, 1,
+                        (hipStream_t)stream);
   return check_launch("lora_amd_conv_up_fwd");
 }
 
@@ -732,27 +732,8 @@ extern "C" int lora_amd_conv_up_fwd_rowscale(void *y, const float *t, const void
   LORA_AMD_CHECK(y && t && up && row_scale && al16(y) && al16(t), LORA_AMD_EINVAL,
                  "conv_up_fwd_rowscale: null or unaligned pointer");
   LORA_AMD_CHECK(dropout_p >= 0.f && dropout_p < 1.f, LORA_AMD_EINVAL, "conv_up_fwd_rowscale: dropout p=%f", dropout_p);
-  hipStream_t st = (hipStream_t)stream;
-  const int S = stream_split(q.ngroups_out, C_out);
-  const int cps = (C_out + S - 1) / S;
-  const dim3 grid((unsigned)q.ngroups_out, (unsigned)S);
-  const int RT = r <= 4 ? 4 : r <= 8 ? 8 : 16;
-  const bool drop = dropout_p > 0.f;
-  const int HW = H * W;
-#define CU(E, RTV, D)                                                                                              \
-  hipLaunchKernelGGL((conv_up_fwd_kernel<E, RTV, D, true>), grid, dim3(kCT), 0, st,                                 \
-                     reinterpret_cast<typename E::storage *>(y), t, reinterpret_cast<const float *>(up), B, C_out,   \
-                     HW, r, 64, q.NP, cps, scale, dropout_p, seed, offset, nullptr, row_scale, nsel, rows_per_sample)
-#define CU_RT(E, D) do { if (RT == 4) CU(E, 4, D); else if (RT == 8) CU(E, 8, D); else CU(E, 16, D); } while (0)
-#define CU_E(E) do { if (drop) CU_RT(E, true); else CU_RT(E, false); } while (0)
-  switch (act_dtype) {
-    case LORA_AMD_F32: CU_E(f32_t); break;
-    case LORA_AMD_F16: CU_E(f16_t); break;
-    default: CU_E(bf16_t); break;
-  }
-#undef CU_E
-#undef CU_RT
-#undef CU
+  launch_conv_up<true>(y, t, up, B, C_out, H * W, r, act_dtype, q, scale, dropout_p, seed, offset, nullptr, row_scale, nsel,
+                       rows_per_sample, (hipStream_t)stream);
   return check_launch("lora_amd_conv_up_fwd_rowscale");
 }
 
@@ -772,18 +753,14 @@ extern "C" int lora_amd_conv_bwd_g(const void *g, const float *t, const void *up
   const dim3 grid((unsigned)q.ngroups_out, (unsigned)S, (unsigned)((r + 3) / 4));
   const bool drop = dropout_p > 0.f;
   const int HW = H * W;
-#define CG(E, D)                                                                                                  \
-  hipLaunchKernelGGL((conv_bwd_g_kernel<E, D>), grid, dim3(kCT), 0, st,                                           \
-                     reinterpret_cast<const typename E::storage *>(g), t, reinterpret_cast<const float *>(up), dst, \
-                     up_part, B, C_out, HW, r, q.rank_pad, 64, q.NP, cps, scale, dropout_p, seed, offset, offset_dev)
-#define CG_E(E) do { if (drop) CG(E, true); else CG(E, false); } while (0)
-  switch (act_dtype) {
-    case LORA_AMD_F32: CG_E(f32_t); break;
-    case LORA_AMD_F16: CG_E(f16_t); break;
-    default: CG_E(bf16_t); break;
-  }
-#undef CG_E
-#undef CG
+  by_dtype(act_dtype, [&](auto e) {
+    by_bool(drop, [&](auto d) {
+      using E = decltype(e);
+      hipLaunchKernelGGL((conv_bwd_g_kernel<E, decltype(d)::value>), grid, dim3(kCT), 0, st,
+                         reinterpret_cast<const typename E::storage *>(g), t, reinterpret_cast<const float *>(up), dst,
+                         up_part, B, C_out, HW, r, q.rank_pad, 64, q.NP, cps, scale, dropout_p, seed, offset, offset_dev);
+    });
+  });
   launch_finalize(gt_part, S, (int64_t)B * r * HW, sel, 1, gt_out, B, r, HW, st);
   return check_launch("lora_amd_conv_bwd_g");
 }
@@ -801,23 +778,18 @@ extern "C" int lora_amd_conv_bwd_x(const void *x, void *dx, const float *gt, con
   const int cps = (C_in + S - 1) / S;
   const dim3 grid_dn((unsigned)q.ngroups_in, (unsigned)S, (unsigned)((r + 3) / 4));
   const dim3 grid_dx((unsigned)q.ngroups_in, (unsigned)S);
-#define CX(E, KSV)                                                                                                  \
-  do {                                                                                                              \
-    hipLaunchKernelGGL((conv_bwd_down_kernel<E, KSV>), grid_dn, dim3(kCT), 0, st,                                   \
-                       reinterpret_cast<const typename E::storage *>(x), gt, down_part, B, C_in, H, W, r, q.rank_pad, \
-                       q.cpw_in, q.NP, cps);                                                                        \
-    if (dx != nullptr)                                                                                              \
-      hipLaunchKernelGGL((conv_bwd_dx_kernel<E, KSV>), grid_dx, dim3(kCT), 0, st,                                   \
-                         reinterpret_cast<typename E::storage *>(dx), gt, reinterpret_cast<const float *>(down), B, \
-                         C_in, H, W, r, q.cpw_in, q.NP, cps);                                                       \
-  } while (0)
-#define CX_E(E) do { if (ks == 1) CX(E, 1); else CX(E, 3); } while (0)
-  switch (act_dtype) {
-    case LORA_AMD_F32: CX_E(f32_t); break;
-    case LORA_AMD_F16: CX_E(f16_t); break;
-    default: CX_E(bf16_t); break;
-  }
-#undef CX_E
-#undef CX
+  by_dtype(act_dtype, [&](auto e) {
+    by_int<1, 3>(ks, [&](auto k) {
+      using E = decltype(e);
+      constexpr int KS = decltype(k)::value;
+      hipLaunchKernelGGL((conv_bwd_down_kernel<E, KS>), grid_dn, dim3(kCT), 0, st,
+                         reinterpret_cast<const typename E::storage *>(x), gt, down_part, B, C_in, H, W, r, q.rank_pad,
+                         q.cpw_in, q.NP, cps);
+      if (dx != nullptr)
+        hipLaunchKernelGGL((conv_bwd_dx_kernel<E, KS>), grid_dx, dim3(kCT), 0, st,
+                           reinterpret_cast<typename E::storage *>(dx), gt, reinterpret_cast<const float *>(down), B,
+                           C_in, H, W, r, q.cpw_in, q.NP, cps);
+    });
+  });
   return check_launch("lora_amd_conv_bwd_x");
 }

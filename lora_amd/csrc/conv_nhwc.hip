@@ -935,18 +935,13 @@ extern "C" int lora_amd_conv3_nhwc_pack(const float *down, int32_t r, int32_t C_
   const int KS = (9 * r + 31) / 32;
   const int64_t pieces = (int64_t)9 * (C_in / 32) * 64 + (int64_t)(C_in / 16) * KS * 64;
   const unsigned grid = (unsigned)std::min<int64_t>((pieces + 255) / 256, 1024);
-  if (act_dtype == LORA_AMD_BF16)
-    hipLaunchKernelGGL(conv3_pack_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, down, r, C_in, KS,
-                       (__bf16 *)pf, (__bf16 *)pd);
-  else
-    hipLaunchKernelGGL(conv3_pack_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, down, r, C_in, KS,
-                       (_Float16 *)pf, (_Float16 *)pd);
+  by_dtype<bf16_t, f16_t>(act_dtype, [&](auto e) {
+    using S = typename decltype(e)::storage;
+    hipLaunchKernelGGL(conv3_pack_kernel<decltype(e)>, dim3(grid), dim3(256), 0, (hipStream_t)stream, down, r, C_in, KS,
+                       (S *)pf, (S *)pd);
+  });
   return check_launch("lora_amd_conv3_nhwc_pack");
 }
-
-#define NH_BY_DTYPE(LAUNCH)                        \
-  if (act_dtype == LORA_AMD_BF16) { LAUNCH(bf16_t) } \
-  else { LAUNCH(f16_t) }
 
 static int nh_launch_sum(const float *part, int nparts, int64_t n, float *out, void *stream) {
   const int64_t n4 = n / 4;
@@ -971,16 +966,13 @@ extern "C" int lora_amd_conv3_nhwc_down_fwd(const void *x, const void *pf, float
   const NhGeom g = nh_geom(B, C_in, H, W, r, pt);
   const dim3 grid((unsigned)((int64_t)B * g.nrg * g.ntc), (unsigned)q.ksplit);
   float *dst = q.ksplit > 1 ? t_part : t_out;
-#define NH_LAUNCH_T(E)                                                                                         \
-  using S = typename E::storage;                                                                               \
-  if (pt == 4) hipLaunchKernelGGL((conv3_down_nhwc_kernel<E, 4>), grid, dim3(kNhThreads), 0,                  \
-                                  (hipStream_t)stream, (const S *)x, (const S *)pf, dst, g);                   \
-  else if (pt == 2) hipLaunchKernelGGL((conv3_down_nhwc_kernel<E, 2>), grid, dim3(kNhThreads), 0,             \
-                                       (hipStream_t)stream, (const S *)x, (const S *)pf, dst, g);              \
-  else hipLaunchKernelGGL((conv3_down_nhwc_kernel<E, 1>), grid, dim3(kNhThreads), 0, (hipStream_t)stream,     \
-                          (const S *)x, (const S *)pf, dst, g);
-  NH_BY_DTYPE(NH_LAUNCH_T)
-#undef NH_LAUNCH_T
+  by_dtype<bf16_t, f16_t>(act_dtype, [&](auto e) {
+    by_int<4, 2, 1>(pt, [&](auto ptv) {
+      using S = typename decltype(e)::storage;
+      hipLaunchKernelGGL((conv3_down_nhwc_kernel<decltype(e), decltype(ptv)::value>), grid, dim3(kNhThreads), 0,
+                         (hipStream_t)stream, (const S *)x, (const S *)pf, dst, g);
+    });
+  });
   const int rc = check_launch("lora_amd_conv3_nhwc_down_fwd");
   if (rc != LORA_AMD_OK || q.ksplit == 1) return rc;
   return nh_launch_sum(t_part, q.ksplit, (int64_t)B * H * W * r, t_out, stream);
@@ -1019,10 +1011,9 @@ extern "C" int lora_amd_conv3_nhwc_pack_batched(const lora_amd_conv3_pack_site *
                  "conv3_nhwc_pack_batched: activations must be bf16 or f16");
   const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
   const NhPackSite *sd = reinterpret_cast<const NhPackSite *>(sites_dev);
-  if (act_dtype == LORA_AMD_BF16)
-    hipLaunchKernelGGL(conv3_site_pack_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, sd, n, total);
-  else
-    hipLaunchKernelGGL(conv3_site_pack_kernel<f16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, sd, n, total);
+  by_dtype<bf16_t, f16_t>(act_dtype, [&](auto e) {
+    hipLaunchKernelGGL(conv3_site_pack_kernel<decltype(e)>, dim3(grid), dim3(256), 0, (hipStream_t)stream, sd, n, total);
+  });
   return check_launch("lora_amd_conv3_nhwc_pack_batched");
 }
 
@@ -1048,14 +1039,13 @@ extern "C" int lora_amd_conv3_nhwc_fwd_fused(const void *x, const void *pf, cons
   const dim3 grid((unsigned)((int64_t)B * g.nrg * g.ntc), (unsigned)q.ksplit);
   using S = bf16_t::storage;
   const bool drop = dropout_p > 0.f;
-#define NH_FUSED(PT_, D_)                                                                                              \
-  hipLaunchKernelGGL((conv3_fwd_fused_kernel<bf16_t, PT_, D_>), grid, dim3(kNhThreads), 0, (hipStream_t)stream,        \
-                     (const S *)x, (const S *)pf, (const S *)pu, (S *)y, t_out, t_part, counters, g, C_out, scale,      \
-                     dropout_p, seed, offset, offset_dev)
-  if (q.pt == 4) { if (drop) NH_FUSED(4, true); else NH_FUSED(4, false); }
-  else if (q.pt == 2) { if (drop) NH_FUSED(2, true); else NH_FUSED(2, false); }
-  else { if (drop) NH_FUSED(1, true); else NH_FUSED(1, false); }
-#undef NH_FUSED
+  by_int<4, 2, 1>(q.pt, [&](auto ptv) {
+    by_bool(drop, [&](auto d) {
+      hipLaunchKernelGGL((conv3_fwd_fused_kernel<bf16_t, decltype(ptv)::value, decltype(d)::value>), grid, dim3(kNhThreads), 0,
+                         (hipStream_t)stream, (const S *)x, (const S *)pf, (const S *)pu, (S *)y, t_out, t_part, counters, g,
+                         C_out, scale, dropout_p, seed, offset, offset_dev);
+    });
+  });
   return check_launch("lora_amd_conv3_nhwc_fwd_fused");
 }
 
@@ -1070,28 +1060,15 @@ extern "C" int lora_amd_conv3_nhwc_bwd_dx(void *dx, const float *gt, const void 
   const NhGeom g = nh_geom(B, C_in, H, W, r, pt);
   const dim3 grid((unsigned)((int64_t)B * g.nrg * g.ntc), (unsigned)q.csplit);
   const int KS = (9 * r + 31) / 32;
-#define NH_LAUNCH_DX2(E, PT_, KS_)                                                                      \
-  hipLaunchKernelGGL((conv3_dx_nhwc_kernel<E, PT_, KS_>), grid, dim3(kNhThreads), 0, (hipStream_t)stream, \
-                     (typename E::storage *)dx, gt, (const typename E::storage *)pd, g);
-#define NH_LAUNCH_DX(E)                                                         \
-  if (pt == 2) {                                                                \
-    switch (KS) {                                                               \
-      case 2: NH_LAUNCH_DX2(E, 2, 2) break;                                     \
-      case 3: NH_LAUNCH_DX2(E, 2, 3) break;                                     \
-      case 4: NH_LAUNCH_DX2(E, 2, 4) break;                                     \
-      default: NH_LAUNCH_DX2(E, 2, 5) break;                                    \
-    }                                                                           \
-  } else {                                                                      \
-    switch (KS) {                                                               \
-      case 2: NH_LAUNCH_DX2(E, 1, 2) break;                                     \
-      case 3: NH_LAUNCH_DX2(E, 1, 3) break;                                     \
-      case 4: NH_LAUNCH_DX2(E, 1, 4) break;                                     \
-      default: NH_LAUNCH_DX2(E, 1, 5) break;                                    \
-    }                                                                           \
-  }
-  NH_BY_DTYPE(NH_LAUNCH_DX)
-#undef NH_LAUNCH_DX
-#undef NH_LAUNCH_DX2
+  by_dtype<bf16_t, f16_t>(act_dtype, [&](auto e) {
+    by_int<2, 1>(pt, [&](auto ptv) {
+      by_int<2, 3, 4, 5>(KS, [&](auto ksv) {
+        using S = typename decltype(e)::storage;
+        hipLaunchKernelGGL((conv3_dx_nhwc_kernel<decltype(e), decltype(ptv)::value, decltype(ksv)::value>), grid, dim3(kNhThreads),
+                           0, (hipStream_t)stream, (S *)dx, gt, (const S *)pd, g);
+      });
+    });
+  });
   return check_launch("lora_amd_conv3_nhwc_bwd_dx");
 }
 
@@ -1105,20 +1082,13 @@ extern "C" int lora_amd_conv3_nhwc_bwd_down(const void *x, const float *gt, floa
   const NhGeom g = nh_geom(B, C_in, H, W, r, 1);
   const int rank_pad = nh_rank_pad(r);
   const dim3 grid((unsigned)((C_in / 64) * q.nsplit));
-#define NH_LAUNCH_DD2(E, RQ_)                                                                                   \
-  hipLaunchKernelGGL((conv3_ddown_nhwc_kernel<E, RQ_>), grid, dim3(kDdThreads), 0, (hipStream_t)stream,        \
-                     (const typename E::storage *)x, gt, down_part, g, q.pr, q.nsplit, rank_pad,          \
-                     1);
-#define NH_LAUNCH_DD(E)                    \
-  switch (r / 4) {                         \
-    case 1: NH_LAUNCH_DD2(E, 1) break;     \
-    case 2: NH_LAUNCH_DD2(E, 2) break;     \
-    case 3: NH_LAUNCH_DD2(E, 3) break;     \
-    default: NH_LAUNCH_DD2(E, 4) break;    \
-  }
-  NH_BY_DTYPE(NH_LAUNCH_DD)
-#undef NH_LAUNCH_DD
-#undef NH_LAUNCH_DD2
+  by_dtype<bf16_t, f16_t>(act_dtype, [&](auto e) {
+    by_int<1, 2, 3, 4>(r / 4, [&](auto rq) {
+      hipLaunchKernelGGL((conv3_ddown_nhwc_kernel<decltype(e), decltype(rq)::value>), grid, dim3(kDdThreads), 0,
+                         (hipStream_t)stream, (const typename decltype(e)::storage *)x, gt, down_part, g, q.pr, q.nsplit,
+                         rank_pad, 1);
+    });
+  });
   return check_launch("lora_amd_conv3_nhwc_bwd_down");
 }
 

@@ -817,28 +817,34 @@ extern "C" int lora_amd_linear_bwd_factors_mfma_ragged_mapped(const lora_amd_fm_
   // lora_amd_factors_mfma_set_tuning; everything else: the 10-pair kernel of its block height
   const int narrow = (lds_class == 1 && rows_per_block == 64) ? g_fm_narrow : 0;
   if (lds_class == 1 && rows_per_block != 64 && rows_per_block != 32) rows_per_block = 64;
-#define FML(E, D, P, B, G64, G32, H) hipLaunchKernelGGL((factors_reg_kernel<E, D, P, B, G64, G32, H>), dim3((unsigned)grid), dim3(kFmThreads), 0, st, sites_dev, n, block_map_dev)
-#define FM2(E, D)                                                            \
-  do {                                                                       \
-    if (narrow == 1) FML(E, D, kFrPairsNarrow, 3, 1, 1, 1);                  \
-    else if (narrow == 2) FML(E, D, kFrPairsNarrow, 3, 2, 2, 1);             \
-    else if (narrow == 3) FML(E, D, kFrPairsNarrow, 2, 2, 2, 1);             \
-    else if (narrow == 4) FML(E, D, kFrPairsNarrow, 2, 3, 3, 1);             \
-    else if (narrow == 5) FML(E, D, kFrPairsNarrow, 2, 4, 4, 1);             \
-    else if (rows_per_block == 64) FML(E, D, kFrPairsWide, 2, 2, 4, 1);      \
-    else if (rows_per_block == 32) FML(E, D, kFrPairsWide, 2, 2, 4, 0);      \
-    else FML(E, D, kFrPairsWide, 2, 2, 4, 2);                                \
-  } while (0)
-#define FM(E) do { if (drop) FM2(E, true); else FM2(E, false); } while (0)
+  // the arguments are factors_reg_kernel's template arguments, in its order
+  auto launch = [&](auto e, auto d, auto pairs, auto minb, auto rg64, auto rg32, auto heights) {
+    hipLaunchKernelGGL((factors_reg_kernel<decltype(e), decltype(d)::value, decltype(pairs)::value, decltype(minb)::value,
+                                           decltype(rg64)::value, decltype(rg32)::value, decltype(heights)::value>),
+                       dim3((unsigned)grid), dim3(kFmThreads), 0, st, sites_dev, n, block_map_dev);
+  };
+  constexpr auto narrow_p = int_c<kFrPairsNarrow>;
+  constexpr auto wide_p = int_c<kFrPairsWide>;
   if (g_fm_wide != 0 && narrow == 0 && rows_per_block == 0 && !drop && act_dtype == LORA_AMD_BF16) {
     // ring depths of the 10-pair kernel (64-row sites, 32-row sites): 1 = (3, 4), 2 = (4, 4), 3 = (2, 6), 4 = (3, 6); default (2, 4)
-    if (g_fm_wide == 1) FML(bf16_t, false, kFrPairsWide, 2, 3, 4, 2);
-    else if (g_fm_wide == 2) FML(bf16_t, false, kFrPairsWide, 2, 4, 4, 2);
-    else if (g_fm_wide == 3) FML(bf16_t, false, kFrPairsWide, 2, 2, 6, 2);
-    else FML(bf16_t, false, kFrPairsWide, 2, 3, 6, 2);
-  } else if (act_dtype == LORA_AMD_F16) FM(f16_t); else FM(bf16_t);
-#undef FM2
-#undef FML
-#undef FM
+    constexpr std::false_type d{};
+    if (g_fm_wide == 1) launch(bf16_t{}, d, wide_p, int_c<2>, int_c<3>, int_c<4>, int_c<2>);
+    else if (g_fm_wide == 2) launch(bf16_t{}, d, wide_p, int_c<2>, int_c<4>, int_c<4>, int_c<2>);
+    else if (g_fm_wide == 3) launch(bf16_t{}, d, wide_p, int_c<2>, int_c<2>, int_c<6>, int_c<2>);
+    else launch(bf16_t{}, d, wide_p, int_c<2>, int_c<3>, int_c<6>, int_c<2>);
+  } else {
+    by_dtype<f16_t, bf16_t>(act_dtype, [&](auto e) {
+      by_bool(drop, [&](auto d) {
+        if (narrow == 1) launch(e, d, narrow_p, int_c<3>, int_c<1>, int_c<1>, int_c<1>);
+        else if (narrow == 2) launch(e, d, narrow_p, int_c<3>, int_c<2>, int_c<2>, int_c<1>);
+        else if (narrow == 3) launch(e, d, narrow_p, int_c<2>, int_c<2>, int_c<2>, int_c<1>);
+        else if (narrow == 4) launch(e, d, narrow_p, int_c<2>, int_c<3>, int_c<3>, int_c<1>);
+        else if (narrow == 5) launch(e, d, narrow_p, int_c<2>, int_c<4>, int_c<4>, int_c<1>);
+        else if (rows_per_block == 64) launch(e, d, wide_p, int_c<2>, int_c<2>, int_c<4>, int_c<1>);
+        else if (rows_per_block == 32) launch(e, d, wide_p, int_c<2>, int_c<2>, int_c<4>, int_c<0>);
+        else launch(e, d, wide_p, int_c<2>, int_c<2>, int_c<4>, int_c<2>);
+      });
+    });
+  }
   return check_launch("lora_amd_linear_bwd_factors_mfma_ragged");
 }

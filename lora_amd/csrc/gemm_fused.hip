@@ -348,28 +348,28 @@ static int launch_gemm_fwd(const void *x, int64_t ldx, const void *w, int64_t ld
   }
   const int rg = r <= 4 ? 1 : 4;
   hipStream_t st = (hipStream_t)stream;
-#define GF(E, RSV, CSV, NSV, RGV)                                                                                  \
-  hipLaunchKernelGGL((linear_gemm_fwd_kernel<E, RSV, CSV, NSV, RGV, RSC>),                                         \
-                     dim3((unsigned)((N + 32 * CSV - 1) / (32 * CSV)), (unsigned)((M + 32 * RSV - 1) / (32 * RSV))), \
-                     dim3(kGT), 0, st, reinterpret_cast<const typename E::storage *>(x), ldx,                      \
-                     reinterpret_cast<const typename E::storage *>(w), ldw,                                        \
-                     reinterpret_cast<const typename E::storage *>(bias), reinterpret_cast<typename E::storage *>(y), \
-                     ldy, down, up, t_out, M, K, N, r, scale, t_scale, factor_layout, xhc, xhp, yhc, yhp, row_scale, \
-                     nsel, rows_per_sample)
-#define GF_R(E, RSV, CSV, NSV) do { if (rg == 1) GF(E, RSV, CSV, NSV, 1); else GF(E, RSV, CSV, NSV, 4); } while (0)
-#define GF_S(E, RSV, CSV) do { if (stages == 3) GF_R(E, RSV, CSV, 3); else GF_R(E, RSV, CSV, 2); } while (0)
-#define GF_T(E)                                                                        \
-  do {                                                                                 \
-    if (shape == 1) { if (stages == 3 && rg == 4) GF(E, 2, 10, 2, 4); else GF_S(E, 2, 10); } \
-    else if (shape == 2) GF_S(E, 2, 5);                                                \
-    else if (shape == 3) GF_S(E, 1, 5);                                                \
-    else GF_S(E, 4, 5);                                                                \
-  } while (0)
-  if (act_dtype == LORA_AMD_BF16) GF_T(bf16_t); else GF_T(f16_t);
-#undef GF_T
-#undef GF_S
-#undef GF_R
-#undef GF
+  by_dtype<bf16_t, f16_t>(act_dtype, [&](auto e) {
+    using S = typename decltype(e)::storage;
+    // the arguments are linear_gemm_fwd_kernel's RS, CS, NS and RG
+    auto launch = [&](auto rs, auto cs, auto ns, auto rgv) {
+      constexpr int RSV = decltype(rs)::value, CSV = decltype(cs)::value;
+      hipLaunchKernelGGL((linear_gemm_fwd_kernel<decltype(e), RSV, CSV, decltype(ns)::value, decltype(rgv)::value, RSC>),
+                         dim3((unsigned)((N + 32 * CSV - 1) / (32 * CSV)), (unsigned)((M + 32 * RSV - 1) / (32 * RSV))),
+                         dim3(kGT), 0, st, reinterpret_cast<const S *>(x), ldx, reinterpret_cast<const S *>(w), ldw,
+                         reinterpret_cast<const S *>(bias), reinterpret_cast<S *>(y), ldy, down, up, t_out, M, K, N, r, scale,
+                         t_scale, factor_layout, xhc, xhp, yhc, yhp, row_scale, nsel, rows_per_sample);
+    };
+    auto by_rank_group = [&](auto rs, auto cs, auto ns) {
+      if (rg == 1) launch(rs, cs, ns, int_c<1>); else launch(rs, cs, ns, int_c<4>);
+    };
+    auto by_stages = [&](auto rs, auto cs) {
+      if (stages == 3) by_rank_group(rs, cs, int_c<3>); else by_rank_group(rs, cs, int_c<2>);
+    };
+    if (shape == 1) { if (stages == 3 && rg == 4) launch(int_c<2>, int_c<10>, int_c<2>, int_c<4>); else by_stages(int_c<2>, int_c<10>); }
+    else if (shape == 2) by_stages(int_c<2>, int_c<5>);
+    else if (shape == 3) by_stages(int_c<1>, int_c<5>);
+    else by_stages(int_c<4>, int_c<5>);
+  });
   return check_launch(what);
 }
 

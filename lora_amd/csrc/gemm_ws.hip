@@ -662,40 +662,34 @@ extern "C" int lora_amd_linear_ws_heads(const void *x, int64_t ldx, int64_t M, i
   for (int s = 0; s < nsites; ++s)
     LORA_AMD_CHECK(!drop || sites[s].N % 8 == 0, LORA_AMD_EINVAL,
                    "linear_ws: site %d: dropout needs N %% 8 == 0 (mask chunks of 8 columns)", s);
-#define WS_L(E, KFV, CSV, RSV, FLV, RMV, DV, HV) \
-  hipLaunchKernelGGL((linear_ws_kernel<E, KFV, CSV, RSV, FLV, RMV, DV, HV>), dim3(grid), dim3(kWsThreads), 0, st, a)
-#define WS_D(E, KFV, CSV, RSV, DV, HV)                          \
-  do {                                                          \
-    if (fl == 3) WS_L(E, KFV, CSV, RSV, 3, 0, DV, HV);          \
-    else if (rm == 1) WS_L(E, KFV, CSV, RSV, 0, 1, DV, HV);     \
-    else if (rm == 2) WS_L(E, KFV, CSV, RSV, 0, 2, DV, HV);     \
-    else WS_L(E, KFV, CSV, RSV, 0, 0, DV, HV);                  \
-  } while (0)
-#define WS_H(E, KFV, CSV, RSV) /* dropout sites: dense, head-padded input, head-padded output */ \
-  do {                                                          \
-    if (hd == 1) WS_D(E, KFV, CSV, RSV, true, 1);               \
-    else if (hd == 2) WS_D(E, KFV, CSV, RSV, true, 2);          \
-    else WS_D(E, KFV, CSV, RSV, true, 0);                       \
-  } while (0)
-#define WS(E, KFV, CSV, RSV)                                    \
-  do {                                                          \
-    if (drop) WS_H(E, KFV, CSV, RSV);                           \
-    else WS_D(E, KFV, CSV, RSV, false, 0);                      \
-  } while (0)
-#define WS_K(E)                                                 \
-  do {                                                          \
-    if (K == 320 && half_rows) WS_H(E, 10, 5, 2);               \
-    else if (K == 320 && drop) /* input gradient, dense */ WS_L(E, 10, 5, 4, 3, 0, true, 0); \
-    else if (K == 320) WS_D(E, 10, 5, 4, false, 0);             \
-    else if (K == 640) WS(E, 20, 2, 2);                         \
-    else if (K == 768) WS(E, 24, 2, 2);                         \
-    else WS(E, 40, 1, 1);                                       \
-  } while (0)
-  if (act_dtype == LORA_AMD_BF16) WS_K(bf16_t); else WS_K(f16_t);
-#undef WS_K
-#undef WS
-#undef WS_H
-#undef WS_D
-#undef WS_L
+  by_dtype<bf16_t, f16_t>(act_dtype, [&](auto e) {
+    // the arguments are linear_ws_kernel's template arguments after E, in its order: KF, CS, RS, FL, RM, DROP, HD
+    auto launch = [&](auto kf, auto cs, auto rs, auto flv, auto rmv, auto d, auto h) {
+      hipLaunchKernelGGL((linear_ws_kernel<decltype(e), decltype(kf)::value, decltype(cs)::value, decltype(rs)::value,
+                                           decltype(flv)::value, decltype(rmv)::value, decltype(d)::value, decltype(h)::value>),
+                         dim3(grid), dim3(kWsThreads), 0, st, a);
+    };
+    auto by_layout = [&](auto kf, auto cs, auto rs, auto d, auto h) {
+      if (fl == 3) launch(kf, cs, rs, int_c<3>, int_c<0>, d, h);
+      else if (rm == 1) launch(kf, cs, rs, int_c<0>, int_c<1>, d, h);
+      else if (rm == 2) launch(kf, cs, rs, int_c<0>, int_c<2>, d, h);
+      else launch(kf, cs, rs, int_c<0>, int_c<0>, d, h);
+    };
+    auto by_heads = [&](auto kf, auto cs, auto rs) {  // dropout sites: dense, head-padded input, head-padded output
+      if (hd == 1) by_layout(kf, cs, rs, std::true_type{}, int_c<1>);
+      else if (hd == 2) by_layout(kf, cs, rs, std::true_type{}, int_c<2>);
+      else by_layout(kf, cs, rs, std::true_type{}, int_c<0>);
+    };
+    auto by_drop = [&](auto kf, auto cs, auto rs) {
+      if (drop) by_heads(kf, cs, rs);
+      else by_layout(kf, cs, rs, std::false_type{}, int_c<0>);
+    };
+    if (K == 320 && half_rows) by_heads(int_c<10>, int_c<5>, int_c<2>);
+    else if (K == 320 && drop) launch(int_c<10>, int_c<5>, int_c<4>, int_c<3>, int_c<0>, std::true_type{}, int_c<0>);  // input gradient, dense
+    else if (K == 320) by_layout(int_c<10>, int_c<5>, int_c<4>, std::false_type{}, int_c<0>);
+    else if (K == 640) by_drop(int_c<20>, int_c<2>, int_c<2>);
+    else if (K == 768) by_drop(int_c<24>, int_c<2>, int_c<2>);
+    else by_drop(int_c<40>, int_c<1>, int_c<1>);
+  });
   return check_launch("lora_amd_linear_ws");
 }

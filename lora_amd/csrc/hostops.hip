@@ -926,25 +926,16 @@ extern "C" int lora_amd_groupnorm_fwd(const void *x, const void *gamma, const vo
   GN_CHECKS("groupnorm_fwd");
   LORA_AMD_CHECK(x && gamma && beta && y && stats && workspace, LORA_AMD_EINVAL, "groupnorm_fwd: null pointer");
   LORA_AMD_CHECK(aligned_for(x, dtype) && aligned_for(y, dtype), LORA_AMD_EINVAL, "groupnorm_fwd: unaligned tensor");
-#define GO(E)                                                                                                        \
-  {                                                                                                                  \
-    using S = typename E::storage;                                                                                   \
-    hipLaunchKernelGGL((gn_stats_kernel<E>), grid, block, 0, st, (const S *)x, part, groups, q.cpg, HW, q.chunks,    \
-                       q.per_block, q.S);                                                                            \
-    if (act)                                                                                                         \
-      hipLaunchKernelGGL((gn_apply_kernel<E, true>), grid, block, 0, st, (const S *)x, (const S *)gamma,             \
-                         (const S *)beta, (S *)y, part, stats, groups, q.cpg, HW, q.chunks, q.per_block, q.S, eps);  \
-    else                                                                                                             \
-      hipLaunchKernelGGL((gn_apply_kernel<E, false>), grid, block, 0, st, (const S *)x, (const S *)gamma,            \
-                         (const S *)beta, (S *)y, part, stats, groups, q.cpg, HW, q.chunks, q.per_block, q.S, eps);  \
-  }                                                                                                                  \
-  break
-  switch (dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
+  by_dtype(dtype, [&](auto e) {
+    using E = decltype(e);
+    using S = typename E::storage;
+    hipLaunchKernelGGL((gn_stats_kernel<E>), grid, block, 0, st, (const S *)x, part, groups, q.cpg, HW, q.chunks,
+                       q.per_block, q.S);
+    by_bool(act != 0, [&](auto a) {
+      hipLaunchKernelGGL((gn_apply_kernel<E, decltype(a)::value>), grid, block, 0, st, (const S *)x, (const S *)gamma,
+                         (const S *)beta, (S *)y, part, stats, groups, q.cpg, HW, q.chunks, q.per_block, q.S, eps);
+    });
+  });
   return check_launch("lora_amd_groupnorm_fwd");
 }
 
@@ -957,26 +948,19 @@ extern "C" int lora_amd_groupnorm_bwd(const void *x, const void *gout, const voi
                  "groupnorm_bwd: null pointer");
   LORA_AMD_CHECK(aligned_for(x, dtype) && aligned_for(gout, dtype) && aligned_for(dx, dtype), LORA_AMD_EINVAL,
                  "groupnorm_bwd: unaligned tensor");
-#define GO2(E, A)                                                                                                    \
-  {                                                                                                                  \
-    using S = typename E::storage;                                                                                   \
-    hipLaunchKernelGGL((gn_bwd_stats_kernel<E, A>), grid, block, 0, st, (const S *)x, (const S *)gout,               \
-                       (const S *)gamma, (const S *)beta, stats, part, groups, q.cpg, HW, q.chunks, q.per_block,     \
-                       q.S);                                                                                         \
-    hipLaunchKernelGGL((gn_bwd_apply_kernel<E, A>), grid, block, 0, st, (const S *)x, (const S *)gout,               \
-                       (const S *)gamma, (const S *)beta, stats, part, (S *)dx, groups, q.cpg, HW, q.chunks,         \
-                       q.per_block, q.S);                                                                            \
-  }
-#define GO(E)                  \
-  if (act) GO2(E, true) else GO2(E, false) \
-  break
-  switch (dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
-#undef GO2
+  by_dtype(dtype, [&](auto e) {
+    by_bool(act != 0, [&](auto a) {
+      using E = decltype(e);
+      using S = typename E::storage;
+      constexpr bool A = decltype(a)::value;
+      hipLaunchKernelGGL((gn_bwd_stats_kernel<E, A>), grid, block, 0, st, (const S *)x, (const S *)gout,
+                         (const S *)gamma, (const S *)beta, stats, part, groups, q.cpg, HW, q.chunks, q.per_block,
+                         q.S);
+      hipLaunchKernelGGL((gn_bwd_apply_kernel<E, A>), grid, block, 0, st, (const S *)x, (const S *)gout,
+                         (const S *)gamma, (const S *)beta, stats, part, (S *)dx, groups, q.cpg, HW, q.chunks,
+                         q.per_block, q.S);
+    });
+  });
   return check_launch("lora_amd_groupnorm_bwd");
 }
 
@@ -999,16 +983,10 @@ extern "C" int lora_amd_geglu_fwd(const void *y, int64_t ldy, void *out, int64_t
                  LORA_AMD_EINVAL, "geglu_fwd: rows must be 16-byte aligned (ldy=%lld ldo=%lld)", (long long)ldy,
                  (long long)ldo);
   const dim3 grid((unsigned)((total + kHT * kHU - 1) / (kHT * kHU))), block(kHT);
-#define GO(E)                                                                                                    \
-  hipLaunchKernelGGL((geglu_fwd_kernel<E>), grid, block, 0, st, (const typename E::storage *)y, ldy,             \
-                     (typename E::storage *)out, ldo, M, c8);                                                    \
-  break
-  switch (dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
+  by_dtype(dtype, [&](auto e) {
+    using S = typename decltype(e)::storage;
+    hipLaunchKernelGGL((geglu_fwd_kernel<decltype(e)>), grid, block, 0, st, (const S *)y, ldy, (S *)out, ldo, M, c8);
+  });
   return check_launch("lora_amd_geglu_fwd");
 }
 
@@ -1021,16 +999,11 @@ extern "C" int lora_amd_geglu_bwd(const void *y, int64_t ldy, const void *gout, 
                      aligned_for(gy, dtype),
                  LORA_AMD_EINVAL, "geglu_bwd: rows must be 16-byte aligned");
   const dim3 grid((unsigned)((total + kHT * 2 - 1) / (kHT * 2))), block(kHT);
-#define GO(E)                                                                                                    \
-  hipLaunchKernelGGL((geglu_bwd_kernel<E>), grid, block, 0, st, (const typename E::storage *)y, ldy,             \
-                     (const typename E::storage *)gout, ldg, (typename E::storage *)gy, ldgy, M, c8);            \
-  break
-  switch (dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
+  by_dtype(dtype, [&](auto e) {
+    using S = typename decltype(e)::storage;
+    hipLaunchKernelGGL((geglu_bwd_kernel<decltype(e)>), grid, block, 0, st, (const S *)y, ldy, (const S *)gout, ldg, (S *)gy,
+                       ldgy, M, c8);
+  });
   return check_launch("lora_amd_geglu_bwd");
 }
 
@@ -1062,24 +1035,13 @@ extern "C" int lora_amd_add_layernorm_fwd(const void *x, const void *res, const 
                      aligned_for(res, dtype) && aligned_for(sum_out, dtype),
                  LORA_AMD_EINVAL, "layernorm_fwd: unaligned tensor");
   const bool add = res != nullptr;
-#define GO(E)                                                                                                    \
-  if (add)                                                                                                       \
-    hipLaunchKernelGGL((ln_fwd_kernel<E, true>), grid, block, 0, st, (const typename E::storage *)x,             \
-                       (const typename E::storage *)res, (const typename E::storage *)gamma,                     \
-                       (const typename E::storage *)beta, (typename E::storage *)sum_out,                        \
-                       (typename E::storage *)y, stats, M, c8, logL, eps);                                       \
-  else                                                                                                           \
-    hipLaunchKernelGGL((ln_fwd_kernel<E, false>), grid, block, 0, st, (const typename E::storage *)x,            \
-                       (const typename E::storage *)nullptr, (const typename E::storage *)gamma,                 \
-                       (const typename E::storage *)beta, (typename E::storage *)nullptr,                        \
-                       (typename E::storage *)y, stats, M, c8, logL, eps);                                       \
-  break
-  switch (dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
+  by_dtype(dtype, [&](auto e) {
+    by_bool(add, [&](auto a) {  // without the residual, res and sum_out are null
+      using S = typename decltype(e)::storage;
+      hipLaunchKernelGGL((ln_fwd_kernel<decltype(e), decltype(a)::value>), grid, block, 0, st, (const S *)x, (const S *)res,
+                         (const S *)gamma, (const S *)beta, (S *)sum_out, (S *)y, stats, M, c8, logL, eps);
+    });
+  });
   return check_launch("lora_amd_layernorm_fwd");
 }
 
@@ -1096,22 +1058,13 @@ extern "C" int lora_amd_add_layernorm_bwd(const void *x, const void *gout, const
   LORA_AMD_CHECK(aligned_for(x, dtype) && aligned_for(gout, dtype) && aligned_for(dx, dtype) && aligned_for(gamma, dtype) &&
                      aligned_for(gsum, dtype),
                  LORA_AMD_EINVAL, "layernorm_bwd: unaligned tensor");
-#define GO(E)                                                                                                    \
-  if (gsum != nullptr)                                                                                           \
-    hipLaunchKernelGGL((ln_bwd_kernel<E, true>), grid, block, 0, st, (const typename E::storage *)x,             \
-                       (const typename E::storage *)gout, (const typename E::storage *)gsum,                     \
-                       (const typename E::storage *)gamma, stats, (typename E::storage *)dx, M, c8, logL);       \
-  else                                                                                                           \
-    hipLaunchKernelGGL((ln_bwd_kernel<E, false>), grid, block, 0, st, (const typename E::storage *)x,            \
-                       (const typename E::storage *)gout, (const typename E::storage *)nullptr,                  \
-                       (const typename E::storage *)gamma, stats, (typename E::storage *)dx, M, c8, logL);       \
-  break
-  switch (dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
+  by_dtype(dtype, [&](auto e) {
+    by_bool(gsum != nullptr, [&](auto a) {
+      using S = typename decltype(e)::storage;
+      hipLaunchKernelGGL((ln_bwd_kernel<decltype(e), decltype(a)::value>), grid, block, 0, st, (const S *)x, (const S *)gout,
+                         (const S *)gsum, (const S *)gamma, stats, (S *)dx, M, c8, logL);
+    });
+  });
   return check_launch("lora_amd_layernorm_bwd");
 }
 
@@ -1142,27 +1095,18 @@ extern "C" int lora_amd_groupnorm_nhwc_fwd(const void *x, const void *gamma, con
   LORA_AMD_CHECK(x && gamma && beta && y && aff && workspace, LORA_AMD_EINVAL, "groupnorm_nhwc_fwd: null pointer");
   LORA_AMD_CHECK(aligned_for(x, dtype) && aligned_for(y, dtype) && ((uintptr_t)aff % 32) == 0, LORA_AMD_EINVAL,
                  "groupnorm_nhwc_fwd: unaligned tensor");
-#define GO(E)                                                                                                         \
-  {                                                                                                                   \
-    using S_ = typename E::storage;                                                                                   \
-    hipLaunchKernelGGL((gn_nhwc_stats_kernel<E>), grid, block, 0, st, (const S_ *)x, part, C, HW, q.cw, q.tiles,      \
-                       q.nslots, q.px, q.S);                                                                          \
-    hipLaunchKernelGGL((gn_nhwc_finalize_kernel<E>), gridg, block, 0, st, part, (const S_ *)gamma, (const S_ *)beta,  \
-                       addend, aff, C, HW, groups, q.px, q.S, eps);                                                   \
-    if (act)                                                                                                          \
-      hipLaunchKernelGGL((gn_nhwc_apply_kernel<E, true>), grid, block, 0, st, (const S_ *)x, aff, (S_ *)y, C, HW,     \
-                         q.cw, q.tiles, q.nslots, q.px, q.S);                                                         \
-    else                                                                                                              \
-      hipLaunchKernelGGL((gn_nhwc_apply_kernel<E, false>), grid, block, 0, st, (const S_ *)x, aff, (S_ *)y, C, HW,    \
-                         q.cw, q.tiles, q.nslots, q.px, q.S);                                                         \
-  }                                                                                                                   \
-  break
-  switch (dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
+  by_dtype(dtype, [&](auto e) {
+    using E = decltype(e);
+    using S = typename E::storage;
+    hipLaunchKernelGGL((gn_nhwc_stats_kernel<E>), grid, block, 0, st, (const S *)x, part, C, HW, q.cw, q.tiles,
+                       q.nslots, q.px, q.S);
+    hipLaunchKernelGGL((gn_nhwc_finalize_kernel<E>), gridg, block, 0, st, part, (const S *)gamma, (const S *)beta,
+                       addend, aff, C, HW, groups, q.px, q.S, eps);
+    by_bool(act != 0, [&](auto a) {
+      hipLaunchKernelGGL((gn_nhwc_apply_kernel<E, decltype(a)::value>), grid, block, 0, st, (const S *)x, aff, (S *)y, C, HW,
+                         q.cw, q.tiles, q.nslots, q.px, q.S);
+    });
+  });
   return check_launch("lora_amd_groupnorm_nhwc_fwd");
 }
 
@@ -1174,26 +1118,19 @@ extern "C" int lora_amd_groupnorm_nhwc_bwd(const void *x, const void *gout, cons
   LORA_AMD_CHECK(aligned_for(x, dtype) && aligned_for(gout, dtype) && aligned_for(dx, dtype) &&
                      aligned_for(gamma, dtype) && ((uintptr_t)aff % 32) == 0,
                  LORA_AMD_EINVAL, "groupnorm_nhwc_bwd: unaligned tensor");
-#define GO2(E, A)                                                                                                     \
-  {                                                                                                                   \
-    using S_ = typename E::storage;                                                                                   \
-    hipLaunchKernelGGL((gn_nhwc_bwd_kernel<E, A, false>), grid, block, 0, st, (const S_ *)x, (const S_ *)gout,        \
-                       (const S_ *)gamma, aff, part, (const float *)nullptr, (S_ *)nullptr, C, HW, q.cw, q.tiles,     \
-                       q.nslots, q.px, q.S);                                                                          \
-    hipLaunchKernelGGL(gn_nhwc_bwd_finalize_kernel, gridg, block, 0, st, part, cvec, C, HW, groups, q.S);             \
-    hipLaunchKernelGGL((gn_nhwc_bwd_kernel<E, A, true>), grid, block, 0, st, (const S_ *)x, (const S_ *)gout,         \
-                       (const S_ *)gamma, aff, (float *)nullptr, cvec, (S_ *)dx, C, HW, q.cw, q.tiles, q.nslots,      \
-                       q.px, q.S);                                                                                    \
-  }
-#define GO(E) \
-  if (act) GO2(E, true) else GO2(E, false) \
-  break
-  switch (dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
-#undef GO2
+  by_dtype(dtype, [&](auto e) {
+    by_bool(act != 0, [&](auto a) {
+      using E = decltype(e);
+      using S = typename E::storage;
+      constexpr bool A = decltype(a)::value;
+      hipLaunchKernelGGL((gn_nhwc_bwd_kernel<E, A, false>), grid, block, 0, st, (const S *)x, (const S *)gout,
+                         (const S *)gamma, aff, part, (const float *)nullptr, (S *)nullptr, C, HW, q.cw, q.tiles,
+                         q.nslots, q.px, q.S);
+      hipLaunchKernelGGL(gn_nhwc_bwd_finalize_kernel, gridg, block, 0, st, part, cvec, C, HW, groups, q.S);
+      hipLaunchKernelGGL((gn_nhwc_bwd_kernel<E, A, true>), grid, block, 0, st, (const S *)x, (const S *)gout,
+                         (const S *)gamma, aff, (float *)nullptr, cvec, (S *)dx, C, HW, q.cw, q.tiles, q.nslots,
+                         q.px, q.S);
+    });
+  });
   return check_launch("lora_amd_groupnorm_nhwc_bwd");
 }

@@ -604,17 +604,10 @@ static int launch_rowdot(const void *x, int64_t ldx, const void *f, void *t_out,
   int64_t rows_per_block = (M + 1023) / 1024;
   rows_per_block = ((rows_per_block + rows_iter - 1) / rows_iter) * rows_iter;
   const int grid = (int)((M + rows_per_block - 1) / rows_per_block);
-#define RD(RTV)                                                                                         \
-  hipLaunchKernelGGL((rowdot_kernel<EX, RTV, MASKED>), dim3(grid, batch), dim3(kThreads), 0, st, xp, ldx, f, fdt, \
-                     layout, tp, M, K, r, kt_cols, logL, (int)rows_per_block, scale, sel, selT, p, seed, offset, offset_dev, bs)
-  switch (RT) {
-    case 4: RD(4); break;
-    case 8: RD(8); break;
-    case 16: RD(16); break;
-    case 32: RD(32); break;
-    default: RD(64); break;
-  }
-#undef RD
+  by_int<4, 8, 16, 32, 64>(RT, [&](auto rt) {
+    hipLaunchKernelGGL((rowdot_kernel<EX, decltype(rt)::value, MASKED>), dim3(grid, batch), dim3(kThreads), 0, st, xp, ldx, f, fdt,
+                       layout, tp, M, K, r, kt_cols, logL, (int)rows_per_block, scale, sel, selT, p, seed, offset, offset_dev, bs);
+  });
   return check_launch("lora_amd_rowdot");
 }
 
@@ -642,18 +635,11 @@ static int launch_rank_update(void *y, int64_t ldy, const float *t, const void *
   if (rows > M) rows = M;
   const int tiles_n = (N + cols - 1) / cols;
   const int64_t tiles = tiles_n * ((M + rows - 1) / rows);
-#define RU(RTV)                                                                                            \
-  hipLaunchKernelGGL((rank_update_kernel<EY, RTV, DROP, RSC>), dim3((unsigned)tiles), dim3(kThreads), 0, st, yp, ldy, \
-                     t, f, fdt, layout, M, N, r, (int)rows, cols, tiles_n, scale, p, seed, offset, offset_dev, row_scale, \
-                     nsel, rps)
-  switch (RT) {
-    case 4: RU(4); break;
-    case 8: RU(8); break;
-    case 16: RU(16); break;
-    case 32: RU(32); break;
-    default: RU(64); break;
-  }
-#undef RU
+  by_int<4, 8, 16, 32, 64>(RT, [&](auto rt) {
+    hipLaunchKernelGGL((rank_update_kernel<EY, decltype(rt)::value, DROP, RSC>), dim3((unsigned)tiles), dim3(kThreads), 0, st, yp, ldy,
+                       t, f, fdt, layout, M, N, r, (int)rows, cols, tiles_n, scale, p, seed, offset, offset_dev, row_scale,
+                       nsel, rps);
+  });
   return check_launch("lora_amd_rank_update");
 }
 
@@ -683,16 +669,11 @@ static int launch_colreduce(const void *x, int64_t ldx, const float *t, float *d
   float *partial = reinterpret_cast<float *>(ws);
   for (int rank0 = 0; rank0 < r; rank0 += RT) {
     if (nrb > 0) {  // ranks beyond 16 take extra passes over X
-#define CR(RTV)                                                                                              \
-  hipLaunchKernelGGL((colreduce_stage1_kernel<EX, RTV, MASKED>), dim3((unsigned)(nrb * col_tiles), batch), dim3(kThreads), \
-                     0, st, xp, ldx, t, partial, M, K, r, rank0, col_tiles, p, seed, offset, offset_dev, bs)
-    switch (RT) {
-      case 4: CR(4); break;
-      case 8: CR(8); break;
-      default: CR(16); break;
+      by_int<4, 8, 16>(RT, [&](auto rt) {
+        hipLaunchKernelGGL((colreduce_stage1_kernel<EX, decltype(rt)::value, MASKED>), dim3((unsigned)(nrb * col_tiles), batch),
+                           dim3(kThreads), 0, st, xp, ldx, t, partial, M, K, r, rank0, col_tiles, p, seed, offset, offset_dev, bs);
+      });
     }
-    }
-#undef CR
     const int grid2 = (int)(((int64_t)RT * K + 63) / 64);
     hipLaunchKernelGGL(colreduce_stage2_kernel, dim3(grid2, batch), dim3(kThreads), 0, st, partial, d, nrb, K, r, RT,
                        rank0, out_layout, scale, beta, bs);
@@ -726,17 +707,13 @@ extern "C" int lora_amd_rowdot_masked(const void *x, int64_t ldx, const void *fa
   if (sel == nullptr && r16_rowdot(x, ldx, factor, factor_dtype, factor_layout, reinterpret_cast<float *>(t_out), M, K, r,
                                    x_dtype, scale, dropout_p, seed, offset, offset_dev, st))
     return check_launch("lora_amd_rowdot(mfma)");
-#define GO(E)                                                                                          \
-  return masked ? launch_rowdot<E, true>(x, ldx, factor, t_out, M, K, r, factor_dtype, factor_layout, scale, sel, \
-                                         sel_transposed, dropout_p, seed, offset, offset_dev, st)                  \
-                : launch_rowdot<E, false>(x, ldx, factor, t_out, M, K, r, factor_dtype, factor_layout, scale, sel, \
-                                          sel_transposed, 0.f, 0, 0, nullptr, st)
-  switch (x_dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
+  return by_dtype(x_dtype, [&](auto e) {
+    using E = decltype(e);
+    return masked ? launch_rowdot<E, true>(x, ldx, factor, t_out, M, K, r, factor_dtype, factor_layout, scale, sel,
+                                           sel_transposed, dropout_p, seed, offset, offset_dev, st)
+                  : launch_rowdot<E, false>(x, ldx, factor, t_out, M, K, r, factor_dtype, factor_layout, scale, sel,
+                                            sel_transposed, 0.f, 0, 0, nullptr, st);
+  });
 }
 
 extern "C" int lora_amd_rowdot(const void *x, int64_t ldx, const void *factor, void *t_out, int64_t M, int32_t K,
@@ -759,16 +736,12 @@ extern "C" int lora_amd_rank_update(void *y, int64_t ldy, const float *t, const 
   if (r16_rank_update(y, ldy, t, 1, 0, factor, factor_dtype, factor_layout, M, N, r, y_dtype, scale, dropout_p, seed, offset,
                       offset_dev, st))
     return check_launch("lora_amd_rank_update(mfma)");
-#define GO(E)                                                                                              \
-  return drop ? launch_rank_update<E, true>(y, ldy, t, factor, M, N, r, factor_dtype, factor_layout, scale, \
-                                            dropout_p, seed, offset, offset_dev, st)                                   \
-              : launch_rank_update<E, false>(y, ldy, t, factor, M, N, r, factor_dtype, factor_layout, scale, 0.f, 0, 0, nullptr, st)
-  switch (y_dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
+  return by_dtype(y_dtype, [&](auto e) {
+    using E = decltype(e);
+    return drop ? launch_rank_update<E, true>(y, ldy, t, factor, M, N, r, factor_dtype, factor_layout, scale,
+                                              dropout_p, seed, offset, offset_dev, st)
+                : launch_rank_update<E, false>(y, ldy, t, factor, M, N, r, factor_dtype, factor_layout, scale, 0.f, 0, 0, nullptr, st);
+  });
 }
 
 extern "C" int lora_amd_rank_update_rowscale(void *y, int64_t ldy, const float *t, const void *factor, int64_t M,
@@ -786,18 +759,14 @@ extern "C" int lora_amd_rank_update_rowscale(void *y, int64_t ldy, const float *
   LORA_AMD_CHECK(dropout_p >= 0.f && dropout_p < 1.f, LORA_AMD_EINVAL, "rank_update_rowscale: dropout p=%f", dropout_p);
   hipStream_t st = (hipStream_t)stream;
   const bool drop = dropout_p > 0.f;
-#define GO(E)                                                                                                       \
-  return drop ? launch_rank_update<E, true, true>(y, ldy, t, factor, M, N, r, factor_dtype, factor_layout, scale,   \
-                                                  dropout_p, seed, offset, nullptr, st, row_scale, nsel,            \
-                                                  rows_per_sample)                                                  \
-              : launch_rank_update<E, false, true>(y, ldy, t, factor, M, N, r, factor_dtype, factor_layout, scale,  \
-                                                   0.f, 0, 0, nullptr, st, row_scale, nsel, rows_per_sample)
-  switch (y_dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
+  return by_dtype(y_dtype, [&](auto e) {
+    using E = decltype(e);
+    return drop ? launch_rank_update<E, true, true>(y, ldy, t, factor, M, N, r, factor_dtype, factor_layout, scale,
+                                                    dropout_p, seed, offset, nullptr, st, row_scale, nsel,
+                                                    rows_per_sample)
+                : launch_rank_update<E, false, true>(y, ldy, t, factor, M, N, r, factor_dtype, factor_layout, scale,
+                                                     0.f, 0, 0, nullptr, st, row_scale, nsel, rows_per_sample);
+  });
 }
 
 extern "C" size_t lora_amd_colreduce_workspace(int64_t M, int32_t K, int32_t r) {
@@ -819,17 +788,13 @@ extern "C" int lora_amd_colreduce(const void *x, int64_t ldx, const float *t, fl
   LORA_AMD_CHECK(dropout_p >= 0.f && dropout_p < 1.f, LORA_AMD_EINVAL, "colreduce: dropout p=%f", dropout_p);
   hipStream_t st = (hipStream_t)stream;
   const bool masked = dropout_p > 0.f;
-#define GO(E)                                                                                               \
-  return masked ? launch_colreduce<E, true>(x, ldx, t, d_out, M, K, r, out_layout, scale, beta, dropout_p, seed, \
-                                            offset, offset_dev, workspace, workspace_bytes, st)                         \
-                : launch_colreduce<E, false>(x, ldx, t, d_out, M, K, r, out_layout, scale, beta, 0.f, 0, 0, nullptr, \
-                                             workspace, workspace_bytes, st)
-  switch (x_dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
+  return by_dtype(x_dtype, [&](auto e) {
+    using E = decltype(e);
+    return masked ? launch_colreduce<E, true>(x, ldx, t, d_out, M, K, r, out_layout, scale, beta, dropout_p, seed,
+                                              offset, offset_dev, workspace, workspace_bytes, st)
+                  : launch_colreduce<E, false>(x, ldx, t, d_out, M, K, r, out_layout, scale, beta, 0.f, 0, 0, nullptr,
+                                               workspace, workspace_bytes, st);
+  });
 }
 
 // ---- batched forms (cli_svd.py: every same-shape site of a model in one launch) ---------------------------------
@@ -842,15 +807,10 @@ extern "C" int lora_amd_rowdot_batched(const void *x, int64_t ldx, int64_t strid
   LORA_AMD_CHECK(dtype_ok(factor_dtype) && ldx >= K, LORA_AMD_EINVAL, "rowdot_batched: bad factor dtype / ldx");
   BatchStride bs{stride_x, stride_factor * dtype_size(factor_dtype), stride_t, 0, 0};
   hipStream_t st = (hipStream_t)stream;
-#define GO(E)                                                                                                     \
-  return launch_rowdot<E, false>(x, ldx, factor, t_out, M, K, r, factor_dtype, factor_layout, scale, nullptr, 0, 0.f, 0, \
-                                 0, nullptr, st, batch, bs)
-  switch (x_dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
+  return by_dtype(x_dtype, [&](auto e) {
+    return launch_rowdot<decltype(e), false>(x, ldx, factor, t_out, M, K, r, factor_dtype, factor_layout, scale, nullptr, 0, 0.f, 0,
+                                             0, nullptr, st, batch, bs);
+  });
 }
 
 extern "C" int lora_amd_colreduce_batched(const void *x, int64_t ldx, int64_t stride_x, const float *t, int64_t stride_t,
@@ -863,15 +823,10 @@ extern "C" int lora_amd_colreduce_batched(const void *x, int64_t ldx, int64_t st
                  "colreduce_batched: bad argument");
   BatchStride bs{stride_x, 0, stride_t, stride_d, 0};
   hipStream_t st = (hipStream_t)stream;
-#define GO(E)                                                                                                       \
-  return launch_colreduce<E, false>(x, ldx, t, d_out, M, K, r, out_layout, scale, 0.f, 0.f, 0, 0, nullptr, workspace, \
-                                    workspace_bytes, st, batch, bs)
-  switch (x_dtype) {
-    case LORA_AMD_F32: GO(f32_t);
-    case LORA_AMD_F16: GO(f16_t);
-    default: GO(bf16_t);
-  }
-#undef GO
+  return by_dtype(x_dtype, [&](auto e) {
+    return launch_colreduce<decltype(e), false>(x, ldx, t, d_out, M, K, r, out_layout, scale, 0.f, 0.f, 0, 0, nullptr, workspace,
+                                                workspace_bytes, st, batch, bs);
+  });
 }
 
 // ---- ragged forms (cli_svd.py: every shape group of a model in one launch) ---------------------------------------
@@ -920,15 +875,10 @@ extern "C" int lora_amd_rowdot_ragged(const lora_amd_ragged_desc *descs_dev, int
   LORA_AMD_CHECK(descs_dev && n >= 1 && grid1 >= 1 && grid1 < (1ll << 31), LORA_AMD_EINVAL, "rowdot_ragged: bad argument");
   LORA_AMD_CHECK(r >= 1 && r <= LORA_AMD_MAX_RANK, LORA_AMD_ERANK, "rowdot_ragged: rank %d outside [1,%d]", r, LORA_AMD_MAX_RANK);
   hipStream_t st = (hipStream_t)stream;
-#define RD(RTV) hipLaunchKernelGGL((rowdot_ragged_kernel<RTV>), dim3((unsigned)grid1), dim3(kThreads), 0, st, descs_dev, n, r, factor_layout, scale)
-  switch (rank_tile(r)) {
-    case 4: RD(4); break;
-    case 8: RD(8); break;
-    case 16: RD(16); break;
-    case 32: RD(32); break;
-    default: RD(64); break;
-  }
-#undef RD
+  by_int<4, 8, 16, 32, 64>(rank_tile(r), [&](auto rt) {
+    hipLaunchKernelGGL((rowdot_ragged_kernel<decltype(rt)::value>), dim3((unsigned)grid1), dim3(kThreads), 0, st, descs_dev, n, r,
+                       factor_layout, scale);
+  });
   return check_launch("lora_amd_rowdot_ragged");
 }
 
@@ -940,13 +890,10 @@ extern "C" int lora_amd_colreduce_ragged(const lora_amd_ragged_desc *descs_dev, 
   hipStream_t st = (hipStream_t)stream;
   const int RT = col_rank_tile(r);
   for (int rank0 = 0; rank0 < r; rank0 += RT) {  // ranks beyond 16 take extra passes over X
-#define CR(RTV) hipLaunchKernelGGL((colreduce_stage1_ragged_kernel<RTV>), dim3((unsigned)grid1), dim3(kThreads), 0, st, descs_dev, n, r, rank0)
-    switch (RT) {
-      case 4: CR(4); break;
-      case 8: CR(8); break;
-      default: CR(16); break;
-    }
-#undef CR
+    by_int<4, 8, 16>(RT, [&](auto rt) {
+      hipLaunchKernelGGL((colreduce_stage1_ragged_kernel<decltype(rt)::value>), dim3((unsigned)grid1), dim3(kThreads), 0, st, descs_dev,
+                         n, r, rank0);
+    });
     hipLaunchKernelGGL(colreduce_stage2_ragged_kernel, dim3((unsigned)grid2), dim3(kThreads), 0, st, descs_dev, n, r, RT,
                        rank0, out_layout, scale);
   }

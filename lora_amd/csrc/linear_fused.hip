@@ -1197,21 +1197,17 @@ extern "C" int lora_amd_linear_fwd(const void *x, int64_t ldx, void *y, int64_t 
   const dim3 grid(gx, (unsigned)ny);
   hipStream_t st = (hipStream_t)stream;
   const bool drop = dropout_p > 0.f;
-#define FW(E, RTV, D)                                                                                          \
-  hipLaunchKernelGGL((linear_fwd_kernel<E, RTV, D>), grid, dim3(kFT), 0, st,                                   \
-                     reinterpret_cast<const typename E::storage *>(x), ldx, reinterpret_cast<typename E::storage *>(y), \
-                     ldy, down, up, factor_dtype, t_out, M, K, N, r, kt, nt, cols_per_y, logL, (int)rpb, scale, sel, \
-                     dropout_p, seed, offset, offset_dev)
-#define FW_RT(E, D) do { if (RT == 4) FW(E, 4, D); else if (RT == 8) FW(E, 8, D); else FW(E, 16, D); } while (0)
-#define FW_E(E) do { if (drop) FW_RT(E, true); else FW_RT(E, false); } while (0)
-  switch (act_dtype) {
-    case LORA_AMD_F32: FW_E(f32_t); break;
-    case LORA_AMD_F16: FW_E(f16_t); break;
-    default: FW_E(bf16_t); break;
-  }
-#undef FW_E
-#undef FW_RT
-#undef FW
+  by_dtype(act_dtype, [&](auto e) {
+    by_bool(drop, [&](auto d) {
+      by_int<4, 8, 16>(RT, [&](auto rt) {
+        using E = decltype(e);
+        hipLaunchKernelGGL((linear_fwd_kernel<E, decltype(rt)::value, decltype(d)::value>), grid, dim3(kFT), 0, st,
+                           reinterpret_cast<const typename E::storage *>(x), ldx, reinterpret_cast<typename E::storage *>(y),
+                           ldy, down, up, factor_dtype, t_out, M, K, N, r, kt, nt, cols_per_y, logL, (int)rpb, scale, sel,
+                           dropout_p, seed, offset, offset_dev);
+      });
+    });
+  });
   return check_launch("lora_amd_linear_fwd");
 }
 
@@ -1233,25 +1229,23 @@ extern "C" int lora_amd_linear_bwd_g(const void *g, int64_t ldg, const float *t,
   if (RT == 16 && r16_bwd_g(g, ldg, t, up, factor_dtype, gt_part, up_part, M, N, r, q.log_ct8, q.nct, q.rows_per_block, q.nrb,
                             act_dtype, scale, dropout_p, seed, offset, offset_dev, st))
     return check_launch("lora_amd_linear_bwd_g(mfma)");
-#define BG(E, RTV, D)                                                                                       \
-  hipLaunchKernelGGL((linear_bwd_g_kernel<E, RTV, D>), dim3(grid), dim3(kFT), 0, st,                        \
-                     reinterpret_cast<const typename E::storage *>(g), ldg, t, up, factor_dtype, gt_part, up_part, M, \
-                     N, r, q.log_ct8, q.nct, q.rows_per_block, scale, dropout_p, seed, offset, offset_dev)
-#define BG16(E, D)                                                                                          \
-  hipLaunchKernelGGL((linear_bwd_g_kernel<E, 16, D, true>), dim3(grid), dim3(kFT), 0, st,                   \
-                     reinterpret_cast<const typename E::storage *>(g), ldg, t, up, factor_dtype, gt_part, up_part, M, \
-                     N, r, q.log_ct8, q.nct, q.rows_per_block, scale, dropout_p, seed, offset, offset_dev)
-#define BG_RT(E, D) do { if (RT == 4) BG(E, 4, D); else if (RT == 8) BG(E, 8, D); else BG16(E, D); } while (0)
-#define BG_E(E) do { if (drop) BG_RT(E, true); else BG_RT(E, false); } while (0)
-  switch (act_dtype) {
-    case LORA_AMD_F32: BG_E(f32_t); break;
-    case LORA_AMD_F16: BG_E(f16_t); break;
-    default: BG_E(bf16_t); break;
-  }
-#undef BG_E
-#undef BG_RT
-#undef BG16
-#undef BG
+  by_dtype(act_dtype, [&](auto e) {
+    by_bool(drop, [&](auto d) {
+      by_int<4, 8, 16>(RT, [&](auto rt) {
+        using E = decltype(e);
+        constexpr int RTV = decltype(rt)::value;
+        // rank tile 16 takes the kernel's fourth template argument; 4 and 8 leave it at its default
+        if constexpr (RTV == 16)
+          hipLaunchKernelGGL((linear_bwd_g_kernel<E, 16, decltype(d)::value, true>), dim3(grid), dim3(kFT), 0, st,
+                             reinterpret_cast<const typename E::storage *>(g), ldg, t, up, factor_dtype, gt_part, up_part, M,
+                             N, r, q.log_ct8, q.nct, q.rows_per_block, scale, dropout_p, seed, offset, offset_dev);
+        else
+          hipLaunchKernelGGL((linear_bwd_g_kernel<E, RTV, decltype(d)::value>), dim3(grid), dim3(kFT), 0, st,
+                             reinterpret_cast<const typename E::storage *>(g), ldg, t, up, factor_dtype, gt_part, up_part, M,
+                             N, r, q.log_ct8, q.nct, q.rows_per_block, scale, dropout_p, seed, offset, offset_dev);
+      });
+    });
+  });
   return check_launch("lora_amd_linear_bwd_g");
 }
 
@@ -1297,21 +1291,17 @@ extern "C" int lora_amd_linear_bwd_x(const void *x, int64_t ldx, void *dx, int64
   const unsigned grid = (unsigned)(q.nrb * q.nct);
   hipStream_t st = (hipStream_t)stream;
   const bool has_dx = dx != nullptr;
-#define BX(E, RTV, D)                                                                                        \
-  hipLaunchKernelGGL((linear_bwd_x_kernel<E, RTV, D>), dim3(grid), dim3(kFT), 0, st,                         \
-                     reinterpret_cast<const typename E::storage *>(x), ldx, reinterpret_cast<typename E::storage *>(dx), \
-                     lddx, gt_part, nct_g, down, factor_dtype, sel, down_part, M, K, r, q.log_ct8, q.nct,     \
-                     q.rows_per_block)
-#define BX_RT(E, D) do { if (RT == 4) BX(E, 4, D); else if (RT == 8) BX(E, 8, D); else BX(E, 16, D); } while (0)
-#define BX_E(E) do { if (has_dx) BX_RT(E, true); else BX_RT(E, false); } while (0)
-  switch (act_dtype) {
-    case LORA_AMD_F32: BX_E(f32_t); break;
-    case LORA_AMD_F16: BX_E(f16_t); break;
-    default: BX_E(bf16_t); break;
-  }
-#undef BX_E
-#undef BX_RT
-#undef BX
+  by_dtype(act_dtype, [&](auto e) {
+    by_bool(has_dx, [&](auto d) {
+      by_int<4, 8, 16>(RT, [&](auto rt) {
+        using E = decltype(e);
+        hipLaunchKernelGGL((linear_bwd_x_kernel<E, decltype(rt)::value, decltype(d)::value>), dim3(grid), dim3(kFT), 0, st,
+                           reinterpret_cast<const typename E::storage *>(x), ldx, reinterpret_cast<typename E::storage *>(dx),
+                           lddx, gt_part, nct_g, down, factor_dtype, sel, down_part, M, K, r, q.log_ct8, q.nct,
+                           q.rows_per_block);
+      });
+    });
+  });
   return check_launch("lora_amd_linear_bwd_x");
 }
 
@@ -1373,15 +1363,11 @@ static int bwd_factors_impl(const void *g, int64_t ldg, const float *t, float *u
               x_head_dim / 8, x_head_pad / 8, 0.f, 0, 0, nullptr};
   const unsigned grid = (unsigned)(a.nblocks + b.nblocks);
   hipStream_t st = (hipStream_t)stream;
-#define BF(E, RTV) hipLaunchKernelGGL((linear_bwd_factors_kernel<E, RTV>), dim3(grid), dim3(kFT), 0, st, a, b, M, r)
-#define BF_E(E) do { if (RT == 4) BF(E, 4); else if (RT == 8) BF(E, 8); else BF(E, 16); } while (0)
-  switch (act_dtype) {
-    case LORA_AMD_F32: BF_E(f32_t); break;
-    case LORA_AMD_F16: BF_E(f16_t); break;
-    default: BF_E(bf16_t); break;
-  }
-#undef BF_E
-#undef BF
+  by_dtype(act_dtype, [&](auto e) {
+    by_int<4, 8, 16>(RT, [&](auto rt) {
+      hipLaunchKernelGGL((linear_bwd_factors_kernel<decltype(e), decltype(rt)::value>), dim3(grid), dim3(kFT), 0, st, a, b, M, r);
+    });
+  });
   return check_launch("lora_amd_linear_bwd_factors");
 }
 
@@ -1457,19 +1443,14 @@ extern "C" int lora_amd_linear_bwd_factors_self(const void *g, int64_t ldg, cons
   hipStream_t st = (hipStream_t)stream;
   // both factor slabs in LDS at once -> the wave-specialised kernel (one row block per workgroup, no column splits)
   const bool dual = (int64_t)RT * (N + K) <= kSelfLdsFloats && a.logL_x >= 0;
-#define FS(E, RTV)                                                                                                    \
-  do {                                                                                                                \
-    if (dual) hipLaunchKernelGGL((linear_bwd_factors_self_dual_kernel<E, RTV>), dim3((unsigned)nrb), dim3(kDualThreads), 0, st, a); \
-    else hipLaunchKernelGGL((linear_bwd_factors_self_kernel<E, RTV>), dim3(grid), dim3(kFT), 0, st, a);                \
-  } while (0)
-#define FS_E(E) do { if (RT == 4) FS(E, 4); else if (RT == 8) FS(E, 8); else FS(E, 16); } while (0)
-  switch (act_dtype) {
-    case LORA_AMD_F32: FS_E(f32_t); break;
-    case LORA_AMD_F16: FS_E(f16_t); break;
-    default: FS_E(bf16_t); break;
-  }
-#undef FS_E
-#undef FS
+  by_dtype(act_dtype, [&](auto e) {
+    by_int<4, 8, 16>(RT, [&](auto rt) {
+      using E = decltype(e);
+      constexpr int RTV = decltype(rt)::value;
+      if (dual) hipLaunchKernelGGL((linear_bwd_factors_self_dual_kernel<E, RTV>), dim3((unsigned)nrb), dim3(kDualThreads), 0, st, a);
+      else hipLaunchKernelGGL((linear_bwd_factors_self_kernel<E, RTV>), dim3(grid), dim3(kFT), 0, st, a);
+    });
+  });
   return check_launch("lora_amd_linear_bwd_factors_self");
 }
 
@@ -1513,15 +1494,11 @@ extern "C" int lora_amd_linear_bwd_factors_self_ragged(const lora_amd_self_site 
   const int RT = frank_tile(rank);
   hipStream_t st = (hipStream_t)stream;
   // loads in flight per lane: 4 measured best in the one-launch pass (8 costs occupancy: 1.9 vs ~1.1 ms on configs[1])
-#define FR(E, RTV) hipLaunchKernelGGL((linear_bwd_factors_self_ragged_kernel<E, RTV, 4>), dim3((unsigned)grid), dim3(kFT), 0, st, sites_dev, n)
-#define FR_E(E) do { if (RT == 4) FR(E, 4); else if (RT == 8) FR(E, 8); else FR(E, 16); } while (0)
-  switch (act_dtype) {
-    case LORA_AMD_F32: FR_E(f32_t); break;
-    case LORA_AMD_F16: FR_E(f16_t); break;
-    default: FR_E(bf16_t); break;
-  }
-#undef FR_E
-#undef FR
+  by_dtype(act_dtype, [&](auto e) {
+    by_int<4, 8, 16>(RT, [&](auto rt) {
+      hipLaunchKernelGGL((linear_bwd_factors_self_ragged_kernel<decltype(e), decltype(rt)::value, 4>), dim3((unsigned)grid), dim3(kFT), 0, st, sites_dev, n);
+    });
+  });
   return check_launch("lora_amd_linear_bwd_factors_self_ragged");
 }
 

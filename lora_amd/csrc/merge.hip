@@ -277,19 +277,16 @@ static void launch_merge(const lora_amd_merge_site *sites, int n_sites, int64_t 
                          int rounding, int grid_slab, int n_fast, int rt_fast, hipStream_t st) {
   const bool ref = rounding == LORA_AMD_ROUND_REFERENCE;
   if (n_fast > 0) {
-#define CO(RTV, R)                                                                                       \
-  do {                                                                                                   \
-    if (g_merge_nt)                                                                                      \
-      hipLaunchKernelGGL((merge_co_kernel<EW, EAB, RTV, R, true>), dim3((unsigned)total_tiles),          \
-                         dim3(kMergeThreads), 0, st, sites, n_sites, total_tiles, alpha);                \
-    else                                                                                                 \
-      hipLaunchKernelGGL((merge_co_kernel<EW, EAB, RTV, R, false>), dim3((unsigned)total_tiles),         \
-                         dim3(kMergeThreads), 0, st, sites, n_sites, total_tiles, alpha);                \
-  } while (0)
-#define CO_R(RTV) do { if (ref) CO(RTV, LORA_AMD_ROUND_REFERENCE); else CO(RTV, LORA_AMD_ROUND_ONCE); } while (0)
-    if (rt_fast <= 4) CO_R(4); else if (rt_fast <= 8) CO_R(8); else CO_R(16);
-#undef CO_R
-#undef CO
+    // the planner reports 4, 8 or 16; any other value maps as it always did: up to 4 -> 4, up to 8 -> 8, else 16
+    by_int<4, 8, 16>(rt_fast <= 4 ? 4 : rt_fast <= 8 ? 8 : 16, [&](auto rt) {
+      by_bool(ref, [&](auto rf) {
+        by_bool(g_merge_nt != 0, [&](auto nt) {
+          constexpr int R = decltype(rf)::value ? LORA_AMD_ROUND_REFERENCE : LORA_AMD_ROUND_ONCE;
+          hipLaunchKernelGGL((merge_co_kernel<EW, EAB, decltype(rt)::value, R, decltype(nt)::value>), dim3((unsigned)total_tiles),
+                             dim3(kMergeThreads), 0, st, sites, n_sites, total_tiles, alpha);
+        });
+      });
+    });
   }
   if (n_fast < n_sites) {
     if (ref)
@@ -392,18 +389,11 @@ extern "C" int lora_amd_merge_batched(const lora_amd_merge_site *sites_dev, int3
   const int64_t cap = 256 * g_merge_blocks_per_cu;
   const int grid = (int)(total_tiles < cap ? total_tiles : cap);
   const int n_fast = summary->n_fast_sites, rt_fast = summary->rank_tile_fast;
-#define DISPATCH_AB(EW)                                                                                           \
-  switch (ab_dtype) {                                                                                             \
-    case LORA_AMD_F32: launch_merge<EW, f32_t>(sites_dev, n_sites, total_tiles, alpha, rounding, grid, n_fast, rt_fast, st); break; \
-    case LORA_AMD_F16: launch_merge<EW, f16_t>(sites_dev, n_sites, total_tiles, alpha, rounding, grid, n_fast, rt_fast, st); break; \
-    default: launch_merge<EW, bf16_t>(sites_dev, n_sites, total_tiles, alpha, rounding, grid, n_fast, rt_fast, st); break;          \
-  }
-  switch (w_dtype) {
-    case LORA_AMD_F32: DISPATCH_AB(f32_t); break;
-    case LORA_AMD_F16: DISPATCH_AB(f16_t); break;
-    default: DISPATCH_AB(bf16_t); break;
-  }
-#undef DISPATCH_AB
+  by_dtype(w_dtype, [&](auto ew) {
+    by_dtype(ab_dtype, [&](auto eab) {
+      launch_merge<decltype(ew), decltype(eab)>(sites_dev, n_sites, total_tiles, alpha, rounding, grid, n_fast, rt_fast, st);
+    });
+  });
   return check_launch("lora_amd_merge_batched");
 }
 

@@ -278,23 +278,17 @@ extern "C" int lora_amd_merge_step(const lora_amd_mstep_site *sites_dev, int32_t
   const int RT = rank_max <= 4 ? 4 : rank_max <= 8 ? 8 : 16;
   const bool dith = rounding == LORA_AMD_ROUND_DITHER;
   const int dmode = dith ? g_ms_dither : 0;
-#define MS_K(E, RTV, DV, TRV, TCV)                                                                                     \
-  hipLaunchKernelGGL((merge_step_kernel<E, RTV, DV, TRV, TCV>), dim3((unsigned)total_tiles), dim3(kMsThreads), 0, st, sites_dev, n, alpha)
-#define MS_D(E, RTV, TRV, TCV)                                                                                         \
-  do { if (dmode == 0) MS_K(E, RTV, 0, TRV, TCV); else if (dmode == 1) MS_K(E, RTV, 1, TRV, TCV); else MS_K(E, RTV, 2, TRV, TCV); } while (0)
-#define MS(E, RTV)                                                                                                     \
-  do {                                                                                                                 \
-    if (ms_tile == 0) MS_D(E, RTV, 128, 64);                                                                           \
-    else if (ms_tile == 1) MS_D(E, RTV, 64, 128);                                                                      \
-    else if (ms_tile == 2) MS_D(E, RTV, 128, 128);                                                                     \
-    else MS_D(E, RTV, 256, 64);                                                                                        \
-  } while (0)
-#define MS_E(E) do { if (RT == 4) MS(E, 4); else if (RT == 8) MS(E, 8); else MS(E, 16); } while (0)
-  if (w_dtype == LORA_AMD_F16) MS_E(f16_t); else MS_E(bf16_t);
-#undef MS_E
-#undef MS
-#undef MS_D
-#undef MS_K
+  by_dtype<f16_t, bf16_t>(w_dtype, [&](auto e) {
+    by_int<4, 8, 16>(RT, [&](auto rt) {
+      by_int<0, 1, 2, 3>(ms_tile, [&](auto ti) {
+        by_int<0, 1, 2>(dmode, [&](auto dv) {
+          constexpr MsTile tg = kMsTiles[decltype(ti)::value];
+          hipLaunchKernelGGL((merge_step_kernel<decltype(e), decltype(rt)::value, decltype(dv)::value, tg.tr, tg.tc>),
+                             dim3((unsigned)total_tiles), dim3(kMsThreads), 0, st, sites_dev, n, alpha);
+        });
+      });
+    });
+  });
   return check_launch("lora_amd_merge_step");
 }
 

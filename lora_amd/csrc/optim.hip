@@ -249,17 +249,13 @@ extern "C" int lora_amd_ti_rows_step(void *table, const void *table_grad, const 
                  "ti_rows_step: bad argument");
   if (n_tokens == 0) return LORA_AMD_OK;
   hipStream_t st = (hipStream_t)stream;
-#define TI(E)                                                                                                   \
-  hipLaunchKernelGGL((ti_rows_step_kernel<E>), dim3(n_tokens), dim3(kOptThreads), 0, st,                          \
-                     reinterpret_cast<typename E::storage *>(table),                                             \
-                     reinterpret_cast<const typename E::storage *>(table_grad), ids_dev, rows, exp_avg, exp_avg_sq, \
-                     hidden, lr, beta1, beta2, eps, weight_decay, grad_scale, step, decay_lambda, target_norm)
-  switch (table_dtype) {
-    case LORA_AMD_F32: TI(f32_t); break;
-    case LORA_AMD_F16: TI(f16_t); break;
-    default: TI(bf16_t); break;
-  }
-#undef TI
+  by_dtype(table_dtype, [&](auto e) {
+    using E = decltype(e);
+    hipLaunchKernelGGL((ti_rows_step_kernel<E>), dim3(n_tokens), dim3(kOptThreads), 0, st,
+                       reinterpret_cast<typename E::storage *>(table),
+                       reinterpret_cast<const typename E::storage *>(table_grad), ids_dev, rows, exp_avg, exp_avg_sq,
+                       hidden, lr, beta1, beta2, eps, weight_decay, grad_scale, step, decay_lambda, target_norm);
+  });
   return check_launch("lora_amd_ti_rows_step");
 }
 

@@ -713,11 +713,10 @@ bool r16_rowdot(const void *x, int64_t ldx, const void *f, int fdt, int layout, 
   const unsigned block = (unsigned)(64 * wps * slabs);
   const unsigned grid = (unsigned)((nslabs + slabs - 1) / slabs);
   const float *ff = reinterpret_cast<const float *>(f);
-#define RD(E, D)                                                                                                      \
-  hipLaunchKernelGGL((rowdot16_mfma_kernel<E, D>), dim3(grid), dim3(block), 0, st,                                    \
-                     reinterpret_cast<const typename E::storage *>(x), ldx, ff, layout, t_out, M, C, r, wps, scale, p, seed, offset, offset_dev)
-  if (p > 0.f) RD(bf16_t, true); else RD(bf16_t, false);
-#undef RD
+  by_bool(p > 0.f, [&](auto d) {
+    hipLaunchKernelGGL((rowdot16_mfma_kernel<bf16_t, decltype(d)::value>), dim3(grid), dim3(block), 0, st,
+                       reinterpret_cast<const bf16_t::storage *>(x), ldx, ff, layout, t_out, M, C, r, wps, scale, p, seed, offset, offset_dev);
+  });
   return true;
 }
 
@@ -732,12 +731,11 @@ bool r16_rank_update(void *y, int64_t ldy, const float *t, int nparts, int64_t p
   const int64_t gx = (M + rows - 1) / rows;
   if (gx > 0x7fffffff || ny > 65535) return false;
   const float *ff = reinterpret_cast<const float *>(f);
-#define RU(E, D)                                                                                                      \
-  hipLaunchKernelGGL((rank_update16_mfma_kernel<E, D>), dim3((unsigned)gx, (unsigned)ny), dim3(kR16Threads), 0, st,   \
-                     reinterpret_cast<typename E::storage *>(y), ldy, t, nparts, part_stride, ff, layout, M, N, r,    \
-                     rows, scale, p, seed, offset, offset_dev)
-  if (p > 0.f) RU(bf16_t, true); else RU(bf16_t, false);
-#undef RU
+  by_bool(p > 0.f, [&](auto d) {
+    hipLaunchKernelGGL((rank_update16_mfma_kernel<bf16_t, decltype(d)::value>), dim3((unsigned)gx, (unsigned)ny), dim3(kR16Threads), 0, st,
+                       reinterpret_cast<bf16_t::storage *>(y), ldy, t, nparts, part_stride, ff, layout, M, N, r,
+                       rows, scale, p, seed, offset, offset_dev);
+  });
   return true;
 }
 
@@ -750,12 +748,11 @@ bool r16_bwd_g(const void *g, int64_t ldg, const float *t, const void *up, int f
     return false;
   const unsigned grid = (unsigned)(nrb * nct);
   const float *uf = reinterpret_cast<const float *>(up);
-#define BG(E, D)                                                                                                      \
-  hipLaunchKernelGGL((bwd_g16_mfma_kernel<E, D>), dim3(grid), dim3(kR16Threads), 0, st,                               \
-                     reinterpret_cast<const typename E::storage *>(g), ldg, t, uf, gt_part, up_part, M, N, r, log_ct8, nct, \
-                     rows_per_block, scale, p, seed, offset, offset_dev, gt_out, counters)
-  if (p > 0.f) BG(bf16_t, true); else BG(bf16_t, false);
-#undef BG
+  by_bool(p > 0.f, [&](auto d) {
+    hipLaunchKernelGGL((bwd_g16_mfma_kernel<bf16_t, decltype(d)::value>), dim3(grid), dim3(kR16Threads), 0, st,
+                       reinterpret_cast<const bf16_t::storage *>(g), ldg, t, uf, gt_part, up_part, M, N, r, log_ct8, nct,
+                       rows_per_block, scale, p, seed, offset, offset_dev, gt_out, counters);
+  });
   return true;
 }
 
@@ -800,8 +797,9 @@ extern "C" int lora_amd_rowdot16_planes(const lora_amd_planes_desc *descs_dev, i
   LORA_AMD_CHECK(r >= 1 && r <= 16, LORA_AMD_ERANK, "rowdot16_planes: %d output columns outside [1,16]", r);
   LORA_AMD_CHECK(plane_dtype == LORA_AMD_BF16 || plane_dtype == LORA_AMD_F16, LORA_AMD_EINVAL, "rowdot16_planes: 16-bit planes only");
   hipStream_t st = (hipStream_t)stream;
-  if (plane_dtype == LORA_AMD_F16) hipLaunchKernelGGL((rowdot16_planes_kernel<f16_t, false>), dim3((unsigned)grid), dim3(1024), 0, st, descs_dev, n, r);
-  else hipLaunchKernelGGL((rowdot16_planes_kernel<bf16_t, false>), dim3((unsigned)grid), dim3(1024), 0, st, descs_dev, n, r);
+  by_dtype<f16_t, bf16_t>(plane_dtype, [&](auto e) {
+    hipLaunchKernelGGL((rowdot16_planes_kernel<decltype(e), false>), dim3((unsigned)grid), dim3(1024), 0, st, descs_dev, n, r);
+  });
   return check_launch("lora_amd_rowdot16_planes");
 }
 
@@ -810,13 +808,12 @@ extern "C" int lora_amd_rowdot16_planes_packed(const lora_amd_planes_desc *descs
   LORA_AMD_CHECK(descs_dev && n >= 1 && grid >= 1 && grid < (1ll << 31), LORA_AMD_EINVAL, "rowdot16_planes_packed: bad argument");
   LORA_AMD_CHECK(plane_dtype == LORA_AMD_BF16 || plane_dtype == LORA_AMD_F16, LORA_AMD_EINVAL, "rowdot16_planes_packed: 16-bit planes only");
   hipStream_t st = (hipStream_t)stream;
-#define RP(E)                                                                                                          \
-  do {   /* ROWLD: pieces fetched four lanes per row (kernel comment) */                                               \
-    if (hi_only) hipLaunchKernelGGL((rowdot16_planes_kernel<E, true, false, true>), dim3((unsigned)grid), dim3(1024), 0, st, descs_dev, n, 16); \
-    else hipLaunchKernelGGL((rowdot16_planes_kernel<E, true, true, true>), dim3((unsigned)grid), dim3(1024), 0, st, descs_dev, n, 16);          \
-  } while (0)
-  if (plane_dtype == LORA_AMD_F16) RP(f16_t); else RP(bf16_t);
-#undef RP
+  by_dtype<f16_t, bf16_t>(plane_dtype, [&](auto e) {
+    by_bool(hi_only != 0, [&](auto ho) {  // ROWLD: pieces fetched four lanes per row (kernel comment)
+      hipLaunchKernelGGL((rowdot16_planes_kernel<decltype(e), true, !decltype(ho)::value, true>), dim3((unsigned)grid), dim3(1024), 0, st,
+                         descs_dev, n, 16);
+    });
+  });
   return check_launch("lora_amd_rowdot16_planes_packed");
 }
 
@@ -825,8 +822,9 @@ extern "C" int lora_amd_split16_ragged(const lora_amd_split_desc *descs_dev, int
   LORA_AMD_CHECK(descs_dev && n >= 1 && blocks >= 1 && blocks < (1ll << 31), LORA_AMD_EINVAL, "split16_ragged: bad argument");
   LORA_AMD_CHECK(plane_dtype == LORA_AMD_BF16 || plane_dtype == LORA_AMD_F16, LORA_AMD_EINVAL, "split16_ragged: 16-bit planes only");
   hipStream_t st = (hipStream_t)stream;
-  if (plane_dtype == LORA_AMD_F16) hipLaunchKernelGGL(split16_ragged_kernel<f16_t>, dim3((unsigned)blocks), dim3(256), 0, st, descs_dev, n);
-  else hipLaunchKernelGGL(split16_ragged_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, descs_dev, n);
+  by_dtype<f16_t, bf16_t>(plane_dtype, [&](auto e) {
+    hipLaunchKernelGGL(split16_ragged_kernel<decltype(e)>, dim3((unsigned)blocks), dim3(256), 0, st, descs_dev, n);
+  });
   return check_launch("lora_amd_split16_ragged");
 }
 
@@ -835,7 +833,8 @@ extern "C" int lora_amd_split16_transpose(const lora_amd_splitt_desc *descs_dev,
   LORA_AMD_CHECK(descs_dev && n >= 1 && tiles >= 1 && tiles < (1ll << 31), LORA_AMD_EINVAL, "split16_transpose: bad argument");
   LORA_AMD_CHECK(plane_dtype == LORA_AMD_BF16 || plane_dtype == LORA_AMD_F16, LORA_AMD_EINVAL, "split16_transpose: 16-bit planes only");
   hipStream_t st = (hipStream_t)stream;
-  if (plane_dtype == LORA_AMD_F16) hipLaunchKernelGGL(split16_transpose_kernel<f16_t>, dim3((unsigned)tiles), dim3(256), 0, st, descs_dev, n);
-  else hipLaunchKernelGGL(split16_transpose_kernel<bf16_t>, dim3((unsigned)tiles), dim3(256), 0, st, descs_dev, n);
+  by_dtype<f16_t, bf16_t>(plane_dtype, [&](auto e) {
+    hipLaunchKernelGGL(split16_transpose_kernel<decltype(e)>, dim3((unsigned)tiles), dim3(256), 0, st, descs_dev, n);
+  });
   return check_launch("lora_amd_split16_transpose");
 }
