@@ -122,7 +122,13 @@ int lora_amd_merge_batched(const lora_amd_merge_site *sites_dev, int32_t n_sites
  * rounding: LORA_AMD_ROUND_ONCE (nearest even) or LORA_AMD_ROUND_DITHER: nearest after adding a fixed per-element dither
  * hash(dither_key, n, k) in [0, 1) ulp — P(round away from zero) = frac((W + delta) / ulp), exactly W where delta = 0,
  * identical from step to step: a delta below half an ulp of the frozen weight survives in the sum over a row instead of
- * vanishing element by element.  tiles_k / tile_begin are filled by the plan (host, no GPU needed). */
+ * vanishing element by element.  tiles_k / tile_begin are filled by the plan (host, no GPU needed).
+ * src_f32 (the field that was `reserved`; same offset): 0 = w has the output dtype (zero-initialised tables: as before);
+ * 1 = w is the frozen f32 MASTER [N, K] (f32 models under 16-bit autocast): the value is fmaf(alpha, up down, W32) rounded
+ * ONCE to the 16-bit output dtype, 4 + 2 + 2 bytes per element with out_t instead of 2 + 2 + 2.  Where W and alpha up down
+ * cancel — |value| < 2^-11 (bf16; f16: 2^-8) of |W| + |alpha| sum_j |up_j| max|down_j| (the maximum over the 8-column chunk),
+ * about one element in a thousand — the element is formed again in f64 (exact products, same rank order) before that one
+ * rounding: a bit-for-bit restatement must do the same. */
 typedef struct lora_amd_mstep_site {
   const void *w;
   const float *up, *down;
@@ -131,11 +137,14 @@ typedef struct lora_amd_mstep_site {
   int32_t N, K, r;
   int32_t row_d, row_D, col_d, col_D;
   int32_t dither_key;
-  int32_t tiles_k, reserved;
+  int32_t tiles_k, src_f32;
   int64_t tile_begin;
 } lora_amd_mstep_site;
+/* w_dtype: the OUTPUT dtype (LORA_AMD_F16 / LORA_AMD_BF16; LORA_AMD_F32 is refused).  Every site of a table has the same
+ * src_f32 (a mixed table: LORA_AMD_EINVAL, the message names the site). */
 int lora_amd_merge_step_plan(lora_amd_mstep_site *sites_host, int32_t n, int32_t w_dtype, int64_t *plan_value);
-/* plan_value: what the plan returned (tile count and tile geometry, opaque) */
+/* plan_value: what the plan returned (tile count, tile geometry and the table's source type, opaque): the launch picks the
+ * 16-bit-source or the f32-source kernel from it.  w_dtype: the output dtype, as planned. */
 int lora_amd_merge_step(const lora_amd_mstep_site *sites_dev, int32_t n, int64_t plan_value, int32_t rank_max,
                         int32_t w_dtype, float alpha, int32_t rounding, void *stream);
 /* Tuning hook (scripts/kbench.py): tile geometry 0..3 = 128x64 | 64x128 | 128x128 | 256x64 (rows x columns; applies to

@@ -187,7 +187,7 @@ class MstepSite(C.Structure):
         ("ld_out", C.c_int64), ("ld_out_t", C.c_int64),
         ("N", C.c_int32), ("K", C.c_int32), ("r", C.c_int32),
         ("row_d", C.c_int32), ("row_D", C.c_int32), ("col_d", C.c_int32), ("col_D", C.c_int32),
-        ("dither_key", C.c_int32), ("tiles_k", C.c_int32), ("reserved", C.c_int32),
+        ("dither_key", C.c_int32), ("tiles_k", C.c_int32), ("src_f32", C.c_int32),
         ("tile_begin", C.c_int64),
     ]
 
@@ -548,21 +548,27 @@ class MergePlan:
 
 
 class MergeStepPlan:
-    """Planned table of the in-step merge (``lora_amd_merge_step``): per site the frozen 16-bit weight, the f32 factors and
+    """Planned table of the in-step merge (``lora_amd_merge_step``): per site the frozen weight, the f32 factors and
     where W_eff / W_eff^T go.  ``sites``: dicts with ``w`` [N, K], ``up`` [N, r], ``down`` [r, K], ``out`` (2-D view whose
-    row stride is ld_out), ``out_t`` (2-D view or None), ``row_heads`` / ``col_heads`` = (d, D) or None, ``key`` (dither)."""
+    row stride is ld_out), ``out_t`` (2-D view or None), ``row_heads`` / ``col_heads`` = (d, D) or None, ``key`` (dither).
+    The plan's dtype is the 16-bit dtype of ``out``; ``w`` has that dtype or is the f32 master (``src_f32``), the same for
+    every site of a plan."""
 
     def __init__(self, sites):
         if not sites:
             raise ValueError("MergeStepPlan: no sites")
         lib = require()
-        self.w_dtype, self.device = sites[0]["w"].dtype, sites[0]["w"].device
+        self.w_dtype, self.device = sites[0]["out"].dtype, sites[0]["w"].device
+        self.src_dtype = sites[0]["w"].dtype
+        if self.src_dtype not in (self.w_dtype, torch.float32):
+            raise TypeError("MergeStepPlan: mixed weight dtypes in one plan")
+        self.src_f32 = self.src_dtype == torch.float32 and self.w_dtype != torch.float32
         arr = (MstepSite * len(sites))()
         self.keep, self.bytes_algorithmic, self.rank_max = [], 0, 1
         for q, st in zip(arr, sites):
             w, up, down, out, out_t = st["w"], st["up"], st["down"], st["out"], st.get("out_t")
             _dev_check(w, up, down, out)
-            if w.dtype != self.w_dtype or out.dtype != self.w_dtype or (out_t is not None and out_t.dtype != self.w_dtype):
+            if w.dtype != self.src_dtype or out.dtype != self.w_dtype or (out_t is not None and out_t.dtype != self.w_dtype):
                 raise TypeError("MergeStepPlan: mixed weight dtypes in one plan")
             if up.dtype != torch.float32 or down.dtype != torch.float32:
                 raise TypeError("MergeStepPlan: f32 factors expected")
@@ -584,9 +590,11 @@ class MergeStepPlan:
             q.row_d, q.row_D = rh if rh else (0, 0)
             q.col_d, q.col_D = ch if ch else (0, 0)
             q.dither_key = int(st.get("key", 0)) & 0x7FFFFFFF
+            q.src_f32 = int(self.src_f32)
             self.rank_max = max(self.rank_max, r)
             self.keep.append((w, up, down, out, out_t))
-            self.bytes_algorithmic += (2 + (out_t is not None)) * N * K * w.element_size() + (N + K) * r * 4
+            self.bytes_algorithmic += N * K * (w.element_size() + (1 + (out_t is not None)) * out.element_size()) + \
+                (N + K) * r * 4
         total = C.c_int64(0)
         _check(lib.lora_amd_merge_step_plan(arr, len(sites), dtype_code(self.w_dtype), C.byref(total)),
                "lora_amd_merge_step_plan")

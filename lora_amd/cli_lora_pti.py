@@ -101,10 +101,11 @@ def text2img_dataloader(dataset, batch_size, tokenizer, vae, cached_latents: boo
 
 
 def loss_step(batch, unet, vae, text_encoder, scheduler, train_inpainting=False, t_mutliplier=1.0, mixed_precision=False,
-              mask_temperature=1.0, cached_latents: bool = False):
+              mask_temperature=1.0, cached_latents: bool = False, autocast_dtype: Optional[torch.dtype] = None):
     """ref :260-370 — noise, DDPM forward process with timesteps < 1000 * t_mutliplier, text encoder, UNet, (masked)
     per-sample MSE.  ``mixed_precision`` needs no autocast here: the frozen weights are already resident in the
-    compute dtype and the adapters read the f32 LoRA masters directly."""
+    compute dtype and the adapters read the f32 LoRA masters directly.  ``autocast_dtype`` (``frozen_dtype="fp32"``):
+    f32-resident models, text encoder and UNet under autocast as in ref :315-324."""
     if train_inpainting:
         raise NotImplementedError("train_inpainting needs the 9-channel inpainting UNet of a real checkpoint")
     dev, dt = unet.device, unet.dtype
@@ -118,8 +119,9 @@ def loss_step(batch, unet, vae, text_encoder, scheduler, train_inpainting=False,
                               device=dev).long()
     # formed in f32, rounded once (trainer.forward_backward says why: a 16-bit alpha_bar_t rounds to 1 at t = 0)
     noisy = scheduler.add_noise(latents.float(), noise.float(), timesteps).to(dt)
-    ehs = text_encoder(batch["input_ids"].to(dev))[0]
-    pred = unet(noisy, timesteps, ehs.to(dt)).sample
+    with torch.autocast(dev.type, dtype=autocast_dtype, enabled=autocast_dtype is not None):
+        ehs = text_encoder(batch["input_ids"].to(dev))[0]
+        pred = unet(noisy, timesteps, ehs if autocast_dtype is not None else ehs.to(dt)).sample
     ptype = getattr(scheduler.config, "prediction_type", "epsilon")
     if ptype == "epsilon":
         target = noise
@@ -224,7 +226,7 @@ def perform_tuning(unet, vae, text_encoder, dataloader, num_steps, scheduler, st
                    lr_lambda, save_steps: int, placeholder_token_ids, placeholder_tokens, save_path,
                    lora_unet_target_modules, lora_clip_target_modules, mask_temperature, out_name: str,
                    cached_latents: bool, rows: Optional[PlaceholderRows] = None, rows_lr: float = 0.0, world: int = 1,
-                   is_main: bool = True):
+                   is_main: bool = True, autocast_dtype: Optional[torch.dtype] = None):
     """ref :545-693 — timesteps < 800, clip(1.0) over the trainable set, AdamW, periodic ``step_{n}.safetensors``."""
     global_step = 0
     unet.train()
@@ -235,7 +237,8 @@ def perform_tuning(unet, vae, text_encoder, dataloader, num_steps, scheduler, st
             mult = lr_lambda(global_step + 1)
             state.set_lrs([b * mult for b in base_lrs])
             loss = loss_step(batch, unet, vae, text_encoder, scheduler, t_mutliplier=0.8, mixed_precision=True,
-                             mask_temperature=mask_temperature, cached_latents=cached_latents)
+                             mask_temperature=mask_temperature, cached_latents=cached_latents,
+                             autocast_dtype=autocast_dtype)
             (loss * state.loss_scale if state.loss_scale is not None else loss).backward()
             state.step(state.all_reduce())
             applied = True
@@ -291,8 +294,15 @@ def train(instance_data_dir: str, pretrained_model_name_or_path: str, output_dir
           wandb_log_prompt_cnt: int = 10, wandb_project_name: str = "new_pti_project",
           wandb_entity: str = "new_pti_entity", proxy_token: str = "person",
           enable_xformers_memory_efficient_attention: bool = False, out_name: str = "final_lora",
-          standin: str = "sd15", mixed_precision: str = "bf16"):
-    """ref :696-1036.  ``standin`` / ``mixed_precision`` are additions (stand-in model size; resident compute dtype)."""
+          standin: str = "sd15", mixed_precision: str = "bf16", frozen_dtype: str = "compute",
+          reference_add_noise: bool = False):
+    """ref :696-1036.  ``standin`` / ``mixed_precision`` are additions (stand-in model size; resident compute dtype).
+    ``frozen_dtype="fp32"``: the reference's policy in phase 2 — the models stay f32 and the text encoder and UNet run under
+    ``mixed_precision`` autocast (ref :315-324); the in-step merge reads the f32 master weights.  "compute": the models are
+    cast to the compute dtype.  ``reference_add_noise`` is accepted for symmetry with the DreamBooth CLI and changes nothing
+    here: in that mode the latents are f32, so add_noise already runs in the latents' own dtype, as the reference's does."""
+    if frozen_dtype not in ("compute", "fp32"):
+        raise ValueError(f"frozen_dtype must be 'compute' or 'fp32', got {frozen_dtype!r}")
     torch.manual_seed(seed)
     if log_wandb:
         raise NotImplementedError("log_wandb: wandb / the CLIP evaluation models are not available offline")
@@ -361,7 +371,9 @@ def train(instance_data_dir: str, pretrained_model_name_or_path: str, output_dir
     wdt = {"bf16": torch.bfloat16, "fp16": torch.float16}.get(mixed_precision, torch.float32)
     if dev.type == "cpu":
         wdt = torch.float32
-    unet.to(wdt)
+    master = frozen_dtype == "fp32" and wdt != torch.float32
+    if not master:
+        unet.to(wdt)
     if not use_extended_lora:
         unet_lora_params, _ = inject_trainable_lora(unet, r=lora_rank, target_replace_module=lora_unet_target_modules,
                                                     dropout_p=lora_dropout_p, scale=lora_scale)
@@ -398,7 +410,8 @@ def train(instance_data_dir: str, pretrained_model_name_or_path: str, output_dir
                    # diffusers' polynomial schedule reads lr_init = optimizer.defaults["lr"] = AdamW's 1e-3, not unet_lr
                    T.get_lr_lambda(lr_scheduler_lora, lr_warmup_steps_lora, max_train_steps_tuning, lr_init=1e-3), save_steps,
                    placeholder_token_ids, placeholder_tokens, output_dir, lora_unet_target_modules,
-                   lora_clip_target_modules, mask_temperature, out_name, cached_latents, rows, rows_lr, world, is_main)
+                   lora_clip_target_modules, mask_temperature, out_name, cached_latents, rows, rows_lr, world, is_main,
+                   autocast_dtype=wdt if master else None)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -24,9 +24,19 @@
 //     with the dither P(round up) = frac(delta / ulp) per element, unbiased over the elements of a row (what a GEMM sums),
 //     deterministic from step to step (the dither depends on (site, n, k) only), and exactly W where delta = 0.
 // Algorithmic bytes per site: N K e (W once) + N K e (W_eff) [+ N K e (W_eff^T)] + (N + K) r 4: 3 instead of 4 N K e.
+//
+// SRC32 (lora_amd_mstep_site.src_f32): W is the frozen f32 MASTER (the reference's precision policy: f32 models under 16-bit
+// autocast, train_lora_dreambooth.py:759-770) and the outputs stay 16-bit: the value is fmaf(alpha, p, W32) with p the same
+// rank-order chain (formed again in f64 for the rare element where W and alpha p cancel: see the kernel), rounded ONCE to
+// the output type — not bf16(bf16(W32) + delta), and the sub-ulp residue the dither stands
+// in for on a 16-bit source is then the master's own.  A column owner's chunk is 32 bytes per row: two 16-byte loads at
+// col * 4 and col * 4 + 16 (a row of the tile is still one contiguous run across the lanes of a slot; the pair of loads
+// covers whole 128-byte lines), twice the load registers (U x 8 VGPRs), everything after the add unchanged.  4 + 2 + 2 = 8
+// bytes per element instead of 6.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -39,6 +49,7 @@ constexpr int kMsMaxSitesLds = 256;   // site-table prefix kept in LDS for the t
 // tile geometries (rows n x columns k); the LDS image row is TC * 2 + 4 bytes (the column gather is then 2-way at worst)
 struct MsTile { int tr, tc; };
 constexpr MsTile kMsTiles[4] = {{128, 64}, {64, 128}, {128, 128}, {256, 64}};
+constexpr int kMsSrcF32Bit = 48;      // plan_value: the table's sources are f32 masters
 static int g_ms_tile = 2;     // lora_amd_merge_step_set_tuning; 128 x 128 measured best (profiles/r04_kbench_mstep.log)
 static int g_ms_dither = 2;   // 1: one hash per element; 2: two hashes per 16-byte chunk, 16-bit windows of the 64 bits
 
@@ -96,7 +107,7 @@ __device__ __forceinline__ uint32_t ms_round(float v, uint32_t u16) {
   }
 }
 
-template <class EW, int RT, int DITHER, int TR, int TC>
+template <class EW, bool SRC32, int RT, int DITHER, int TR, int TC>
 __global__ __launch_bounds__(kMsThreads) void merge_step_kernel(const lora_amd_mstep_site *__restrict__ sites, int n_sites,
                                                                 float alpha) {
   using SW = typename EW::storage;
@@ -150,6 +161,17 @@ __global__ __launch_bounds__(kMsThreads) void merge_step_kernel(const lora_amd_m
       for (int i = 0; i < 8; ++i) fc[j][i] = 0.f;
     }
   }
+  // SRC32: per rank the largest |down| of this thread's 8 columns (the bound of the cancellation test below)
+  float dmax[RT];
+  if constexpr (SRC32) {
+#pragma unroll
+    for (int j = 0; j < RT; ++j) {
+      float m = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) m = fmaxf(m, fabsf(fc[j][i]));
+      dmax[j] = m;
+    }
+  }
   // the tile's rows of `up` (f32 [N, r]) -> LDS [nrows][RT]
   for (int i = tid; i < nrows * RT; i += kMsThreads) {
     const int rl = i / RT, j = i - rl * RT;
@@ -157,21 +179,33 @@ __global__ __launch_bounds__(kMsThreads) void merge_step_kernel(const lora_amd_m
   }
   __syncthreads();
 
-  const SW *win = reinterpret_cast<const SW *>(s.w) + (int64_t)row0 * s.K + col;
+  constexpr int WV = SRC32 ? 2 : 1;  // 16-byte loads per row of a chunk
+  using SRC = std::conditional_t<SRC32, float, SW>;
+  const SRC *win = reinterpret_cast<const SRC *>(s.w) + (int64_t)row0 * s.K + col;
   SW *wout = reinterpret_cast<SW *>(s.out) + ms_map(col, s.col_d, s.col_D);
-  su32x4 w[U];
+  su32x4 w[U][WV];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int rl = slot + u * SLOTS;
     const bool ok = live && rl < nrows;
-    w[u] = __builtin_nontemporal_load(gl(reinterpret_cast<const su32x4 *>(win + (int64_t)(ok ? rl : 0) * s.K)));
+    const su32x4 *src = reinterpret_cast<const su32x4 *>(win + (int64_t)(ok ? rl : 0) * s.K);
+#pragma unroll
+    for (int v = 0; v < WV; ++v) w[u][v] = __builtin_nontemporal_load(gl(src + v));
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int rl = slot + u * SLOTS;
     if (!(live && rl < nrows)) continue;
-    union { su32x4 v; SW e[8]; } in;
-    in.v = w[u];
+    float wf[8];
+    if constexpr (SRC32) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) wf[i] = __builtin_bit_cast(float, (uint32_t)w[u][i >> 2][i & 3]);
+    } else {
+      union { su32x4 v; SW e[8]; } in;
+      in.v = w[u][0];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) wf[i] = EW::to_f(in.e[i]);
+    }
     const float *upr = s_up + rl * RT;
     float p[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -190,9 +224,32 @@ __global__ __launch_bounds__(kMsThreads) void merge_step_kernel(const lora_amd_m
       d[0] = ms_dither_pick<0>(h); d[1] = ms_dither_pick<1>(h); d[2] = ms_dither_pick<2>(h); d[3] = ms_dither_pick<3>(h);
       d[4] = ms_dither_pick<4>(h); d[5] = ms_dither_pick<5>(h); d[6] = ms_dither_pick<6>(h); d[7] = ms_dither_pick<7>(h);
     }
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = fmaf(alpha, p[i], wf[i]);
+    if constexpr (SRC32) {
+      // A master is not on the 16-bit grid, so W and alpha p can cancel: the f32 chain is off by up to (r + 2) 2^-24 of the
+      // terms' magnitude, which passes one ulp of the 16-bit RESULT once |v| < (r + 2) 2^-16 (bf16; 2^-13 for f16) of it.
+      // Such an element (about one in a thousand; none where up = 0) is formed again in f64 — exact products, the same rank
+      // order — so that the one rounding is that of the true sum.  `a` bounds sum |up_j| |down_j| from above.
+      constexpr float kCancel = EW::kCode == LORA_AMD_BF16 ? 0x1p-11f : 0x1p-8f;
+      float a = 0.f;
+#pragma unroll
+      for (int j = 0; j < RT; ++j) a = fmaf(fabsf(upr[j]), dmax[j], a);
+      a *= fabsf(alpha);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if (fabsf(v[i]) < kCancel * (fabsf(wf[i]) + a)) {
+          double pd = 0.0;
+#pragma unroll
+          for (int j = 0; j < RT; ++j) pd = fma((double)upr[j], (double)fc[j][i], pd);
+          v[i] = (float)fma((double)alpha, pd, (double)wf[i]);
+        }
+      }
+    }
     uint32_t b[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) b[i] = ms_round<EW, DITHER != 0>(fmaf(alpha, p[i], EW::to_f(in.e[i])), d[i]);
+    for (int i = 0; i < 8; ++i) b[i] = ms_round<EW, DITHER != 0>(v[i], d[i]);
     su32x4 o;
 #pragma unroll
     for (int i = 0; i < 4; ++i) o[i] = b[2 * i] | (b[2 * i + 1] << 16);
@@ -238,11 +295,16 @@ using namespace lora_amd;
 extern "C" int lora_amd_merge_step_plan(lora_amd_mstep_site *sites, int32_t n, int32_t w_dtype, int64_t *total_tiles) {
   LORA_AMD_CHECK(sites && n >= 1 && total_tiles, LORA_AMD_EINVAL, "merge_step_plan: bad argument");
   LORA_AMD_CHECK(w_dtype == LORA_AMD_F16 || w_dtype == LORA_AMD_BF16, LORA_AMD_EINVAL,
-                 "merge_step_plan: 16-bit weights only (f32 weights: lora_amd_merge_batched)");
+                 "merge_step_plan: 16-bit output weights only (f32 outputs: lora_amd_merge_batched; an f32 SOURCE is src_f32)");
   auto map_ok = [](int d, int D, int cols) { return d == 0 || (d > 0 && d % 8 == 0 && D % 8 == 0 && D >= d && cols % d == 0); };
   int64_t acc = 0;
   for (int i = 0; i < n; ++i) {
     lora_amd_mstep_site &s = sites[i];
+    LORA_AMD_CHECK(s.src_f32 == 0 || s.src_f32 == 1, LORA_AMD_EINVAL, "merge_step_plan: site %d: src_f32 = %d (0 or 1)", i,
+                   s.src_f32);
+    LORA_AMD_CHECK(s.src_f32 == sites[0].src_f32, LORA_AMD_EINVAL,
+                   "merge_step_plan: site %d: src_f32 = %d but site 0 has %d (one source type per table)", i, s.src_f32,
+                   sites[0].src_f32);
     LORA_AMD_CHECK(s.N > 0 && s.K > 0 && s.K % 8 == 0 && s.N % 8 == 0, LORA_AMD_EINVAL,
                    "merge_step_plan: site %d: N = %d, K = %d must be multiples of 8", i, s.N, s.K);
     LORA_AMD_CHECK(s.r >= 1 && s.r <= 16, LORA_AMD_ERANK, "merge_step_plan: site %d: rank %d outside [1,16]", i, s.r);
@@ -260,17 +322,19 @@ extern "C" int lora_amd_merge_step_plan(lora_amd_mstep_site *sites, int32_t n, i
     acc += (int64_t)s.tiles_k * ((s.N + tg.tr - 1) / tg.tr);
   }
   LORA_AMD_CHECK(acc < (1ll << 31), LORA_AMD_EINVAL, "merge_step_plan: too many tiles");
-  *total_tiles = acc | ((int64_t)g_ms_tile << 40);  // opaque to the caller: the tile count and the geometry it was planned for
+  // opaque to the caller: the tile count, the geometry it was planned for and the source type of the table
+  *total_tiles = acc | ((int64_t)g_ms_tile << 40) | ((int64_t)sites[0].src_f32 << kMsSrcF32Bit);
   return LORA_AMD_OK;
 }
 
 extern "C" int lora_amd_merge_step(const lora_amd_mstep_site *sites_dev, int32_t n, int64_t plan_value, int32_t rank_max,
                                    int32_t w_dtype, float alpha, int32_t rounding, void *stream) {
-  const int ms_tile = (int)(plan_value >> 40);
+  const int ms_tile = (int)((plan_value >> 40) & 0xff);
+  const bool src32 = (plan_value >> kMsSrcF32Bit) & 1;
   const int64_t total_tiles = plan_value & ((1ll << 40) - 1);
-  LORA_AMD_CHECK(ms_tile >= 0 && ms_tile < 4, LORA_AMD_EINVAL, "merge_step: not a value of lora_amd_merge_step_plan");
+  LORA_AMD_CHECK(ms_tile >= 0 && ms_tile < 4 && (plan_value >> (kMsSrcF32Bit + 1)) == 0, LORA_AMD_EINVAL, "merge_step: not a value of lora_amd_merge_step_plan");
   LORA_AMD_CHECK(sites_dev && n >= 1 && total_tiles >= 1 && total_tiles < (1ll << 31), LORA_AMD_EINVAL, "merge_step: bad argument");
-  LORA_AMD_CHECK(w_dtype == LORA_AMD_F16 || w_dtype == LORA_AMD_BF16, LORA_AMD_EINVAL, "merge_step: 16-bit weights only");
+  LORA_AMD_CHECK(w_dtype == LORA_AMD_F16 || w_dtype == LORA_AMD_BF16, LORA_AMD_EINVAL, "merge_step: 16-bit output weights only");
   LORA_AMD_CHECK(rank_max >= 1 && rank_max <= 16, LORA_AMD_ERANK, "merge_step: rank %d outside [1,16]", rank_max);
   LORA_AMD_CHECK(rounding == LORA_AMD_ROUND_ONCE || rounding == LORA_AMD_ROUND_DITHER, LORA_AMD_EINVAL,
                  "merge_step: rounding must be ROUND_ONCE or ROUND_DITHER, got %d", rounding);
@@ -279,12 +343,15 @@ extern "C" int lora_amd_merge_step(const lora_amd_mstep_site *sites_dev, int32_t
   const bool dith = rounding == LORA_AMD_ROUND_DITHER;
   const int dmode = dith ? g_ms_dither : 0;
   by_dtype<f16_t, bf16_t>(w_dtype, [&](auto e) {
-    by_int<4, 8, 16>(RT, [&](auto rt) {
-      by_int<0, 1, 2, 3>(ms_tile, [&](auto ti) {
-        by_int<0, 1, 2>(dmode, [&](auto dv) {
-          constexpr MsTile tg = kMsTiles[decltype(ti)::value];
-          hipLaunchKernelGGL((merge_step_kernel<decltype(e), decltype(rt)::value, decltype(dv)::value, tg.tr, tg.tc>),
-                             dim3((unsigned)total_tiles), dim3(kMsThreads), 0, st, sites_dev, n, alpha);
+    by_int<0, 1>((int)src32, [&](auto sv) {
+      by_int<4, 8, 16>(RT, [&](auto rt) {
+        by_int<0, 1, 2, 3>(ms_tile, [&](auto ti) {
+          by_int<0, 1, 2>(dmode, [&](auto dv) {
+            constexpr MsTile tg = kMsTiles[decltype(ti)::value];
+            hipLaunchKernelGGL((merge_step_kernel<decltype(e), decltype(sv)::value != 0, decltype(rt)::value,
+                                                  decltype(dv)::value, tg.tr, tg.tc>),
+                               dim3((unsigned)total_tiles), dim3(kMsThreads), 0, st, sites_dev, n, alpha);
+          });
         });
       });
     });

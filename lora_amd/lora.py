@@ -197,28 +197,41 @@ class LoraInjectedLinear(_Adapter):
         w, b = self.linear.weight, self.linear.bias
         dt = _autocast_dtype(x, w)
         xc = x if x.dtype == dt else x.to(dt)
-        wc, bc = self._shadow(w, dt, "w"), self._shadow(b, dt, "b")
+        bc = self._shadow(b, dt, "b")
         ps = self._per_sample()
         if ps is not None:  # one setting per sample (forward only): the rowscale kernels; never the merged / head routes
+            wc = self._shadow(w, dt, "w")
             rows, diag, alpha = ps
             with torch.autocast(device_type=x.device.type, enabled=False):
                 return ops.lora_linear_per_sample(xc, wc, bc, self.lora_down.weight, self.lora_up.weight,
                                                   self._selector_matrix() if diag is None else None,
                                                   1.0 if alpha is not None else self.scale, self._dropout_p(), rows)
+        mw = self.__dict__.get("_merged")
+        if mw is not None:
+            # f32 master under 16-bit autocast: the merged route reads W itself; no 16-bit shadow of it is built
+            wsrc = w if ops.master_site(w, dt) else self._shadow(w, dt, "w")
+            y = self._forward_merged(mw, xc, wsrc, b, bc, dt, in_heads, out_heads)
+            if y is not None:
+                return y
+        wc = self._shadow(w, dt, "w")
         with torch.autocast(device_type=x.device.type, enabled=False):
-            mw = self.__dict__.get("_merged")
-            if mw is not None and ops.merged_ok(xc, wc, self.lora_down.weight, self.lora_up.weight,
-                                                self._selector_matrix(), self._dropout_p(), in_heads, out_heads, b):
-                # the step's merged weight W + scale up down (trainer.enable_merged_weights): frozen GEMM forward and
-                # input gradient, one launch for both factor gradients
-                need_dx = xc.requires_grad and torch.is_grad_enabled()
-                w_eff, b_eff, w_eff_t = mw.lookup(self, wc, bc, dt, in_heads, out_heads, need_dx)
-                return ops.LoraLinearMergedFunction.apply(xc, w_eff, b_eff, self.lora_down.weight, self.lora_up.weight,
-                                                          float(self.scale), self.__dict__.get("_grad_sink"), in_heads,
-                                                          out_heads, w_eff_t)
             return ops.lora_linear(xc, wc, bc, self.lora_down.weight, self.lora_up.weight,
                                    self._selector_matrix(), self.scale, self._dropout_p(),
                                    self.__dict__.get("_grad_sink"), in_heads, out_heads)
+
+    def _forward_merged(self, mw, xc, wsrc, b, bc, dt, in_heads, out_heads) -> Optional[torch.Tensor]:
+        """The step's merged weight W + scale up down (trainer.enable_merged_weights): frozen GEMM forward and input
+        gradient, one launch for both factor gradients.  ``wsrc``: the frozen weight in the compute dtype, or the f32 master
+        (``ops.master_site``).  None when the call is not eligible (``ops.merged_ok``)."""
+        with torch.autocast(device_type=xc.device.type, enabled=False):
+            if not ops.merged_ok(xc, wsrc, self.lora_down.weight, self.lora_up.weight, self._selector_matrix(),
+                                 self._dropout_p(), in_heads, out_heads, b):
+                return None
+            need_dx = xc.requires_grad and torch.is_grad_enabled()
+            w_eff, b_eff, w_eff_t = mw.lookup(self, wsrc, bc, dt, in_heads, out_heads, need_dx)
+            return ops.LoraLinearMergedFunction.apply(xc, w_eff, b_eff, self.lora_down.weight, self.lora_up.weight,
+                                                      float(self.scale), self.__dict__.get("_grad_sink"), in_heads,
+                                                      out_heads, w_eff_t)
 
     def forward_heads(self, input, in_heads=None, out_heads=None):
         """``forward`` for head-padded activations (not in the reference): ``in_heads`` / ``out_heads`` = (heads, d, D)
@@ -255,7 +268,8 @@ def lora_linear_group(adapters, x: torch.Tensor, out_heads=None):
         dt = _autocast_dtype(x, adapters[0].linear.weight)
         xc = x if x.dtype == dt else x.to(dt)
         mw = adapters[0].__dict__["_merged"]
-        wcs = [a._shadow(a.linear.weight, dt, "w") for a in adapters]
+        wcs = [a.linear.weight if ops.master_site(a.linear.weight, dt) else a._shadow(a.linear.weight, dt, "w")
+               for a in adapters]   # f32 masters go to the merge as they are
         bcs = [a._shadow(a.linear.bias, dt, "b") for a in adapters]
         for a, wc in zip(adapters, wcs):
             if a.__dict__["_merged"] is not mw or not ops.merged_ok(xc, wc, a.lora_down.weight, a.lora_up.weight,

@@ -540,12 +540,16 @@ FM_BLOCK_MAP = True
 # fused down-conv / fold / up-projection / dropout / add kernel) and its G pass with the Gt fold inside the launch; False =
 # the launch sequence of rounds 3-5 (pack + down [+ sum_parts] + rank_update; bwd_g + sum_parts): the A/B and the parity twin
 CONV3_FUSED = True
+# f32-resident frozen weights under 16-bit autocast (the reference's precision policy): the in-step merge reads the f32 MASTER
+# (csrc/merge_step.hip, src_f32: W_eff = round16(W32 + scale up down), one rounding, no bf16 copy of W kept) instead of a cached
+# 16-bit shadow of it (round16(round16(W32) + scale up down)); False = the shadow-then-merge route: the A/B and the parity twin
+MASTER_MERGE = True
 
 
 def apply_ab_overrides(spec: str, namespace: dict) -> dict:
     """``LORA_AMD_AB="NAME=0,OTHER=1"``: the ONE measurement switch for same-box A/B runs — flips the module constants
     above (and only those) without a code edit; every A/B log under profiles/ names the spec it ran with."""
-    allowed = ("TRANSPOSED_DX", "DEFER_MASKED_FACTORS", "CONCAT_GROUPS", "RANK16_MFMA", "FM_TWO_CLASSES", "CONCURRENT_FACTOR_LAUNCHES", "FM_LONGEST_FIRST", "FM_LONGEST_FIRST_CLASS1", "FM_BLOCK_MAP", "CONV3_FUSED", "WS_HEADS", "WS_DROPOUT",
+    allowed = ("TRANSPOSED_DX", "DEFER_MASKED_FACTORS", "CONCAT_GROUPS", "RANK16_MFMA", "FM_TWO_CLASSES", "CONCURRENT_FACTOR_LAUNCHES", "FM_LONGEST_FIRST", "FM_LONGEST_FIRST_CLASS1", "FM_BLOCK_MAP", "CONV3_FUSED", "MASTER_MERGE", "WS_HEADS", "WS_DROPOUT",
                "WS_DROPOUT_WIDE",
                "WS_DROPOUT_WIDE_BWD")
     done = {}
@@ -569,6 +573,11 @@ if not RANK16_MFMA and _C.available():
 MERGE_ROUNDING = _C.ROUND_ONCE if os.environ.get("LORA_AMD_MERGE_ROUNDING", "dither") == "once" else _C.ROUND_DITHER
 
 
+def master_site(w: torch.Tensor, dt: torch.dtype) -> bool:
+    """The frozen weight is an f32 master and the compute dtype 16-bit: the merged route reads ``w`` itself (MASTER_MERGE)."""
+    return MASTER_MERGE and w.dtype == torch.float32 and dt in (torch.bfloat16, torch.float16) and not w.requires_grad
+
+
 def _gemm_range():
     """Profiler range around the library GEMMs of the merged-weight path (only while bench.py's adapter-path profile is
     recording: PATH_LOG is a list), so that their device time can be attributed to the adapter path."""
@@ -588,6 +597,10 @@ class MergedWeights:
     ``linear_bwd_factors_self_ragged`` launch after the backward (``flush_factors``; without a trainer state: one
     ``linear_bwd_factors_self`` launch per site, in its backward).
     Eligible: device tensors, dropout not in effect, no selector, frozen weight, f32 factors, rank <= 16.
+
+    f32-resident frozen weights under 16-bit autocast (``master_site``): ``lookup`` / ``lookup_group`` are handed the f32
+    Parameter itself; the scratch weights take the compute dtype and the in-step merge reads the master (``src_f32``) — no
+    16-bit shadow of W exists for such a site.  ``n_master_sites`` counts the adapters that run this way.
 
     Head-padded activations (``forward_heads``): the scratch weight is laid out for them — rows of a head-padded OUTPUT
     are written head by head (pad rows stay zero), columns of a head-padded INPUT through the merge kernel's
@@ -619,7 +632,7 @@ class MergedWeights:
         wants for the input gradient G W_eff — 12.4 vs 14.4 us at 16384 x 320 x 320, 45.6 vs 80.7 us at 1024 x 10240 -> 1280,
         profiles/r03_kbench_gemmlayout.log); None when no input gradient is needed."""
         e = self._entry(module, w, b, dt, in_heads, out_heads)
-        # f32 weights go through the collapse kernel, whose transposed sites need 32 | N (its column tiles)
+        # f32 weights with f32 activations go through the collapse kernel, whose transposed sites need 32 | N (its column tiles)
         if need_dx and TRANSPOSED_DX and e["w_eff_t"] is None and (e["step"] or (in_heads is None and w.shape[0] % 32 == 0)):
             self._add_transposed(e)
         return e["w_eff"], e["b_eff"], e["w_eff_t"]
@@ -643,7 +656,7 @@ class MergedWeights:
                 self.groups.pop(e["group"], None)
             e = None
         if e is None:
-            e = self._create(module, w, b, in_heads, out_heads, out)
+            e = self._create(module, w, b, dt, in_heads, out_heads, out)
             self.entries[key] = e
         return e
 
@@ -668,13 +681,15 @@ class MergedWeights:
                 self.groups.pop(gkey, None)
                 g = None
         if g is None:
-            if any((id(m), None, out_heads, dt) in self.entries for m in modules) or ws[0].dtype == torch.float32:
+            master = master_site(ws[0], dt)
+            if any((id(m), None, out_heads, dt) in self.entries for m in modules) or \
+                    (ws[0].dtype == torch.float32 and not master):
                 return None
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("MergedWeights: a new adapter group appeared during hipGraph capture")
             K = ws[0].shape[1]
             n_outs = [(out_heads[0] * out_heads[2] if out_heads else w.shape[0]) for w in ws]
-            cat = torch.zeros((sum(n_outs), K), dtype=ws[0].dtype, device=ws[0].device)
+            cat = torch.zeros((sum(n_outs), K), dtype=dt if master else ws[0].dtype, device=ws[0].device)
             g = dict(cat=cat, cat_t=None, splits=n_outs, bias=None)
             pos = 0
             for m, w, b, n_o in zip(modules, ws, bs, n_outs):
@@ -698,22 +713,29 @@ class MergedWeights:
         g["entries"] = es
         return g
 
-    def _create(self, module, w, b, in_heads, out_heads, out=None):
+    @property
+    def n_master_sites(self) -> int:
+        """Adapters whose scratch weights are merged from the f32 master (not from a 16-bit shadow of it)."""
+        return len({id(e["module"]) for e in self.entries.values() if e["src_f32"]})
+
+    def _create(self, module, w, b, dt, in_heads, out_heads, out=None):
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("MergedWeights: a new adapter / layout appeared during hipGraph capture; run the step "
                                "eagerly once first (GraphedForwardBackward's warm-up does)")
         N, K = w.shape
         n_out = out_heads[0] * out_heads[2] if out_heads else N
         k_out = in_heads[0] * in_heads[2] if in_heads else K
-        w_eff = out if out is not None else torch.zeros((n_out, k_out), dtype=w.dtype, device=w.device)  # pads stay zero
+        src_f32 = master_site(w, dt)  # the frozen f32 master under 16-bit autocast: scratch weights in the compute dtype
+        cdt = dt if src_f32 else w.dtype
+        w_eff = out if out is not None else torch.zeros((n_out, k_out), dtype=cdt, device=w.device)  # pads stay zero
         b_eff = None
         if b is not None:
             b_eff = pack_heads(b.detach(), out_heads).contiguous() if out_heads else b.detach()
         up, down = module.lora_up.weight, module.lora_down.weight
-        step = w.dtype in (torch.bfloat16, torch.float16)  # the in-step merge kernel (csrc/merge_step.hip)
+        step = cdt in (torch.bfloat16, torch.float16)  # the in-step merge kernel (csrc/merge_step.hip)
         e = dict(module=module, w=w.detach(), w_eff=w_eff, b_eff=b_eff, w_eff_t=None, w_t=None, scale=float(module.scale),
                  ptrs=(up.data_ptr(), down.data_ptr(), w.data_ptr()), in_heads=in_heads, out_heads=out_heads, step=step,
-                 key=self._dither_key(module), group=None)
+                 key=self._dither_key(module), group=None, src_f32=src_f32)
         if not step:  # f32 weights: the collapse kernel's sites (round 3's form; head sub-ranges, separate transposed site)
             heads_in = (in_heads[1], in_heads[2]) if in_heads else None
             sites = []
@@ -757,7 +779,7 @@ class MergedWeights:
             raise RuntimeError("MergedWeights: a site's transposed scratch weight must exist before hipGraph capture")
         w, module, out_heads = e["w"], e["module"], e["out_heads"]
         e["w_eff_t"] = out_t if out_t is not None else torch.zeros((e["w_eff"].shape[1], e["w_eff"].shape[0]),
-                                                                   dtype=w.dtype, device=w.device)  # pads stay zero
+                                                                   dtype=e["w_eff"].dtype, device=w.device)  # pads stay zero
         if not e["step"]:
             e["w_t"] = w.t().contiguous()  # frozen: built once
             heads = (out_heads[1], out_heads[2]) if out_heads else None
@@ -767,7 +789,7 @@ class MergedWeights:
         self._plans = None
 
     def refresh(self) -> None:
-        """ONE merge launch per (weight dtype, scale) group — one in practice — over every registered site."""
+        """ONE merge launch per (weight dtype, source type, scale) group — one in practice — over every registered site."""
         if self._state is not None:
             self._fresh_at = self._state.step_count
         if not self.entries:
@@ -779,11 +801,11 @@ class MergedWeights:
             step_groups, old_groups = {}, {}
             for e in self.entries.values():
                 if e["step"]:
-                    step_groups.setdefault((e["w"].dtype, e["scale"]), []).append(self._msite(e))
+                    step_groups.setdefault((e["w_eff"].dtype, e["src_f32"], e["scale"]), []).append(self._msite(e))
                 else:
                     for st in e["sites"]:
                         old_groups.setdefault((st[0].dtype, e["scale"]), []).append(st)
-            self._plans = [(_C.MergeStepPlan(sites), alpha, MERGE_ROUNDING) for (_, alpha), sites in step_groups.items()]
+            self._plans = [(_C.MergeStepPlan(sites), alpha, MERGE_ROUNDING) for (_, _, alpha), sites in step_groups.items()]
             self._plans += [(_C.MergePlan(sites), alpha, _C.ROUND_ONCE) for (_, alpha), sites in old_groups.items()]
         for plan, alpha, rounding in self._plans:
             plan.launch(alpha, rounding)
@@ -1088,18 +1110,19 @@ def merged_ok(x: torch.Tensor, weight: torch.Tensor, down: torch.Tensor, up: tor
               in_heads, out_heads, bias=None) -> bool:
     """Can this call take the merged-weight path?  (device, no dropout / selector, frozen weight AND bias, f32 factors, a
     shape and alignment the merge and the one-launch factor-gradient kernels cover, 16-bit or f32 activations matching
-    the weight).  Mirrors the planners' preconditions so that a site they would refuse takes the per-site kernels
-    instead of raising inside the forward."""
+    the weight — or 16-bit activations on an f32 master weight, ``master_site``).  Mirrors the planners' preconditions so
+    that a site they would refuse takes the per-site kernels instead of raising inside the forward."""
     if not x.is_cuda or dropout_p > 0.0 or sel is not None or weight.requires_grad:
         return False
     if bias is not None and bias.requires_grad:  # the merged path caches the bias and returns no gradient for it
         return False
     if (weight.data_ptr() | down.data_ptr() | up.data_ptr()) % 16 or not weight.is_contiguous():
         return False
-    if weight.dtype == torch.float32 and (in_heads is not None or out_heads is not None) and \
+    master = x.dtype != weight.dtype and master_site(weight, x.dtype)  # the in-step merge reads the f32 master
+    if weight.dtype == torch.float32 and not master and (in_heads is not None or out_heads is not None) and \
             (weight.shape[0] % 32 or weight.shape[1] % 32):
         return False  # head layouts of f32 weights run on the collapse kernel's column-owner tiles
-    if down.dtype != torch.float32 or up.dtype != torch.float32 or x.dtype != weight.dtype:
+    if down.dtype != torch.float32 or up.dtype != torch.float32 or (x.dtype != weight.dtype and not master):
         return False
     N, K = weight.shape
     r = down.shape[0]

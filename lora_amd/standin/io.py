@@ -44,7 +44,7 @@ class StandinVAE(nn.Module):
 
     @torch.no_grad()
     def encode(self, pixels: torch.Tensor):
-        x = pixels.float()
+        x = pixels.to(self.mix.dtype)  # f32 unless the VAE itself was cast (the reference casts it to the compute dtype)
         pooled = torch.nn.functional.avg_pool2d(x, 8)
         mean = torch.einsum("oc,bchw->bohw", self.mix, pooled) + torch.nn.functional.conv2d(x, self.tex, stride=8)
         return types.SimpleNamespace(latent_dist=self._Dist(mean.to(pixels.dtype)))

@@ -263,6 +263,9 @@ class StepConfig:
     t_multiplier: float = 1.0  # cli_lora_pti.py:300 (0.8 in perform_tuning)
     prediction_type: str = "epsilon"
     autocast_dtype: Optional[torch.dtype] = None  # reference-style mixed precision; None = model dtype
+    # the noisy latents as diffusers forms them: scheduler.add_noise in the latents' OWN dtype (ref
+    # train_lora_dreambooth.py:837); False = formed in f32 and rounded once (see forward_backward)
+    reference_add_noise: bool = False
 
 
 def dreambooth_loss(model_pred: torch.Tensor, target: torch.Tensor, cfg: StepConfig) -> torch.Tensor:
@@ -324,7 +327,8 @@ def forward_backward(unet, scheduler, latents: torch.Tensor, cond, cfg: StepConf
     # first — bf16(0.99915) = 1, so a t = 0 sample gets NO noise and small t a badly quantised one — and then rounds three more
     # times.  Measured on a batch holding t = 0 (profiles/r06_bracket_t0.log): the step's LoRA gradients sit 6.4 x as far from
     # the f32 step as the bf16-autocast reference's; formed in f32: 1.29 x.  16 K elements per sample: free.
-    if latents.dtype in (torch.bfloat16, torch.float16):
+    # StepConfig.reference_add_noise asks for the reference's arithmetic as it is.
+    if latents.dtype in (torch.bfloat16, torch.float16) and not cfg.reference_add_noise:
         noisy = scheduler.add_noise(latents.float(), noise.float(), timesteps).to(latents.dtype)
     else:
         noisy = scheduler.add_noise(latents, noise, timesteps)

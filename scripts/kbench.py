@@ -80,13 +80,16 @@ def bench_merge(args):
     return out
 
 
-def mstep_tensors(r=4):
+def mstep_tensors(r=4, src=torch.bfloat16):
+    """``src``: dtype of the frozen weights the merge reads (bf16: the resident 16-bit weight; f32: the master); the
+    outputs are bf16 either way."""
     shapes = sd15_lora_site_shapes()
     tens = []
     for N, K in shapes:
-        w = (torch.randn(N, K, device=DEV) * 0.03).to(torch.bfloat16)
-        tens.append((w, torch.randn(N, r, device=DEV) * 0.05, torch.randn(r, K, device=DEV) * 0.25, torch.empty_like(w),
-                     torch.empty(K, N, dtype=w.dtype, device=DEV) if K != 768 else None))
+        w = (torch.randn(N, K, device=DEV) * 0.03).to(src)
+        tens.append((w, torch.randn(N, r, device=DEV) * 0.05, torch.randn(r, K, device=DEV) * 0.25,
+                     torch.empty(N, K, dtype=torch.bfloat16, device=DEV),
+                     torch.empty(K, N, dtype=torch.bfloat16, device=DEV) if K != 768 else None))
     return tens
 
 
@@ -110,6 +113,22 @@ def bench_mstep(args):
                                   sites=plan.n_sites, tiles=plan.total_tiles, MB=plan.bytes_algorithmic / 1e6,
                                   us=med * 1e6, best_us=best * 1e6, GBs=gbs, frac8=gbs / 8000)), flush=True)
     _C.merge_step_set_tuning(2, 2)
+    # the same table read from f32 MASTERS (src_f32: 4 + 2 + 2 bytes per element instead of 2 + 2 + 2) next to the 16-bit
+    # sources, default geometry and rounding, both legs in this one call (three alternating rounds, the median of each)
+    plans = {"bf16": mstep_plan(tens), "f32": mstep_plan(mstep_tensors(args.rank, torch.float32))}
+    runs = {k: [] for k in plans}
+    for _ in range(3):
+        for k, plan in plans.items():
+            runs[k].append(timeit(lambda: plan.launch(0.7, _C.ROUND_DITHER), iters=args.iters)[0])
+    rec = {"kernel": "merge_step_source", "tile": "128x128", "sites": plans["bf16"].n_sites}
+    for k, plan in plans.items():
+        t = sorted(runs[k])[1]
+        rec[k] = {"MB": plan.bytes_algorithmic / 1e6, "us": t * 1e6, "us_rounds": [x * 1e6 for x in runs[k]],
+                  "frac8": plan.bytes_algorithmic / t / 8e12}
+    rec["time_ratio_f32_over_bf16"] = rec["f32"]["us"] / rec["bf16"]["us"]
+    rec["byte_ratio"] = rec["f32"]["MB"] / rec["bf16"]["MB"]
+    rec["target_ratio_max"] = 8 / 6 * 1.10
+    print(json.dumps(rec), flush=True)
 
 
 def bench_r16(args):

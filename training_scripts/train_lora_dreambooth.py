@@ -101,6 +101,12 @@ def parse_args(input_args=None):
     a("--channels_last", type=int, default=0, help="Run the UNet in NHWC (the layout MIOpen's convolutions use on "
       "MI355X; +5 %% steps/s on the SD1.5 stand-in).  Linear sites run as they are; Conv2d adapter sites take the "
       "channels-last MFMA kernels of csrc/conv_nhwc.hip (3x3) or the Linear kernels on the pixel rows (1x1).")
+    a("--frozen_dtype", type=str, default="compute", choices=["compute", "fp32"], help="Dtype the frozen UNet (and a "
+      "trained text encoder) is resident in.  compute: the --mixed_precision dtype.  fp32: the reference's policy — f32 "
+      "models under --mixed_precision autocast; the in-step merge then reads the f32 master weights.  No effect with "
+      "--mixed_precision no or on the CPU.")
+    a("--reference_add_noise", action="store_true", help="Form the noisy latents in the latents' own dtype, as "
+      "diffusers' add_noise does, instead of in f32 rounded once.")
     args = p.parse_args(input_args) if input_args is not None else p.parse_args()
 
     env_local_rank = int(os.environ.get("LOCAL_RANK", -1))
@@ -162,15 +168,20 @@ def main(args):
     if device.type == "cpu":
         weight_dtype = torch.float32
 
+    # --frozen_dtype fp32: what the reference does (ref :759-770) — the trained models stay f32 and run under autocast;
+    # only the VAE and an untrained text encoder are cast
+    master = args.frozen_dtype == "fp32" and weight_dtype != torch.float32
+    frozen_dtype = torch.float32 if master else weight_dtype
+
     unet.requires_grad_(False)
-    unet.to(device=device, dtype=weight_dtype)
+    unet.to(device=device, dtype=frozen_dtype)
     if args.channels_last and device.type == "cuda":
         unet.to(memory_format=torch.channels_last)
     unet_lora_params, _ = inject_trainable_lora(unet, r=args.lora_rank, loras=args.resume_unet)  # ref :596-598
     vae.requires_grad_(False)
     text_encoder.requires_grad_(False)
-    vae.to(device)
-    text_encoder.to(device=device, dtype=weight_dtype)
+    vae.to(device=device, dtype=weight_dtype) if master else vae.to(device)
+    text_encoder.to(device=device, dtype=frozen_dtype if args.train_text_encoder else weight_dtype)
     if args.train_text_encoder:  # ref :608-621
         inject_trainable_lora(text_encoder, target_replace_module=["CLIPAttention"], r=args.lora_rank,
                               loras=args.resume_text_encoder)
@@ -219,7 +230,8 @@ def main(args):
                                 args.max_train_steps * args.gradient_accumulation_steps, lr_init=args.learning_rate)
     cfg = T.StepConfig(with_prior_preservation=args.with_prior_preservation, prior_loss_weight=args.prior_loss_weight,
                        num_train_timesteps=noise_scheduler.config.num_train_timesteps,
-                       prediction_type=getattr(noise_scheduler.config, "prediction_type", "epsilon"))
+                       prediction_type=getattr(noise_scheduler.config, "prediction_type", "epsilon"),
+                       autocast_dtype=weight_dtype if master else None, reference_add_noise=args.reference_add_noise)
     if is_main:
         print("***** Running training *****")
         print(f"  Num examples = {len(dataset)}")
@@ -235,7 +247,8 @@ def main(args):
 
     def encode(batch):
         with torch.no_grad():  # frozen VAE (ref :818-821 leaves autograd on; nothing upstream needs a gradient)
-            lat = vae.encode(batch["pixel_values"].to(device)).latent_dist.sample() * 0.18215
+            lat = vae.encode(batch["pixel_values"].to(device, dtype=weight_dtype if master else None)
+                             ).latent_dist.sample() * 0.18215
         return lat.to(weight_dtype), batch["input_ids"].to(device)
 
     te_arg = text_encoder  # the reference always runs the text encoder inside the step (ref :840)
@@ -286,6 +299,8 @@ def main(args):
         dist.barrier()
     if is_main:
         print("\n\nLora TRAINING DONE!\n\n")
+        if merged is not None and master:
+            print(f"merged weights: {len(merged.entries)} sites, {merged.n_master_sites} adapters on f32 masters")
         if args.output_format in ("pt", "both"):
             save_lora_weight(unet, args.output_dir + "/lora_weight.pt")
             if args.train_text_encoder:
