@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import os
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -72,15 +72,17 @@ class dropout_pool:
 
 # nn.Dropout on the branch runs inside the weight-stationary kernels; under dropout they also take the shapes whose p = 0
 # choice is another kernel, forward and backward (the alternative there is the rank-16 VALU kernel on top of the library
-# GEMM; configs[3], same box: 21.26 -> 22.20 -> 22.44 steps/s, round 2).  Module constants (tests flip them), no switches.
+# GEMM; configs[3], same box: 21.26 -> 22.20 -> 22.44 steps/s, round 2).  Module constants, no switches
+# (tests/test_round2_cpu.py checks the defaults and flips WS_DROPOUT through apply_ab_overrides).
 WS_DROPOUT = WS_DROPOUT_WIDE = WS_DROPOUT_WIDE_BWD = True
 # the dropout sites around the attention core in head-padded rows on the weight-stationary kernel (round 6; False = the
-# unpack -> kernel -> pack copies of rounds 3-5: the A/B and the parity twin)
+# unpack -> kernel -> pack copies of rounds 3-5; tests/test_gpu_ws_heads.py runs both)
 WS_HEADS = True
 
 
 # When a list: every adapter forward / backward appends (phase, kernel path, M, K, N, r) — what bench.py turns into
-# ``config.kernel_choices`` and the adapter-path byte count.  None (default): nothing is recorded.
+# ``config.kernel_choices`` and the adapter-path byte count.  None (default): nothing is recorded
+# (tests set it, e.g. tests/test_gpu_ws_heads.py, to assert the route a site took).
 PATH_LOG: Optional[list] = None
 
 
@@ -109,45 +111,13 @@ class GradSink:
             self.owner._reduce_table = None  # table must be rebuilt with the new buffers
         return w
 
-    def workspace(self, key, plan, device):
-        """Linear site, key = (M, K, N, r): (gt_part, up_part, down_part)."""
+    def lookup(self, key, alloc, rows):
+        """The persistent partial slabs of shape ``key``.  On first use ``alloc()`` makes them and
+        ``rows(w, up_grad, down_grad, beta)`` the reduce_batched rows that fold them into this sink's gradients."""
         w = self.ws.get(key)
         if w is None:
-            w = tuple(torch.empty(max(int(n), 1), dtype=torch.float32, device=device)
-                      for n in (plan.gt_part_floats, plan.up_part_floats, plan.down_part_floats))
-            _, K, N, r = key
-            self._new(key, w, [(w[1], self.up_grad, plan.nparts_up, plan.rank_tile, N, r, _C.FACTOR_KR, 1.0, 1.0),
-                               (w[2], self.down_grad, plan.nparts_down, plan.rank_tile, K, r, _C.FACTOR_RK, 1.0, 1.0)])
-        return w
-
-    def self_workspace(self, key, plan, device):
-        """Merged-weight Linear site, key = ("self", M, K, N, r, row blocks): (up_part, down_part) of
-        ``linear_bwd_factors_self`` / the deferred one-launch pass."""
-        w = self.ws.get(key)
-        if w is None:
-            w = tuple(torch.empty(max(int(n), 1), dtype=torch.float32, device=device)
-                      for n in (plan.up_part_floats, plan.down_part_floats))
-            _, _, K, N, r, _ = key
-            self._new(key, w, [(w[0], self.up_grad, plan.nparts, plan.rank_tile, N, r, _C.FACTOR_KR, 1.0, 1.0),
-                               (w[1], self.down_grad, plan.nparts, plan.rank_tile, K, r, _C.FACTOR_RK, 1.0, 1.0)])
-        return w
-
-    def conv_workspace(self, key, plan, device):
-        """Conv site, key = ("conv", B, Ci, Co, H, W, ks, r): (t_part, gt_part, gt, up_part, down_part)."""
-        w = self.ws.get(key)
-        if w is None:
-            _, B, Ci, Co, H, W, ks, r = key
-            w = conv_buffers(plan, B, r, H * W, device)
-            self._new(key, w, conv_reduce_rows(w, plan, Ci, Co, ks, r, self.up_grad, self.down_grad, 1.0))
-        return w
-
-    def conv3_nhwc_workspace(self, key, lplan, cplan, device):
-        """Channels-last 3x3 site, key = ("conv3n", B, Ci, Co, H, W, r): (gt_part, up_part, gt, down_part)."""
-        w = self.ws.get(key)
-        if w is None:
-            _, B, Ci, Co, H, W, r = key
-            w = conv3_nhwc_buffers(lplan, cplan, B * H * W, r, device)
-            self._new(key, w, conv3_nhwc_reduce_rows(w, lplan, cplan, Ci, Co, r, self.up_grad, self.down_grad, 1.0))
+            w = alloc()
+            self._new(key, w, rows(w, self.up_grad, self.down_grad, 1.0))
         return w
 
     def reduce_rows(self, key, plan=None):
@@ -165,10 +135,35 @@ class GradSink:
         self.pending = None
 
 
+# ---- the partial slabs of one site kind: ``*_buffers`` allocates them, ``*_reduce_rows`` names the two reduce_batched rows
+# that fold them into (up_grad, down_grad); ``_*_site`` bundles both with the shape key for GradSink.lookup / _begin / _finish
+def _slabs(sizes, device, least: int = 1):
+    return tuple(torch.empty(max(int(n), least), dtype=torch.float32, device=device) for n in sizes)
+
+
+def linear_buffers(plan, device):
+    """Linear site (``_C.linear_plan``): (gt_part, up_part, down_part)."""
+    return _slabs((plan.gt_part_floats, plan.up_part_floats, plan.down_part_floats), device)
+
+
+def linear_reduce_rows(w, plan, K, N, r, up_grad, down_grad, beta):
+    return [(w[1], up_grad, plan.nparts_up, plan.rank_tile, N, r, _C.FACTOR_KR, 1.0, beta),
+            (w[2], down_grad, plan.nparts_down, plan.rank_tile, K, r, _C.FACTOR_RK, 1.0, beta)]
+
+
+def self_buffers(plan, device):
+    """``linear_bwd_factors_self`` / the deferred one-launch passes (``_C.factors_self_plan``, ``_C.factors_mfma_plan``):
+    (up_part, down_part)."""
+    return _slabs((plan.up_part_floats, plan.down_part_floats), device)
+
+
+def self_reduce_rows(w, plan, K, N, r, up_grad, down_grad, beta):
+    return [(w[0], up_grad, plan.nparts, plan.rank_tile, N, r, _C.FACTOR_KR, 1.0, beta),
+            (w[1], down_grad, plan.nparts, plan.rank_tile, K, r, _C.FACTOR_RK, 1.0, beta)]
+
+
 def conv_buffers(plan, B: int, r: int, HW: int, device):
-    f = lambda n: torch.empty(max(int(n), 1), dtype=torch.float32, device=device)  # noqa: E731
-    return (f(plan.t_part_floats), f(plan.gt_part_floats), f(B * r * HW), f(plan.up_part_floats),
-            f(plan.down_part_floats))
+    return _slabs((plan.t_part_floats, plan.gt_part_floats, B * r * HW, plan.up_part_floats, plan.down_part_floats), device)
 
 
 def conv_reduce_rows(w, plan, Ci, Co, ks, r, up_grad, down_grad, beta):
@@ -177,13 +172,54 @@ def conv_reduce_rows(w, plan, Ci, Co, ks, r, up_grad, down_grad, beta):
 
 
 def conv3_nhwc_buffers(lplan, cplan, M: int, r: int, device):
-    f = lambda n: torch.empty(max(int(n), 4), dtype=torch.float32, device=device)  # noqa: E731
-    return (f(lplan.gt_part_floats), f(lplan.up_part_floats), f(M * r), f(cplan.down_part_floats))
+    return _slabs((lplan.gt_part_floats, lplan.up_part_floats, M * r, cplan.down_part_floats), device, least=4)
 
 
 def conv3_nhwc_reduce_rows(w, lplan, cplan, Ci, Co, r, up_grad, down_grad, beta):
     return [(w[1], up_grad, lplan.nparts_up, lplan.rank_tile, Co, r, _C.FACTOR_KR, 1.0, beta),
             (w[3], down_grad, cplan.nsplit, cplan.rank_pad, Ci * 9, r, _C.FACTOR_RK, 1.0, beta)]
+
+
+def _linear_site(plan, M, K, N, r, device):
+    return ((M, K, N, r), lambda: linear_buffers(plan, device),
+            lambda w, ug, dg, beta: linear_reduce_rows(w, plan, K, N, r, ug, dg, beta))
+
+
+def _self_site(kind, plan, M, K, N, r, device):
+    """``kind``: "self" (VALU pass) or "mfma" (matrix-core pass); the key carries the plan's row-block count."""
+    return ((kind, M, K, N, r, int(plan.nparts)), lambda: self_buffers(plan, device),
+            lambda w, ug, dg, beta: self_reduce_rows(w, plan, K, N, r, ug, dg, beta))
+
+
+def _conv_site(plan, B, Ci, Co, H, W, ks, r, device):
+    return (("conv", B, Ci, Co, H, W, ks, r), lambda: conv_buffers(plan, B, r, H * W, device),
+            lambda w, ug, dg, beta: conv_reduce_rows(w, plan, Ci, Co, ks, r, ug, dg, beta))
+
+
+def _begin(sink, site):
+    """First step of a backward that writes partial slabs: a sink still holding the partials of an earlier backward folds
+    them now, then hands out its persistent slabs for ``site`` = (key, alloc, rows); without a sink, fresh ones."""
+    key, alloc, rows = site
+    if sink is None:
+        return alloc()
+    if sink.pending is not None:
+        sink.flush()
+    return sink.lookup(key, alloc, rows)
+
+
+def _finish(sink, site, w, down, up):
+    """Last step: the slabs ``w`` stay pending on the sink (the trainer's batched reduce folds them into the flat gradient
+    buffer) and (None, None) is returned, or they are folded here into fresh (d_down, d_up) in the factors' dtypes."""
+    key, _, rows = site
+    if sink is not None:
+        sink.pending = key
+        return None, None
+    d_up = torch.empty(up.shape, dtype=torch.float32, device=up.device)
+    d_down = torch.empty(down.shape, dtype=torch.float32, device=down.device)
+    table, n, total = _C.make_reduce_table(rows(w, d_up, d_down, 0.0), up.device)
+    _C.reduce_batched(table, n, total)
+    d_up = d_up.to(up.dtype)
+    return d_down.to(down.dtype), d_up
 
 
 def _rows2d(t: torch.Tensor, cols: int) -> torch.Tensor:
@@ -248,6 +284,45 @@ def colreduce_any(x, t, layout, scale=1.0, out=None, beta=0.0, p=0.0, seed=0, of
         return full
     out.mul_(beta).add_(full.view_as(out))
     return out
+
+
+class OwedSite(NamedTuple):
+    """One site whose factor gradients the step's deferred pass still owes (``MergedWeights.flush_factors``).  ``kind``:
+    "mfma" (matrix-core pass) or "self" (VALU pass); ``plan``: the site's plan in that pass; ``drop`` = (p, seed, offset) of
+    nn.Dropout on the branch (matrix-core pass only: G enters masked) or None."""
+    g: torch.Tensor
+    x: torch.Tensor
+    down: torch.Tensor
+    up: torch.Tensor
+    up_part: torch.Tensor
+    down_part: torch.Tensor
+    scale: float
+    g_heads: Optional[tuple]
+    x_heads: Optional[tuple]
+    kind: str
+    plan: object
+    drop: Optional[tuple]
+
+
+def _deferred_plan(sink, g2, x2, down, up, sel=None):
+    """The matrix-core plan of a site whose two factor gradients may go to the step's deferred pass — a trainer state that
+    runs one, no selector, f32 factors, 16-bit rows, a shape the pass takes — else None."""
+    mw = getattr(getattr(sink, "owner", None), "merged", None)
+    if (mw is None or not mw.defer_factors or not _C.FACTORS_MFMA or sel is not None or down.dtype != torch.float32
+            or up.dtype != torch.float32 or g2.dtype not in (torch.bfloat16, torch.float16) or x2.dtype != g2.dtype):
+        return None
+    plan = _C.factors_mfma_plan(x2.shape[0], down.shape[1], up.shape[0], down.shape[0], g2.dtype)
+    return plan if plan.supported else None
+
+
+def _defer(sink, kind, plan, g2, x2, down, up, scale, g_heads=None, x_heads=None, drop=None) -> None:
+    """Leave both factor gradients of a site to the trainer's deferred pass: the sink's slabs of (kind, shape) are what the
+    pass will write, the site is owed, and the sink is pending until the trainer's batched reduce folds the slabs."""
+    site = _self_site(kind, plan, x2.shape[0], down.shape[1], up.shape[0], down.shape[0], g2.device)
+    up_part, down_part = _begin(sink, site)
+    mw = sink.owner.merged
+    mw.owe(g2, x2, down, up, up_part, down_part, scale, g_heads, x_heads, kind, plan, drop)
+    sink.pending = site[0]
 
 
 class LoraLinearFunction(torch.autograd.Function):
@@ -320,7 +395,7 @@ class LoraLinearFunction(torch.autograd.Function):
         same layouts and both factor gradients in the step's deferred matrix-core pass (which takes the head layouts and
         regenerates the mask); anything else — no trainer state, a shape the kernels refuse — detours through dense copies
         and the regular backward."""
-        x2, weight, down, up, t, sel = ctx.saved_tensors
+        x2, weight, down, up = ctx.saved_tensors[:4]
         in_heads, out_heads = ctx.in_heads, ctx.out_heads
         N, K = weight.shape
         r, M = down.shape[0], x2.shape[0]
@@ -328,43 +403,19 @@ class LoraLinearFunction(torch.autograd.Function):
         if not _C._rows_ok(g2):
             g2 = g2.contiguous()
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
-        s, p, seed, off, sink = ctx.scale, ctx.p, ctx.seed, ctx.off, ctx.sink
+        s, drop, sink = ctx.scale, (ctx.p, ctx.seed, ctx.off), ctx.sink
         down_c, up_c = down.contiguous(), up.contiguous()
-        mw = getattr(getattr(sink, "owner", None), "merged", None)
-        plan_m = None
-        if (mw is not None and mw.defer_factors and _C.FACTORS_MFMA and DEFER_MASKED_FACTORS and not need_w
-                and g2.dtype == x2.dtype):
-            plan_m = _C.factors_mfma_plan(M, K, N, r, g2.dtype)
-            if not plan_m.supported:
-                plan_m = None
+        plan_m = None if need_w else _deferred_plan(sink, g2, x2, down_c, up_c)
         dx_ok = (not need_x) or (WS_DROPOUT and _C.ws_supported(g2, N, K, r) and weight.is_contiguous()
                                  and _C.ws_heads_ok(N, K, out_heads, in_heads))
         if plan_m is None or not dx_ok:
-            from types import SimpleNamespace
-
-            x_log = unpack_heads(x2, in_heads) if in_heads else x2
-            g_log = unpack_heads(g2, out_heads) if out_heads else g2
-            fake = SimpleNamespace(saved_tensors=(x_log, weight, down, up, t, sel), in_heads=None, out_heads=None,
-                                   needs_input_grad=tuple(ctx.needs_input_grad[:5]) + (False,) * 6, scale=s, p=p,
-                                   seed=seed, off=off, sink=sink, fused=_C.fused_ok(x_log, N, r), has_bias=ctx.has_bias,
-                                   x_shape=x_log.shape)
-            dx, dw, db, d_down, d_up = LoraLinearFunction.backward(fake, g_log)[:5]
-            if dx is not None:
-                if in_heads:
-                    dx = pack_heads(dx, in_heads)
-                dx = dx.view(*ctx.x_shape[:-1], dx.shape[-1])
-            return dx, dw, db, d_down, d_up, None, None, None, None, None, None
-        if sink.pending is not None:
-            sink.flush()
+            return _linear_backward_unpacked(ctx, g2, drop) + (None,) * 6
         dx = None
         if need_x:
-            dx2, _gt = _C.linear_ws_dx(g2, weight, down_c, up_c, s, 0, p, seed, off, g_heads=out_heads, dx_heads=in_heads)
+            dx2, _gt = _C.linear_ws_dx(g2, weight, down_c, up_c, s, 0, *drop, g_heads=out_heads, dx_heads=in_heads)
             dx = dx2.view(*ctx.x_shape[:-1], dx2.shape[1])
-        key = ("mfma", M, K, N, r, int(plan_m.nparts))
-        up_part_m, down_part_m = sink.self_workspace(key, plan_m, g2.device)
-        mw.owe(g2, x2, down_c, up_c, up_part_m, down_part_m, s, out_heads, in_heads, "mfma", plan_m, (p, seed, off))
+        _defer(sink, "mfma", plan_m, g2, x2, down_c, up_c, s, out_heads, in_heads, drop)
         _log("bwd", ("ws_heads_dx+" if need_x else "") + "factors_deferred_mfma", M, K, N, r)
-        sink.pending = key
         db = None
         if ctx.has_bias and need_b:
             db = (unpack_heads(g2, out_heads) if out_heads else g2).sum(0)
@@ -373,184 +424,163 @@ class LoraLinearFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        if getattr(ctx, "in_heads", None) is not None or getattr(ctx, "out_heads", None) is not None:
+        if ctx.in_heads is not None or ctx.out_heads is not None:
             return LoraLinearFunction._backward_heads(ctx, g)
-        x2, weight, down, up, t, sel = ctx.saved_tensors
-        N, K = weight.shape
-        r = down.shape[0]
-        M = x2.shape[0]
-        g2 = _rows2d(g, N)
-        need_x, need_w, need_b, need_down, need_up = ctx.needs_input_grad[:5]
-        s, p, seed, off = ctx.scale, ctx.p, ctx.seed, ctx.off
-        sink = ctx.sink
-        d_up = d_down = dx = None
-        down_c, up_c = down.contiguous(), up.contiguous()
+        return _linear_backward(ctx.saved_tensors, ctx.needs_input_grad[:5], g, ctx.scale, (ctx.p, ctx.seed, ctx.off),
+                                ctx.sink, ctx.fused, ctx.has_bias, ctx.x_shape) + (None,) * 6
 
-        if ctx.fused and _C._rows_ok(g2) and (need_down or need_up or need_x):
-            key = (M, K, N, r)
-            plan = _C.linear_plan(*key)
-            if sink is not None and sink.pending is not None:
-                sink.flush()
-            mw = getattr(getattr(sink, "owner", None), "merged", None)
-            plan_m = None
-            if (mw is not None and mw.defer_factors and _C.FACTORS_MFMA and DEFER_MASKED_FACTORS and sel is None
-                    and down_c.dtype == torch.float32 and up_c.dtype == torch.float32
-                    and g2.dtype in (torch.bfloat16, torch.float16) and x2.dtype == g2.dtype):
-                plan_m = _C.factors_mfma_plan(M, K, N, r, g2.dtype)
-                if not plan_m.supported:
-                    plan_m = None
-            if not need_x and not need_w and plan_m is not None:
-                # no input gradient wanted (cross-attention k / v on the text states, the time-embedding projections):
-                # the backward of the site is its two factor gradients, and both are the deferred pass's — no launch here
-                # (configs[3]: 54 sites x two latency-bound launches of 10-23 us each)
-                key = ("mfma", M, K, N, r, int(plan_m.nparts))
-                up_part_m, down_part_m = sink.self_workspace(key, plan_m, g2.device)
-                mw.owe(g2, x2, down_c, up_c, up_part_m, down_part_m, s, None, None, "mfma", plan_m, (p, seed, off))
-                _log("bwd", "factors_deferred_mfma", M, K, N, r)
-                sink.pending = key
-                db = g2.sum(0) if (ctx.has_bias and need_b) else None
-                return None, None, db, None, None, None, None, None, None, None, None
-            # the per-site partial slabs (Gt column tiles, dUp / dDown row blocks) exist only on the paths that write them: a
-            # site whose factor gradients go to the step's deferred matrix-core pass registers nothing here (the
-            # dead slabs of every dropout site, and a reset of the trainer's reduce table per site)
-            key0, _bufs = key, []
 
-            def bufs():
-                if not _bufs:
-                    if sink is not None:
-                        _bufs.append(sink.workspace(key0, plan, g2.device))
-                    else:
-                        _bufs.append(tuple(torch.empty(max(int(n), 1), dtype=torch.float32, device=g2.device)
-                                           for n in (plan.gt_part_floats, plan.up_part_floats, plan.down_part_floats)))
-                return _bufs[0]
-            tile = 0
-            if (need_x and sel is None and down_c.dtype == torch.float32 and up_c.dtype == torch.float32
-                    and weight.is_contiguous() and g2.dtype in (torch.bfloat16, torch.float16)
-                    and weight.dtype == g2.dtype):
-                tile = _C.gemm_choice_bwd(g2, x2, weight, t, down_c, up_c, s, bufs)
-                if (p > 0.0 and WS_DROPOUT_WIDE_BWD and tile != _C.WS_TILE and M >= 256
-                        and _C.ws_supported(g2, N, K, r) and K % 8 == 0):
-                    tile = _C.WS_TILE
-                if p > 0.0 and (tile != _C.WS_TILE or not WS_DROPOUT):
-                    tile = 0  # the mask of the forward: weight-stationary kernel or the three-launch path
-            if tile:
-                # dX = G W + s (G up) down and Gt = s G up in ONE MFMA launch (weight-stationary on W^T packed in
-                # fragment order, or the LDS-ring kernel on the resident W^T); what remains are the parameter-gradient
-                # partials (G^T T and Gt^T X), both in one more launch
-                if tile == _C.WS_TILE:
-                    dx2, gt = _C.linear_ws_dx(g2, weight, down_c, up_c, s, 0, p, seed, off)
-                else:
-                    dx2, gt = _C.linear_gemm_dx(g2, _C.weight_t(weight), down_c, up_c, s, tile)
-                # both factor gradients: deferred to the step's one-launch matrix-core pass when a trainer state runs one
-                # (T recomputed from X, the forward's dropout mask regenerated on G inside the pass), else one launch here
-                if plan_m is not None:
-                    key = ("mfma", M, K, N, r, int(plan_m.nparts))
-                    up_part_m, down_part_m = sink.self_workspace(key, plan_m, g2.device)
-                    mw.owe(g2, x2, down_c, up_c, up_part_m, down_part_m, s, None, None, "mfma", plan_m, (p, seed, off))
-                    _log("bwd", ("ws" if tile == _C.WS_TILE else f"ring{tile}") + "_dx+factors_deferred_mfma", M, K, N, r)
-                else:
-                    gt_part, up_part, down_part = bufs()
-                    _C.linear_bwd_factors(g2, t, up_part, x2, gt, down_part, r, s, dropout=(p, seed, off))
-                    _log("bwd", ("ws" if tile == _C.WS_TILE else f"ring{tile}") + "_dx+factors", M, K, N, r)
-            elif plan_m is not None and need_x and r > 8 and not need_w:
-                # ranks 9..16 off the fused-GEMM tables (the GEGLU projections, M = 144 sites): Gt and the low-rank term of
-                # dX on the matrix-core primitives around the frozen GEMM, both factor gradients deferred
-                gt = rowdot_any(g2, up_c, _C.FACTOR_KR, s, None, True, p, seed, off)
-                dx2 = g2 @ weight  # frozen dense GEMM
-                if not _C._rows_ok(dx2):
-                    dx2 = dx2.contiguous()
-                rank_update_any_(dx2, gt, down_c, _C.FACTOR_RK, 1.0)
-                key = ("mfma", M, K, N, r, int(plan_m.nparts))
-                up_part_m, down_part_m = sink.self_workspace(key, plan_m, g2.device)
-                mw.owe(g2, x2, down_c, up_c, up_part_m, down_part_m, s, None, None, "mfma", plan_m, (p, seed, off))
-                _log("bwd", "rowdot+lib+rank_update+factors_deferred_mfma", M, K, N, r)
+def _linear_backward(saved, needs, g, s, drop, sink, fused, has_bias, x_shape):
+    """Gradient of :class:`LoraLinearFunction` on dense rows -> (dx, dw, db, d_down, d_up).  ``saved`` = (x2, weight, down,
+    up, t, sel) of the forward, ``needs`` = needs_input_grad of those five inputs, ``drop`` = (p, seed, offset) of the
+    forward's mask, ``fused`` = the forward's shape takes the fused kernels."""
+    x2, weight, down, up, t, sel = saved
+    N, K = weight.shape
+    r = down.shape[0]
+    M = x2.shape[0]
+    g2 = _rows2d(g, N)
+    need_x, need_w, need_b, need_down, need_up = needs
+    p, seed, off = drop
+    d_up = d_down = dx = None
+    down_c, up_c = down.contiguous(), up.contiguous()
+
+    if fused and _C._rows_ok(g2) and (need_down or need_up or need_x):
+        plan = _C.linear_plan(M, K, N, r)
+        site = _linear_site(plan, M, K, N, r, g2.device)
+        plan_m = _deferred_plan(sink, g2, x2, down_c, up_c, sel)
+        if not need_x and not need_w and plan_m is not None:
+            # no input gradient wanted (cross-attention k / v on the text states, the time-embedding projections):
+            # the backward of the site is its two factor gradients, and both are the deferred pass's — no launch here
+            # (configs[3]: 54 sites x two latency-bound launches of 10-23 us each)
+            _defer(sink, "mfma", plan_m, g2, x2, down_c, up_c, s, drop=drop)
+            _log("bwd", "factors_deferred_mfma", M, K, N, r)
+            return None, None, (g2.sum(0) if (has_bias and need_b) else None), None, None
+        # the per-site partial slabs (Gt column tiles, dUp / dDown row blocks) exist only on the paths that write them: a
+        # site whose factor gradients go to the step's deferred matrix-core pass registers nothing here (ADVICE r4: the
+        # dead slabs of every dropout site, and a reset of the trainer's reduce table per site)
+        _bufs = []
+
+        def bufs():
+            if not _bufs:
+                _bufs.append(_begin(sink, site))
+            return _bufs[0]
+        tile = 0
+        if (need_x and sel is None and down_c.dtype == torch.float32 and up_c.dtype == torch.float32
+                and weight.is_contiguous() and g2.dtype in (torch.bfloat16, torch.float16)
+                and weight.dtype == g2.dtype):
+            tile = _C.gemm_choice_bwd(g2, x2, weight, t, down_c, up_c, s, bufs)
+            if (p > 0.0 and WS_DROPOUT_WIDE_BWD and tile != _C.WS_TILE and M >= 256
+                    and _C.ws_supported(g2, N, K, r) and K % 8 == 0):
+                tile = _C.WS_TILE
+            if p > 0.0 and (tile != _C.WS_TILE or not WS_DROPOUT):
+                tile = 0  # the mask of the forward: weight-stationary kernel or the three-launch path
+        deferred = False
+        if tile:
+            # dX = G W + s (G up) down and Gt = s G up in ONE MFMA launch (weight-stationary on W^T packed in
+            # fragment order, or the LDS-ring kernel on the resident W^T); what remains are the parameter-gradient
+            # partials (G^T T and Gt^T X), both in one more launch
+            if tile == _C.WS_TILE:
+                dx2, gt = _C.linear_ws_dx(g2, weight, down_c, up_c, s, 0, p, seed, off)
             else:
-                _log("bwd", "g+lib+x", M, K, N, r)
-                gt_part, up_part, down_part = bufs()
-                _C.linear_bwd_g(g2, t, up_c, gt_part, up_part, s, p, seed, off)
-                dx2 = (g2 @ weight) if need_x else None  # frozen dense GEMM
-                if dx2 is not None and not _C._rows_ok(dx2):
-                    dx2 = dx2.contiguous()
-                _C.linear_bwd_x(x2, dx2, gt_part, plan.nct_g, down_c, sel, down_part)
-            if need_x:
-                dx = dx2.view(ctx.x_shape)
-            if sink is not None:
-                sink.pending = key  # summed into the flat grad buffer by the trainer's batched reduce
+                dx2, gt = _C.linear_gemm_dx(g2, _C.weight_t(weight), down_c, up_c, s, tile)
+            # both factor gradients: deferred to the step's one-launch matrix-core pass when a trainer state runs one
+            # (T recomputed from X, the forward's dropout mask regenerated on G inside the pass; configs[3]: 22.54 ->
+            # 24.09 steps/s against one launch per site, profiles/r04_cfg3_ab.txt), else one launch here
+            name = "ws" if tile == _C.WS_TILE else f"ring{tile}"
+            if plan_m is not None:
+                _defer(sink, "mfma", plan_m, g2, x2, down_c, up_c, s, drop=drop)
+                deferred = True
+                _log("bwd", name + "_dx+factors_deferred_mfma", M, K, N, r)
             else:
                 gt_part, up_part, down_part = bufs()
-                d_up = torch.empty((N, r), dtype=torch.float32, device=g2.device)
-                d_down = torch.empty((r, K), dtype=torch.float32, device=g2.device)
-                rows = [(up_part, d_up, plan.nparts_up, plan.rank_tile, N, r, _C.FACTOR_KR, 1.0, 0.0),
-                        (down_part, d_down, plan.nparts_down, plan.rank_tile, K, r, _C.FACTOR_RK, 1.0, 0.0)]
-                table, n, total = _C.make_reduce_table(rows, g2.device)
-                _C.reduce_batched(table, n, total)
-                d_up, d_down = d_up.to(up.dtype), d_down.to(down.dtype)
+                _C.linear_bwd_factors(g2, t, up_part, x2, gt, down_part, r, s, dropout=drop)
+                _log("bwd", name + "_dx+factors", M, K, N, r)
+        elif plan_m is not None and need_x and r > 8 and not need_w:
+            # ranks 9..16 off the fused-GEMM tables (the GEGLU projections, M = 144 sites): Gt and the low-rank term of
+            # dX on the matrix-core primitives around the frozen GEMM, both factor gradients deferred
+            gt = rowdot_any(g2, up_c, _C.FACTOR_KR, s, None, True, p, seed, off)
+            dx2 = g2 @ weight  # frozen dense GEMM
+            if not _C._rows_ok(dx2):
+                dx2 = dx2.contiguous()
+            rank_update_any_(dx2, gt, down_c, _C.FACTOR_RK, 1.0)
+            _defer(sink, "mfma", plan_m, g2, x2, down_c, up_c, s, drop=drop)
+            deferred = True
+            _log("bwd", "rowdot+lib+rank_update+factors_deferred_mfma", M, K, N, r)
         else:
-            gt = None
-            _log("bwd", "primitives", M, K, N, r)
-            if need_x or need_down:
-                gt = rowdot_any(g2, up_c, _C.FACTOR_KR, s, sel, True, p, seed, off)  # dT = s*(G.*mask) @ B @ S
-            if need_up:
-                if sink is not None:
-                    colreduce_any(g2, t, _C.FACTOR_KR, s, out=sink.up_grad, beta=1.0, p=p, seed=seed, off=off)
-                else:
-                    d_up = colreduce_any(g2, t, _C.FACTOR_KR, s, p=p, seed=seed, off=off).to(up.dtype)
-            if need_down:
-                if sink is not None:
-                    colreduce_any(x2, gt, _C.FACTOR_RK, 1.0, out=sink.down_grad, beta=1.0)
-                else:
-                    d_down = colreduce_any(x2, gt, _C.FACTOR_RK, 1.0).to(down.dtype)
-            if need_x:
-                dx2 = g2 @ weight  # frozen dense GEMM
-                rank_update_any_(dx2, gt, down_c, _C.FACTOR_RK, 1.0)
-                dx = dx2.view(ctx.x_shape)
-        dw = g2.t() @ x2 if need_w else None
-        db = g2.sum(0) if (ctx.has_bias and need_b) else None
-        return dx, dw, db, d_down, d_up, None, None, None, None, None, None
+            _log("bwd", "g+lib+x", M, K, N, r)
+            gt_part, up_part, down_part = bufs()
+            _C.linear_bwd_g(g2, t, up_c, gt_part, up_part, s, p, seed, off)
+            dx2 = (g2 @ weight) if need_x else None  # frozen dense GEMM
+            if dx2 is not None and not _C._rows_ok(dx2):
+                dx2 = dx2.contiguous()
+            _C.linear_bwd_x(x2, dx2, gt_part, plan.nct_g, down_c, sel, down_part)
+        if need_x:
+            dx = dx2.view(x_shape)
+        if not deferred:
+            d_down, d_up = _finish(sink, site, bufs(), down, up)
+    else:
+        gt = None
+        _log("bwd", "primitives", M, K, N, r)
+        if need_x or need_down:
+            gt = rowdot_any(g2, up_c, _C.FACTOR_KR, s, sel, True, p, seed, off)  # dT = s*(G.*mask) @ B @ S
+        if need_up:
+            if sink is not None:
+                colreduce_any(g2, t, _C.FACTOR_KR, s, out=sink.up_grad, beta=1.0, p=p, seed=seed, off=off)
+            else:
+                d_up = colreduce_any(g2, t, _C.FACTOR_KR, s, p=p, seed=seed, off=off).to(up.dtype)
+        if need_down:
+            if sink is not None:
+                colreduce_any(x2, gt, _C.FACTOR_RK, 1.0, out=sink.down_grad, beta=1.0)
+            else:
+                d_down = colreduce_any(x2, gt, _C.FACTOR_RK, 1.0).to(down.dtype)
+        if need_x:
+            dx2 = g2 @ weight  # frozen dense GEMM
+            rank_update_any_(dx2, gt, down_c, _C.FACTOR_RK, 1.0)
+            dx = dx2.view(x_shape)
+    dw = g2.t() @ x2 if need_w else None
+    db = g2.sum(0) if (has_bias and need_b) else None
+    return dx, dw, db, d_down, d_up
 
 
-# Module constants (tests and A/B scripts flip them; not environment switches):
-# input gradients of the merged-weight sites as F.linear(G, W_eff^T-stored) instead of G @ W_eff (MergedWeights.lookup);
-TRANSPOSED_DX = True
-# factor gradients of the dropout sites that run the fused MFMA input-gradient kernels: deferred to the step's matrix-core
-# pass (mask regenerated inside) instead of one linear_bwd_factors launch per site (configs[3]: 22.54 -> 24.09 steps/s,
-# same box, profiles/r04_cfg3_ab.txt);
-DEFER_MASKED_FACTORS = True
+def _linear_backward_unpacked(ctx, g2, drop=(0.0, 0, 0)):
+    """Dense detour of a backward whose forward ran in head-padded rows (``ctx.in_heads`` / ``ctx.out_heads``; saved
+    tensors x2, weight, down, up, t; such a forward takes no selector): unpacked copies of X and G through
+    :func:`_linear_backward` (which also times the fused candidates of the shape), dX packed again
+    -> (dx, dw, db, d_down, d_up)."""
+    x2, weight, down, up, t = ctx.saved_tensors[:5]
+    x_log = unpack_heads(x2, ctx.in_heads) if ctx.in_heads else x2
+    g_log = unpack_heads(g2, ctx.out_heads) if ctx.out_heads else g2
+    dx, dw, db, d_down, d_up = _linear_backward(
+        (x_log, weight, down, up, t, None), ctx.needs_input_grad[:5], g_log, ctx.scale, drop, ctx.sink,
+        _C.fused_ok(x_log, weight.shape[0], down.shape[0]), ctx.has_bias, x_log.shape)
+    if dx is not None:
+        if ctx.in_heads:
+            dx = pack_heads(dx, ctx.in_heads)
+        dx = dx.view(*ctx.x_shape[:-1], dx.shape[-1])
+    return dx, dw, db, d_down, d_up
+
+
+# Module constants, not environment switches; each is the parity twin or the A/B that a test still flips:
 # q / k / v (k / v) of an attention block on ONE concatenated scratch weight: one forward GEMM per group (+0.8 %, same box)
+# (tests/test_round2_cpu.py flips it through apply_ab_overrides)
 CONCAT_GROUPS = True
-# ranks 9..16 on 16-bit activations: matrix-core forms of rowdot / rank_update / linear_fwd / linear_bwd_g
-# (csrc/rank16_mfma.hip; 0 = the VALU kernels, through the library's lora_amd_rank16_mfma hook)
-RANK16_MFMA = True
-# the one-launch factor pass as one launch per REGISTER class (class 1 = the M = 16384 sites: three workgroups per CU,
-# csrc/factor_mfma.hip) instead of one launch of the two-per-CU kernel over every site (rounds 4-5)
-FM_TWO_CLASSES = True
-# the factor-pass launches of one flush on forked streams (their tails could overlap) instead of back to back on the launch
-# stream.  OFF: measured, same box, the captured step with the fork / join edges runs 31.3 steps/s against 35.6 without
-# (profiles/r06_concurrent_factor_launches_ab.txt: a multi-stream hipGraph costs the whole step 3.9 ms, far more than three tails)
-CONCURRENT_FACTOR_LAUNCHES = False
-# the factor-pass tables ordered longest row blocks first (flush_factors) instead of in backward order; ..._CLASS1: also the
-# class-1 table.  Same box, kernel traces (profiles/r06_fm_table_order_ab.txt): class 2 278-285 -> 248-249 us, class 1
-# 319-321 -> 323 us (its blocks differ 5x, but the wide ones are a third of them and already interleaved): class 2 only
-FM_LONGEST_FIRST = True
-FM_LONGEST_FIRST_CLASS1 = False
-# the factor pass finds a workgroup's site through the plan's block -> site map (one scalar load) instead of copying the table's
-# block prefix to LDS and searching it (third session of round 6; False = the search: the A/B)
-FM_BLOCK_MAP = True
 # the channels-last 3x3 site as ONE forward launch (csrc/conv_nhwc.hip, round 6: batched pack once per optimiser step + the
 # fused down-conv / fold / up-projection / dropout / add kernel) and its G pass with the Gt fold inside the launch; False =
-# the launch sequence of rounds 3-5 (pack + down [+ sum_parts] + rank_update; bwd_g + sum_parts): the A/B and the parity twin
+# the launch sequence of rounds 3-5 (pack + down [+ sum_parts] + rank_update; bwd_g + sum_parts)
+# (tests/test_gpu_conv_nhwc.py runs both)
 CONV3_FUSED = True
 # f32-resident frozen weights under 16-bit autocast (the reference's precision policy): the in-step merge reads the f32 MASTER
 # (csrc/merge_step.hip, src_f32: W_eff = round16(W32 + scale up down), one rounding, no bf16 copy of W kept) instead of a cached
-# 16-bit shadow of it (round16(round16(W32) + scale up down)); False = the shadow-then-merge route: the A/B and the parity twin
+# 16-bit shadow of it (round16(round16(W32) + scale up down)); False = the shadow-then-merge route
+# (tests/test_gpu_master_policy.py runs both)
 MASTER_MERGE = True
 
 
 def apply_ab_overrides(spec: str, namespace: dict) -> dict:
     """``LORA_AMD_AB="NAME=0,OTHER=1"``: the ONE measurement switch for same-box A/B runs — flips the module constants
-    above (and only those) without a code edit; every A/B log under profiles/ names the spec it ran with."""
-    allowed = ("TRANSPOSED_DX", "DEFER_MASKED_FACTORS", "CONCAT_GROUPS", "RANK16_MFMA", "FM_TWO_CLASSES", "CONCURRENT_FACTOR_LAUNCHES", "FM_LONGEST_FIRST", "FM_LONGEST_FIRST_CLASS1", "FM_BLOCK_MAP", "CONV3_FUSED", "MASTER_MERGE", "WS_HEADS", "WS_DROPOUT",
-               "WS_DROPOUT_WIDE",
+    listed in ``allowed`` (and only those) without a code edit; every A/B log under profiles/ names the spec it ran with
+    (a constant retired since then is an unknown name here)."""
+    allowed = ("CONCAT_GROUPS", "CONV3_FUSED", "MASTER_MERGE", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
                "WS_DROPOUT_WIDE_BWD")
     done = {}
     for item in filter(None, (s.strip() for s in spec.split(","))):
@@ -562,14 +592,12 @@ def apply_ab_overrides(spec: str, namespace: dict) -> dict:
 
 
 apply_ab_overrides(os.environ.get("LORA_AMD_AB", ""), globals())
-if not RANK16_MFMA and _C.available():
-    _C.rank16_mfma(0)
 
 # Rounding of the in-step merge of 16-bit weights (csrc/merge_step.hip): "dither" (default) = nearest with a fixed
 # per-element dither, so that a delta below half an ulp of the frozen weight survives in the row sums; "once" = nearest even
 # (one of the two documented USER options that are environment variables read once at import — the other is
 # LORA_AMD_FACTORS_MFMA in _C.py; they choose numerics / a pass, not a measurement variant, so they are not
-# part of LORA_AMD_AB; tests flip the module attribute)
+# part of LORA_AMD_AB; tests/test_gpu_parity_r4.py and tests/test_gpu_master_policy.py flip the module attribute)
 MERGE_ROUNDING = _C.ROUND_ONCE if os.environ.get("LORA_AMD_MERGE_ROUNDING", "dither") == "once" else _C.ROUND_DITHER
 
 
@@ -633,7 +661,7 @@ class MergedWeights:
         profiles/r03_kbench_gemmlayout.log); None when no input gradient is needed."""
         e = self._entry(module, w, b, dt, in_heads, out_heads)
         # f32 weights with f32 activations go through the collapse kernel, whose transposed sites need 32 | N (its column tiles)
-        if need_dx and TRANSPOSED_DX and e["w_eff_t"] is None and (e["step"] or (in_heads is None and w.shape[0] % 32 == 0)):
+        if need_dx and e["w_eff_t"] is None and (e["step"] or (in_heads is None and w.shape[0] % 32 == 0)):
             self._add_transposed(e)
         return e["w_eff"], e["b_eff"], e["w_eff_t"]
 
@@ -702,7 +730,7 @@ class MergedWeights:
                                        torch.zeros(n_o, dtype=cat.dtype, device=cat.device) for e, n_o in zip(es, n_outs)])
             self.groups[gkey] = g
         es = [self.entries[(id(m), None, out_heads, dt)] for m in modules]
-        if need_dx and TRANSPOSED_DX and g["cat_t"] is None:
+        if need_dx and g["cat_t"] is None:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("MergedWeights: a group's transposed scratch weight must exist before hipGraph capture")
             g["cat_t"] = torch.zeros((g["cat"].shape[1], g["cat"].shape[0]), dtype=g["cat"].dtype, device=g["cat"].device)
@@ -812,8 +840,7 @@ class MergedWeights:
         self.refreshes += 1
 
     def owe(self, g2, x2, down, up, up_part, down_part, scale, g_heads, x_heads, kind="self", plan=None, drop=None) -> None:
-        """``drop`` = (p, seed, offset) of nn.Dropout on the site's branch (matrix-core pass only): G enters masked."""
-        self._owed.append((g2, x2, down, up, up_part, down_part, scale, g_heads, x_heads, kind, plan, drop))
+        self._owed.append(OwedSite(g2, x2, down, up, up_part, down_part, scale, g_heads, x_heads, kind, plan, drop))
 
     def _upload(self, key, raw: bytes, device, capturing: bool) -> torch.Tensor:
         """A site table -> device memory on the launch stream.  The table changes every eager step (fresh G / X
@@ -877,76 +904,72 @@ class MergedWeights:
         if not self._owed:
             return
         owed, self._owed = self._owed, []
-        groups = {}
-        # one launch per register class of a (dtype, rank tile, masked) group: class 1 (the narrower operand's block fits 6
-        # resident pairs per wave: every M = 16384 site) runs three workgroups per CU, class 2 two (csrc/factor_mfma.hip)
-        one_class = not FM_TWO_CLASSES
-        for st in owed:
-            r, kind, plan = st[2].shape[0], st[9], st[10]
-            rt = 4 if r <= 4 else 8 if r <= 8 else 16
-            masked = kind == "mfma" and st[11] is not None and st[11][0] > 0.0
-            # (register class, masked, block height): class 1 = one height per table (64), class 2 = one launch for both
-            # heights (0: the workgroup enters its site's instantiation)
-            cls = 0
-            if kind == "mfma":
-                c_ = 2 if one_class else int(plan.lds_class)
-                cls = (c_, masked, int(plan.rows_per_block) if c_ == 1 else 0)
-            groups.setdefault((kind, st[0].dtype, rt, cls), []).append(st)
+        groups = self._group_owed(owed)
+        self._pack_groups(groups)
         capturing = torch.cuda.is_current_stream_capturing()
-        packed = {}  # activation dtype -> packs of this flush's sites, each adapter once
-        for (kind, dt, rt, cls), sites in groups.items():
+        # every table goes up on the launch stream first; then the launches (independent: disjoint slabs), largest first
+        launches = [self._table_launch(gkey, sites, capturing) for gkey, sites in groups.items()]
+        launches.sort(key=lambda t: -t[0])
+        for _, launch in launches:
+            launch()
+
+    @staticmethod
+    def _group_owed(owed) -> dict:
+        """(pass, activation dtype, rank tile, class) -> sites in backward order.  The matrix-core pass is one launch per
+        REGISTER class of a (dtype, rank tile, masked) group: class 1 (the narrower operand's block fits 6 resident pairs
+        per wave: every M = 16384 site) runs three workgroups per CU and one block height per table, class 2 two per CU
+        and one launch for both heights (0: the workgroup enters its site's instantiation; csrc/factor_mfma.hip)."""
+        groups = {}
+        for st in owed:
+            r = st.down.shape[0]
+            cls = 0
+            if st.kind == "mfma":
+                c = int(st.plan.lds_class)
+                masked = st.drop is not None and st.drop[0] > 0.0
+                cls = (c, masked, int(st.plan.rows_per_block) if c == 1 else 0)
+            groups.setdefault((st.kind, st.g.dtype, 4 if r <= 4 else 8 if r <= 8 else 16, cls), []).append(st)
+        return groups
+
+    def _pack_groups(self, groups) -> None:
+        """This step's factors of every matrix-core site in fragment order: one pack launch per activation dtype, each
+        adapter once."""
+        packed = {}
+        for (kind, dt, _, _), sites in groups.items():
             if kind == "mfma":
                 for st in sites:
-                    pk = self._packs_of(st[2], st[3], dt, st[10])
+                    pk = self._packs_of(st.down, st.up, dt, st.plan)
                     packed.setdefault(dt, {})[id(pk[0])] = pk
         for dt, pks in packed.items():
             self._pack_factors(dt, list(pks.values()))
-        launches = []   # (workgroups, closure): the tables go up on the launch stream first, the kernels may then run side by side
-        for (kind, dt, rt, cls), sites in groups.items():
-            dev0 = sites[0][0].device
-            if kind == "mfma":
-                # longest row blocks first: a block of the widest sites lives 3-5x longer than one of the square ones; in backward
-                # order some of them start late and run alone in the launch's tail (FM_LONGEST_FIRST above).  Stable: equal
-                # blocks keep the backward order.
-                if FM_LONGEST_FIRST and (cls[0] != 1 or FM_LONGEST_FIRST_CLASS1):
-                    sites = sorted(sites, key=lambda st: -int(st[10].rows_per_block) * (st[0].shape[1] + st[1].shape[1]))
-                rows = []
-                for (g2, x2, down, up, up_part, down_part, scale, g_heads, x_heads, _, plan, drop) in sites:
-                    pk = self._packs_of(down, up, dt, plan)
-                    rows.append((g2, x2, pk[0], pk[1], up_part, down_part, scale, g_heads, x_heads, down.shape[0],
-                                 plan, drop))
-                arr, grid = _C.factors_mfma_table(rows, dt, cls[0])
-                # the block -> site map rides behind the table (one upload): a workgroup finds its site with one scalar load
-                raw, moff = _C.factors_mfma_table_bytes(arr, grid) if FM_BLOCK_MAP else (bytes(arr), 0)
-                dev = self._upload((kind, dt, rt, cls), raw, dev0, capturing)
-                launches.append((grid, lambda dev=dev, n=len(sites), grid=grid, cls=cls, dt=dt, moff=moff:
-                                 _C.linear_bwd_factors_mfma_ragged(dev, n, grid, cls[0], dt, cls[1], cls[2], moff)))
-            else:
-                arr, grid = _C.factors_self_ragged_table([st[:9] for st in sites], dt)
-                dev = self._upload((kind, dt, rt, cls), bytes(arr), dev0, capturing)
-                launches.append((grid, lambda dev=dev, n=len(sites), grid=grid, r=sites[0][2].shape[0], dt=dt:
-                                 _C.linear_bwd_factors_self_ragged(dev, n, grid, r, dt)))
-        # The launches of one flush are independent (disjoint slabs): the largest goes out on the launch stream, the others on
-        # side streams forked from it and joined behind it, so that the tail of one launch fills with the workgroups of the next
-        # instead of three tails in a row (round 6: one launch per register class and block height = three launches in the
-        # headline step).  Capturable: the fork / join become edges of the hipGraph.
-        launches.sort(key=lambda t: -t[0])
-        if len(launches) == 1 or not CONCURRENT_FACTOR_LAUNCHES:
-            for _, fn in launches:
-                fn()
-            return
-        main = torch.cuda.current_stream()
-        side = self.__dict__.setdefault("_side_streams", [])
-        while len(side) < len(launches) - 1:
-            side.append(torch.cuda.Stream(device=main.device))
-        for st_ in side[:len(launches) - 1]:
-            st_.wait_stream(main)
-        launches[0][1]()
-        for (_, fn), st_ in zip(launches[1:], side):
-            with torch.cuda.stream(st_):
-                fn()
-        for st_ in side[:len(launches) - 1]:
-            main.wait_stream(st_)
+
+    def _table_launch(self, gkey, sites, capturing: bool):
+        """Builds and uploads the site table of one group -> (workgroups, the launch on that table)."""
+        kind, dt, _, cls = gkey
+        dev0 = sites[0].g.device
+        if kind != "mfma":
+            arr, grid = _C.factors_self_ragged_table([st[:9] for st in sites], dt)   # g .. x_heads
+            dev = self._upload(gkey, bytes(arr), dev0, capturing)
+            n, r = len(sites), sites[0].down.shape[0]
+            return grid, lambda: _C.linear_bwd_factors_self_ragged(dev, n, grid, r, dt)
+        lds_class, masked, height = cls
+        if lds_class != 1:
+            # longest row blocks first: a block of the widest sites lives 3-5x longer than one of the square ones; in backward
+            # order some of them start late and run alone in the launch's tail.  Stable: equal blocks keep the backward
+            # order.  Class 2 only (kernel traces, same box, profiles/r06_fm_table_order_ab.txt: class 2 278-285 -> 248-249 us;
+            # class 1 319-321 -> 323 us: its blocks differ 5x, but the wide ones are a third of them and already interleaved)
+            sites = sorted(sites, key=lambda st: -int(st.plan.rows_per_block) * (st.g.shape[1] + st.x.shape[1]))
+        rows = []
+        for st in sites:
+            pk = self._packs_of(st.down, st.up, dt, st.plan)
+            rows.append((st.g, st.x, pk[0], pk[1], st.up_part, st.down_part, st.scale, st.g_heads, st.x_heads,
+                         st.down.shape[0], st.plan, st.drop))
+        arr, grid = _C.factors_mfma_table(rows, dt, lds_class)
+        # the block -> site map rides behind the table (one upload): a workgroup finds its site with one scalar load instead
+        # of copying the table's block prefix to LDS and searching it (614-615 -> 603-606 us)
+        raw, moff = _C.factors_mfma_table_bytes(arr, grid)
+        dev = self._upload(gkey, raw, dev0, capturing)
+        n = len(sites)
+        return grid, lambda: _C.linear_bwd_factors_mfma_ragged(dev, n, grid, lds_class, dt, masked, height, moff)
 
     def invalidate(self) -> None:
         """Factor tensors were re-bound (new storage) or a scale changed: rebuild the entries on their next use."""
@@ -964,39 +987,21 @@ def _merged_factor_grads(g2, x2, down, up, scale, sink, out_heads, in_heads, K, 
     ``MergedWeights.defer_factors``: the matrix-core pass for 16-bit activations, the VALU pass otherwise), or one
     ``linear_bwd_factors_self`` launch here.  Returns (d_down, d_up) — None when they leave through ``sink``."""
     M, r = x2.shape[0], down.shape[0]
+    down_c, up_c = down.contiguous(), up.contiguous()
     mw = getattr(getattr(sink, "owner", None), "merged", None)
-    defer = mw is not None and mw.defer_factors
-    plan, kind = None, "self"
-    if defer and _C.FACTORS_MFMA_MODE == "all":
-        plan = _C.factors_mfma_plan(M, K, N, r, g2.dtype)
-        kind = "mfma" if plan.supported else "self"
-    if kind == "self":
-        plan = _C.factors_self_plan(M, K, N, r, _C.SELF_ROWS_DEFERRED if defer else 0)
-    key = (kind, M, K, N, r, int(plan.nparts))
-    if sink is not None:
-        if sink.pending is not None:
-            sink.flush()
-        up_part, down_part = sink.self_workspace(key, plan, g2.device)
-    else:
-        up_part, down_part = (torch.empty(max(int(n), 1), dtype=torch.float32, device=g2.device)
-                              for n in (plan.up_part_floats, plan.down_part_floats))
-    if defer:
-        mw.owe(g2, x2, down.contiguous(), up.contiguous(), up_part, down_part, scale, out_heads, in_heads, kind, plan)
+    if mw is not None and mw.defer_factors:
+        plan = _deferred_plan(sink, g2, x2, down_c, up_c) if _C.FACTORS_MFMA_MODE == "all" else None
+        kind = "mfma"
+        if plan is None:
+            kind, plan = "self", _C.factors_self_plan(M, K, N, r, _C.SELF_ROWS_DEFERRED)
+        _defer(sink, kind, plan, g2, x2, down_c, up_c, scale, out_heads, in_heads)
         _log("bwd", f"{tag}_dx+factors_deferred_{kind}", M, K, N, r)
-    else:
-        _C.linear_bwd_factors_self(g2, x2, down.contiguous(), up.contiguous(), up_part, down_part, scale,
-                                   g_heads=out_heads, x_heads=in_heads)
-        _log("bwd", f"{tag}_dx+factors_self", M, K, N, r)
-    if sink is not None:
-        sink.pending = key
         return None, None
-    d_up = torch.empty((N, r), dtype=torch.float32, device=g2.device)
-    d_down = torch.empty((r, K), dtype=torch.float32, device=g2.device)
-    rows = [(up_part, d_up, plan.nparts, plan.rank_tile, N, r, _C.FACTOR_KR, 1.0, 0.0),
-            (down_part, d_down, plan.nparts, plan.rank_tile, K, r, _C.FACTOR_RK, 1.0, 0.0)]
-    table, n, total = _C.make_reduce_table(rows, g2.device)
-    _C.reduce_batched(table, n, total)
-    return d_down.to(down.dtype), d_up.to(up.dtype)
+    site = _self_site("self", _C.factors_self_plan(M, K, N, r, 0), M, K, N, r, g2.device)
+    up_part, down_part = w = _begin(sink, site)
+    _C.linear_bwd_factors_self(g2, x2, down_c, up_c, up_part, down_part, scale, g_heads=out_heads, x_heads=in_heads)
+    _log("bwd", f"{tag}_dx+factors_self", M, K, N, r)
+    return _finish(sink, site, w, down, up)
 
 
 class LoraLinearMergedFunction(torch.autograd.Function):
@@ -1181,48 +1186,17 @@ class LoraLinearHeadsFunction(torch.autograd.Function):
         tile = _C.gemm_choice_bwd_cached(M, K, N, r, g2.dtype)
         if not (tile and plan.fused and _C._rows_ok(g2) and weight.is_contiguous() and _C.heads_tile_ok(ctx.in_heads)
                 and not need_w):
-            # dense detour: unpacked copies through the regular backward (which also times the fused candidates, so the
-            # next backward of this shape stays in the padded layout)
-            from types import SimpleNamespace
-
-            x_log = unpack_heads(x2, ctx.in_heads) if ctx.in_heads else x2
-            g_log = unpack_heads(g2, ctx.out_heads) if ctx.out_heads else g2
-            fake = SimpleNamespace(saved_tensors=(x_log, weight, down, up, t, None),
-                                   needs_input_grad=tuple(ctx.needs_input_grad[:5]) + (False,) * 4, scale=s, p=0.0,
-                                   seed=0, off=0, sink=sink, fused=_C.fused_ok(x_log, N, r), has_bias=ctx.has_bias,
-                                   x_shape=x_log.shape)
-            dx, dw, db, d_down, d_up = LoraLinearFunction.backward(fake, g_log)[:5]
-            if dx is not None:
-                if ctx.in_heads:
-                    dx = pack_heads(dx, ctx.in_heads)
-                dx = dx.view(*ctx.x_shape[:-1], dx.shape[-1])
-            return dx, dw, db, d_down, d_up, None, None, None, None, None
-        key = (M, K, N, r)
-        if sink is not None:
-            if sink.pending is not None:
-                sink.flush()
-            _, up_part, down_part = sink.workspace(key, plan, g2.device)
-        else:
-            up_part, down_part = (torch.empty(max(int(n), 1), dtype=torch.float32, device=g2.device)
-                                  for n in (plan.up_part_floats, plan.down_part_floats))
+            # dense detour (it also times the fused candidates, so the next backward of this shape stays in the padded layout)
+            return _linear_backward_unpacked(ctx, g2) + (None,) * 5
+        site = _linear_site(plan, M, K, N, r, g2.device)
+        w = _begin(sink, site)
         down_c, up_c = down.contiguous(), up.contiguous()
         dx2, gt = _C.linear_gemm_dx(g2, _C.weight_t(weight), down_c, up_c, s, tile, g_heads=ctx.out_heads,
                                     dx_heads=ctx.in_heads)
         _log("bwd", f"ring{tile}_heads_dx+factors", M, K, N, r)
-        _C.linear_bwd_factors(g2, t, up_part, x2, gt, down_part, r, s, None, g_heads=ctx.out_heads,
-                              x_heads=ctx.in_heads)
+        _C.linear_bwd_factors(g2, t, w[1], x2, gt, w[2], r, s, None, g_heads=ctx.out_heads, x_heads=ctx.in_heads)
         dx = dx2.view(*ctx.x_shape[:-1], dx2.shape[1]) if need_x else None
-        d_up = d_down = None
-        if sink is not None:
-            sink.pending = key
-        else:
-            d_up = torch.empty((N, r), dtype=torch.float32, device=g2.device)
-            d_down = torch.empty((r, K), dtype=torch.float32, device=g2.device)
-            rows = [(up_part, d_up, plan.nparts_up, plan.rank_tile, N, r, _C.FACTOR_KR, 1.0, 0.0),
-                    (down_part, d_down, plan.nparts_down, plan.rank_tile, K, r, _C.FACTOR_RK, 1.0, 0.0)]
-            table, n, total = _C.make_reduce_table(rows, g2.device)
-            _C.reduce_batched(table, n, total)
-            d_up, d_down = d_up.to(up.dtype), d_down.to(down.dtype)
+        d_down, d_up = _finish(sink, site, w, down, up)
         db = None
         if ctx.has_bias and need_b:
             db = (unpack_heads(g2, ctx.out_heads) if ctx.out_heads else g2).sum(0)
@@ -1325,34 +1299,18 @@ class LoraLinearGroupFunction(torch.autograd.Function):
                 if not _C._rows_ok(g2):
                     g2 = g2.contiguous()
                 down_c, up_c = down.contiguous(), up.contiguous()
-                key = (M, K, N, r)
-                plan = _C.linear_plan(*key)
-                if sink is not None:
-                    if sink.pending is not None:
-                        sink.flush()
-                    gt_part, up_part, down_part = sink.workspace(key, plan, g2.device)
-                else:
-                    gt_part, up_part, down_part = (torch.empty(max(int(k_), 1), dtype=torch.float32, device=g2.device)
-                                                   for k_ in (plan.gt_part_floats, plan.up_part_floats,
-                                                              plan.down_part_floats))
+                plan = _C.linear_plan(M, K, N, r)
+                site = _linear_site(plan, M, K, N, r, g2.device)
+                w = _begin(sink, site)
                 # dX (+)= G W + s (G up) down and Gt = s G up: weight-stationary on W^T, accumulating across the sites
                 first = dx2 is None
                 if first:
                     dx2 = torch.empty((M, K), dtype=x2.dtype, device=x2.device)
                 (_, gt), = _C.linear_ws(g2, [dict(wp=_C.ws_pack(weight, True), N=K, down=up_c, up=down_c, scale=scale,
                                                   t_scale=scale, flayout=3 if first else 7, y=dx2)])
-                _C.linear_bwd_factors(g2, ts[i], up_part, x2, gt, down_part, r, scale)
+                _C.linear_bwd_factors(g2, ts[i], w[1], x2, gt, w[2], r, scale)
                 _log("bwd", "ws_dx+factors", M, K, N, r)
-                if sink is not None:
-                    sink.pending = key
-                else:
-                    d_up = torch.empty((N, r), dtype=torch.float32, device=g2.device)
-                    d_down = torch.empty((r, K), dtype=torch.float32, device=g2.device)
-                    rows = [(up_part, d_up, plan.nparts_up, plan.rank_tile, N, r, _C.FACTOR_KR, 1.0, 0.0),
-                            (down_part, d_down, plan.nparts_down, plan.rank_tile, K, r, _C.FACTOR_RK, 1.0, 0.0)]
-                    table, nn_, total = _C.make_reduce_table(rows, g2.device)
-                    _C.reduce_batched(table, nn_, total)
-                    d_up, d_down = d_up.to(up.dtype), d_down.to(down.dtype)
+                d_down, d_up = _finish(sink, site, w, down, up)
                 if need_w:
                     dw = g2.t() @ x2
                 if has_bias and need_b:
@@ -1454,8 +1412,7 @@ class LoraConvFunction(torch.autograd.Function):
         if not y.is_contiguous():
             y = y.contiguous()
         plan = _C.conv_plan(B, Ci, Co, H, W, ks, r)
-        key = ("conv", B, Ci, Co, H, W, ks, r)
-        t_part = sink.conv_workspace(key, plan, x.device)[0] if sink is not None else \
+        t_part = sink.lookup(*_conv_site(plan, B, Ci, Co, H, W, ks, r, x.device))[0] if sink is not None else \
             torch.empty(max(int(plan.t_part_floats), 1), dtype=torch.float32, device=x.device)
         t = torch.empty((B, r, H, W), dtype=torch.float32, device=x.device)
         down_c, up_c = down.float().contiguous(), up.float().contiguous()  # f32 masters: no-ops in training
@@ -1479,16 +1436,8 @@ class LoraConvFunction(torch.autograd.Function):
         pad = (ks - 1) // 2
         need_x, need_w, need_b, need_down, need_up = ctx.needs_input_grad[:5]
         g = g.contiguous()
-        plan = _C.conv_plan(B, Ci, Co, H, W, ks, r)
-        key = ("conv", B, Ci, Co, H, W, ks, r)
-        sink = ctx.sink
-        if sink is not None:
-            if sink.pending is not None:
-                sink.flush()
-            bufs = sink.conv_workspace(key, plan, g.device)
-        else:
-            bufs = conv_buffers(plan, B, r, H * W, g.device)
-        _, gt_part, gt, up_part, down_part = bufs
+        site = _conv_site(_C.conv_plan(B, Ci, Co, H, W, ks, r), B, Ci, Co, H, W, ks, r, g.device)
+        _, gt_part, gt, up_part, down_part = bufs = _begin(ctx.sink, site)
         down_c, up_c = down.float().contiguous(), up.float().contiguous()
         _C.conv_bwd_g(g, t, up_c, sel, gt_part, gt, up_part, ctx.scale, ctx.p, ctx.seed, ctx.off)
         dx = None
@@ -1498,16 +1447,7 @@ class LoraConvFunction(torch.autograd.Function):
             if not dx.is_contiguous():
                 dx = dx.contiguous()
         _C.conv_bwd_x(x, dx, gt, down_c, down_part, ks)
-        d_down = d_up = None
-        if sink is not None:
-            sink.pending = key
-        else:
-            d_up = torch.empty(up.shape, dtype=torch.float32, device=g.device)
-            d_down = torch.empty(down.shape, dtype=torch.float32, device=g.device)
-            table, n, total = _C.make_reduce_table(conv_reduce_rows(bufs, plan, Ci, Co, ks, r, d_up, d_down, 0.0),
-                                                   g.device)
-            _C.reduce_batched(table, n, total)
-            d_up, d_down = d_up.to(up.dtype), d_down.to(down.dtype)
+        d_down, d_up = _finish(ctx.sink, site, bufs, down, up)
         dw = db = None
         if need_w:
             dw = torch.ops.aten.convolution_backward(g, x, weight, None, [1, 1], [pad, pad], [1, 1], False, [0, 0], 1,
@@ -1690,15 +1630,10 @@ class LoraConv3NhwcFunction(torch.autograd.Function):
         g2 = g.permute(0, 2, 3, 1).view(M, Co)
         cplan = _C.conv3_nhwc_plan(B, Ci, H, W, r)
         lplan = _C.linear_plan(M, Ci, Co, r)
-        key = ("conv3n", B, Ci, Co, H, W, r)
         sink = ctx.sink
-        if sink is not None:
-            if sink.pending is not None:
-                sink.flush()
-            bufs = sink.conv3_nhwc_workspace(key, lplan, cplan, g.device)
-        else:
-            bufs = conv3_nhwc_buffers(lplan, cplan, M, r, g.device)
-        gt_part, up_part, gt_buf, down_part = bufs
+        site = (("conv3n", B, Ci, Co, H, W, r), lambda: conv3_nhwc_buffers(lplan, cplan, M, r, g.device),
+                lambda w, ug, dg, beta: conv3_nhwc_reduce_rows(w, lplan, cplan, Ci, Co, r, ug, dg, beta))
+        gt_part, up_part, gt_buf, down_part = bufs = _begin(sink, site)
         up2 = up.reshape(Co, r).float().contiguous()
         s, p, seed, off = ctx.scale, ctx.p, ctx.seed, ctx.off
         fused_g = bool(lplan.fused) and _C._rows_ok(g2)
@@ -1725,23 +1660,20 @@ class LoraConv3NhwcFunction(torch.autograd.Function):
             _C.conv3_nhwc_bwd_dx_(dx, gt, pd)
         _C.conv3_nhwc_bwd_down(x, gt, down_part)
         d_down = d_up = None
-        if sink is not None and fused_g:
-            sink.pending = key  # both partial sets are folded by the trainer's batched reduce
+        if d_up_direct is None:
+            d_down, d_up = _finish(sink, site, bufs, down, up)
         else:
+            # dUp came whole from the primitives: it is added to the sink's gradient (or returned), and only the dDown
+            # partials are folded — now, with beta 1 into the sink or beta 0 into a fresh tensor; nothing stays pending
             to_sink = sink is not None
-            up_t = sink.up_grad if to_sink else torch.empty(up.shape, dtype=torch.float32, device=g.device)
             down_t = sink.down_grad if to_sink else torch.empty(down.shape, dtype=torch.float32, device=g.device)
-            rows = conv3_nhwc_reduce_rows(bufs, lplan, cplan, Ci, Co, r, up_t, down_t, 1.0 if to_sink else 0.0)
-            if d_up_direct is not None:
-                rows = rows[1:]
-                if to_sink:
-                    up_t.add_(d_up_direct.view_as(up_t))
-                else:
-                    up_t = d_up_direct.view(up.shape)
+            rows = conv3_nhwc_reduce_rows(bufs, lplan, cplan, Ci, Co, r, None, down_t, 1.0 if to_sink else 0.0)[1:]
+            if to_sink:
+                sink.up_grad.add_(d_up_direct.view_as(sink.up_grad))
             table, n, total = _C.make_reduce_table(rows, g.device)
             _C.reduce_batched(table, n, total)
             if not to_sink:
-                d_up, d_down = up_t.to(up.dtype), down_t.to(down.dtype)
+                d_up, d_down = d_up_direct.view(up.shape).to(up.dtype), down_t.to(down.dtype)
         dw = db = None
         if need_w:
             dw = torch.ops.aten.convolution_backward(g, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,

@@ -182,3 +182,84 @@ def test_dropout_site_forward_heads_with_and_without_the_copies(in_heads, out_he
         assert float(_pads(y1, out_heads).float().abs().max()) == 0.0
     if in_heads:
         assert float(_pads(dx1, in_heads).float().abs().max()) == 0.0
+
+
+def _close(got, want, absref, dt, k, msg):
+    """``close`` after printing the worst |got - want| / tolerance of the array (the figure a reader of a failure wants)."""
+    from tests.test_gpu_kernels import EPS
+    tol = k * np.asarray(absref, np.float64) + EPS[dt] * np.abs(np.asarray(want, np.float64)) + 1e-30
+    print(f"{msg}: worst |err| / tol = {float((np.abs(np.asarray(got, np.float64) - want) / tol).max()):.3g}")
+    close(got, want, absref, dt, k=k, msg=msg)
+
+
+def test_dropout_site_in_head_padded_rows_without_a_trainer_state(monkeypatch):
+    """LoraInjectedLinear.forward_heads (dropout 0.1, rank 16) with NO FlatLoraState: the forward still runs in head-padded
+    rows, but nothing can defer the factor gradients, so the backward detours through dense copies and the regular backward.
+    Against the ops.WS_HEADS = False twin (copies around the dense forward) on the same seed stream: y, dx and both
+    factors' .grad are the same bits — equality, not a tolerance: the backward that impersonated an autograd context for
+    this detour gave equality on all four too."""
+    M, K, N, r, out_heads = 2304, 320, 320, 16, (8, 40, 64)
+
+    def run(flag):
+        monkeypatch.setattr(ops, "WS_HEADS", flag)
+        torch.manual_seed(0)
+        m = L.LoraInjectedLinear(K, N, False, r=r, dropout_p=0.1, scale=1.0).to(DEV).to(torch.bfloat16)
+        m.linear.requires_grad_(False)
+        T.promote_lora_to_fp32(m)
+        m.lora_up.weight.data.normal_(0, 0.05)
+        m.train()
+        x, gy = rnd((M, K), "bf16", seed=5), rnd((M, N), "bf16", seed=6)
+        xd = x.clone().requires_grad_(True)
+        log = []
+        monkeypatch.setattr(ops, "PATH_LOG", log)
+        with ops.dropout_pool(DEV):
+            torch.manual_seed(99)   # the dropout stream of both runs
+            y = m.forward_heads(xd, None, out_heads)
+            y.backward(_pack(gy, out_heads, 0.0))
+        return (y.detach().clone(), xd.grad.clone(), m.lora_down.weight.grad.clone(), m.lora_up.weight.grad.clone(),
+                [(e[0], e[1]) for e in log])
+
+    y1, dx1, dd1, du1, paths1 = run(True)
+    y0, dx0, dd0, du0, paths0 = run(False)
+    print("paths", paths1, paths0)
+    assert paths1[0] == ("fwd", "ws_heads") and paths1[1][0] == "bwd", paths1
+    assert "heads" not in paths1[1][1] and "deferred" not in paths1[1][1], paths1   # the dense detour
+    assert not any("heads" in p_ for _, p_ in paths0), paths0
+    for name, a, b in (("y", y1, y0), ("dx", dx1, dx0), ("d_down", dd1, dd0), ("d_up", du1, du0)):
+        print(name, "equal" if torch.equal(a, b) else f"max |diff| {float((a.float() - b.float()).abs().max()):.3e}")
+        assert float(a.float().abs().max()) > 0 and torch.equal(a, b), name
+    assert float(_pads(y1, out_heads).float().abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("in_heads,out_heads", [(None, (8, 40, 64)), ((8, 40, 64), None)])
+def test_maskless_ring_site_in_head_padded_rows_fused_and_detoured(in_heads, out_heads, monkeypatch):
+    """ops.lora_linear without dropout at the smallest M (4096) that routes a 320 x 320 rank-4 site into
+    LoraLinearHeadsFunction: its backward as it is (fused, head-padded) and with LORA_AMD_GEMM_BWD=0, which leaves no fused
+    tile and forces the dense detour — both against oracle.lora_linear_backward on the unpacked tensors; the pad columns of
+    a head-padded dX are exactly zero."""
+    M, K, N, r, s_ = 4096, 320, 320, 4, 0.7
+    x, gy, w = rnd((M, K), "bf16", seed=31), rnd((M, N), "bf16", seed=32), rnd((N, K), "bf16", 0.05, seed=33)
+    down0, up0 = rnd((r, K), "f32", 0.2, seed=34), rnd((N, r), "f32", 0.3, seed=35)
+    G, X, W, A, U = n(gy), n(x), n(w), n(down0), n(up0)
+    dxo, ddo, duo, _, _ = O.lora_linear_backward(G, X, W, A, U, s_)
+    gto = s_ * np.abs(G) @ np.abs(U)
+    for env, want in ((None, "_heads_dx+factors"), ("0", "g+lib+x")):
+        if env is not None:
+            monkeypatch.setenv("LORA_AMD_GEMM_BWD", env)
+        log = []
+        monkeypatch.setattr(ops, "PATH_LOG", log)
+        xd = (_pack(x, in_heads, 0.0) if in_heads else x).clone().requires_grad_(True)
+        down, up = down0.clone().requires_grad_(True), up0.clone().requires_grad_(True)
+        y = ops.lora_linear(xd, w, None, down, up, None, s_, 0.0, None, in_heads, out_heads)
+        y.backward(_pack(gy, out_heads, 0.0) if out_heads else gy)
+        paths = [(e[0], e[1]) for e in log]
+        print("paths", env, paths)
+        assert paths[0][0] == "fwd" and paths[0][1].startswith("ring") and paths[0][1].endswith("_heads"), paths
+        assert paths[1][0] == "bwd" and paths[1][1].endswith(want), paths
+        dx = xd.grad
+        if in_heads:
+            assert float(_pads(dx, in_heads).float().abs().max()) == 0.0
+            dx = _unpack(dx, in_heads)
+        _close(n(dx), dxo, np.abs(G) @ np.abs(W) + np.abs(s_ * G @ U) @ np.abs(A), "bf16", 2.0, f"dX[{want}]")
+        _close(n(up.grad), duo, s_ * (np.abs(G).T @ (np.abs(X) @ np.abs(A).T)), "f32", 1e-4, f"dUp[{want}]")
+        _close(n(down.grad), ddo, gto.T @ np.abs(X), "f32", 1e-4, f"dDown[{want}]")
