@@ -925,6 +925,34 @@ int lora_amd_geglu_fwd(const void *y, int64_t ldy, void *out, int64_t ldo, int64
 int lora_amd_geglu_bwd(const void *y, int64_t ldy, const void *gout, int64_t ldg, void *gy, int64_t ldgy, int64_t M,
                        int32_t inner, int32_t dtype, void *stream);
 
+/* Backward of o = softmax(scale q k^T) v for a SHORT key axis (the 77 text tokens of the cross-attention layers): the
+ * whole key axis is one tile, the softmax is recomputed from q and k (no log-sum-exp, no saved output).  Operands are
+ * [B, H, S, D] views described by their (batch, head, row) strides in elements (`*_strides_host`, three values each) with a
+ * dense last dimension: contiguous [B, H, S, D] memory and the transposed view of [B, S, H, D] memory alike.  bf16,
+ * 1 <= Sk <= 80, D in {64, 80, 96, 128, 160}, any Sq; every pointer 16-byte aligned and every stride a multiple of 8.
+ * dq / dk / dv have the shapes of q / k / v; dk and dv may both be NULL (no key / value gradient wanted: their products,
+ * the workspace and the second launch are skipped).  Two launches: the main kernel writes dq and one f32 slab of dk / dv
+ * partials per workgroup into `workspace`, the fold sums a (batch, head)'s slabs in slab order — no atomics, the same
+ * bits on every run.  Nothing at or past row Sk of k / v or row Sq of q / dout is read. */
+typedef struct lora_amd_attn_short_plan {
+  int32_t run_blocks;      /* consecutive 64-query blocks one workgroup walks                 */
+  int32_t slabs;           /* workgroups (= partial slabs) per (batch, head)                  */
+  int64_t slab_bytes;      /* one slab: [dk | dv][80][D] f32                                  */
+  int64_t workspace_bytes; /* B * H * slabs * slab_bytes                                      */
+} lora_amd_attn_short_plan;
+/* Pure host: 1 if the kernel takes the problem.  `strides_host[0..n_strides)`: every stride of every operand. */
+int lora_amd_attn_short_bwd_supported(int64_t Sq, int32_t Sk, int32_t D, int32_t dtype, const int64_t *strides_host,
+                                      int32_t n_strides);
+/* Pure host: the run length, the slab count and the workspace size of a supported problem. */
+int lora_amd_attn_short_bwd_plan(int32_t B, int32_t H, int64_t Sq, int32_t Sk, int32_t D,
+                                 lora_amd_attn_short_plan *plan_host);
+int lora_amd_attn_short_bwd(const void *q, const int64_t *q_strides_host, const void *k,
+                            const int64_t *k_strides_host, const void *v, const int64_t *v_strides_host,
+                            const void *dout, const int64_t *dout_strides_host, void *dq,
+                            const int64_t *dq_strides_host, void *dk, const int64_t *dk_strides_host, void *dv,
+                            const int64_t *dv_strides_host, int32_t B, int32_t H, int64_t Sq, int32_t Sk, int32_t D,
+                            float scale, int32_t dtype, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,11 +59,18 @@ SYMBOLS = (
     "lora_amd_groupnorm_nhwc_workspace", "lora_amd_groupnorm_nhwc_fwd", "lora_amd_groupnorm_nhwc_bwd",
     "lora_amd_add_layernorm_fwd", "lora_amd_add_layernorm_bwd",
     "lora_amd_linear_gemm_fwd_rowscale", "lora_amd_rank_update_rowscale", "lora_amd_conv_up_fwd_rowscale",
+    "lora_amd_attn_short_bwd_supported", "lora_amd_attn_short_bwd_plan", "lora_amd_attn_short_bwd",
 )
 
 
 class HipExtensionMissing(RuntimeError):
     pass
+
+
+class AttnShortPlan(C.Structure):
+    """lora_amd_attn_short_plan (include/lora_amd.h): run length, slab count and workspace of the short-key backward."""
+    _fields_ = [("run_blocks", C.c_int32), ("slabs", C.c_int32), ("slab_bytes", C.c_int64),
+                ("workspace_bytes", C.c_int64)]
 
 
 class FactorsSelfPlan(C.Structure):
@@ -410,6 +417,11 @@ def _declare(lib: C.CDLL) -> None:
     lib.lora_amd_layernorm_supported.argtypes = [i32]
     lib.lora_amd_layernorm_fwd.argtypes = [vp, vp, vp, vp, vp, i64, i32, f32, i32, vp]
     lib.lora_amd_layernorm_bwd.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp]
+    lib.lora_amd_attn_short_bwd_supported.argtypes = [i64, i32, i32, i32, vp, i32]
+    lib.lora_amd_attn_short_bwd_plan.argtypes = [i32, i32, i64, i32, i32, C.POINTER(AttnShortPlan)]
+    lib.lora_amd_attn_short_bwd.argtypes = [vp, vp] * 7 + [i32, i32, i64, i32, i32, f32, i32, vp, sz, vp]
+    for name in ("lora_amd_attn_short_bwd_supported", "lora_amd_attn_short_bwd_plan", "lora_amd_attn_short_bwd"):
+        getattr(lib, name).restype = C.c_int
     for name in ("lora_amd_groupnorm_supported", "lora_amd_groupnorm_fwd", "lora_amd_groupnorm_bwd",
                  "lora_amd_geglu_fwd", "lora_amd_geglu_bwd", "lora_amd_layernorm_supported",
                  "lora_amd_layernorm_fwd", "lora_amd_layernorm_bwd"):
@@ -2288,3 +2300,75 @@ def add_layernorm_bwd(s: torch.Tensor, gout: torch.Tensor, gsum: Optional[torch.
                                                 stats.data_ptr(), dx.data_ptr(), s.numel() // K, K,
                                                 dtype_code(s.dtype), _stream()), "lora_amd_add_layernorm_bwd")
     return dx
+
+
+# ----------------------------------------------------------------------------- short-key attention backward (attn_short.hip)
+def _bhs_strides(t: torch.Tensor):
+    """(batch, head, row) strides of a [B, H, S, D] view as the C array the launcher reads."""
+    return (C.c_int64 * 3)(t.stride(0), t.stride(1), t.stride(2))
+
+
+def attn_short_bwd_supported(Sq: int, Sk: int, D: int, dtype: torch.dtype, *tensors: torch.Tensor) -> bool:
+    """Pure host: does the short-key backward take this problem?  ``tensors``: the [B, H, S, D] operands whose layout is
+    already known (dense last dimension, 16-byte aligned rows and base)."""
+    code = _DT.get(dtype)
+    if code is None:
+        return False
+    strides = []
+    for t in tensors:
+        if t.dim() != 4 or t.stride(3) != 1 or t.data_ptr() % 16 != 0:
+            return False
+        strides += [t.stride(0), t.stride(1), t.stride(2)]
+    arr = (C.c_int64 * max(1, len(strides)))(*strides)
+    return bool(require().lora_amd_attn_short_bwd_supported(Sq, Sk, D, code, arr, len(strides)))
+
+
+_attn_short_plans: Dict[Tuple[int, int, int, int, int], Tuple[int, int, int, int]] = {}
+
+
+def attn_short_bwd_plan(B: int, H: int, Sq: int, Sk: int, D: int) -> Tuple[int, int, int, int]:
+    """Pure host: (run_blocks, slabs per (batch, head), slab_bytes, workspace_bytes)."""
+    key = (B, H, Sq, Sk, D)
+    got = _attn_short_plans.get(key)
+    if got is None:
+        plan = AttnShortPlan()
+        _check(require().lora_amd_attn_short_bwd_plan(B, H, Sq, Sk, D, C.byref(plan)), "lora_amd_attn_short_bwd_plan")
+        got = _attn_short_plans[key] = (plan.run_blocks, plan.slabs, plan.slab_bytes, plan.workspace_bytes)
+    return got
+
+
+def attn_short_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dout: torch.Tensor, scale: float, *,
+                   need_kv: bool = True, dq: Optional[torch.Tensor] = None, dk: Optional[torch.Tensor] = None,
+                   dv: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """(dq, dk, dv) of softmax(scale q k^T) v given dout, for [B, H, S, D] views with at most 80 keys; dk = dv = None when
+    ``need_kv`` is false.  Outputs take the layout of q / k / v unless given; ``workspace``: a uint8 / f32 device tensor of
+    at least ``attn_short_bwd_plan(...)[3]`` bytes (allocated here when missing)."""
+    _dev_check(q, k, v, dout, dq, dk, dv, workspace)
+    B, H, Sq, D = q.shape
+    Sk = k.shape[2]
+    if k.shape != (B, H, Sk, D) or v.shape != k.shape or dout.shape != q.shape:
+        raise ValueError(f"attn_short_bwd: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)}, "
+                         f"dout {tuple(dout.shape)}")
+    dq = torch.empty_like(q) if dq is None else dq
+    if need_kv:
+        dk = torch.empty_like(k) if dk is None else dk
+        dv = torch.empty_like(v) if dv is None else dv
+    else:
+        dk = dv = None
+    ops_ = [q, k, v, dout, dq] + ([dk, dv] if need_kv else [])
+    if any(t.dtype != q.dtype for t in ops_) or not attn_short_bwd_supported(Sq, Sk, D, q.dtype, *ops_):
+        raise ValueError(f"attn_short_bwd: unsupported problem (Sq {Sq}, Sk {Sk}, D {D}, {q.dtype}, strides "
+                         f"{[tuple(t.stride()) for t in ops_]})")
+    ws_bytes = attn_short_bwd_plan(B, H, Sq, Sk, D)[3]
+    if need_kv:
+        if workspace is None:
+            workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+        have = workspace.numel() * workspace.element_size()
+    else:
+        have = 0
+    st = [_bhs_strides(t) for t in ops_]
+    _check(require().lora_amd_attn_short_bwd(
+        q.data_ptr(), st[0], k.data_ptr(), st[1], v.data_ptr(), st[2], dout.data_ptr(), st[3], dq.data_ptr(), st[4],
+        _ptr(dk), st[5] if need_kv else None, _ptr(dv), st[6] if need_kv else None, B, H, Sq, Sk, D, float(scale),
+        dtype_code(q.dtype), _ptr(workspace) if need_kv else None, have, _stream()), "lora_amd_attn_short_bwd")
+    return dq, dk, dv

@@ -574,13 +574,17 @@ CONV3_FUSED = True
 # 16-bit shadow of it (round16(round16(W32) + scale up down)); False = the shadow-then-merge route
 # (tests/test_gpu_master_policy.py runs both)
 MASTER_MERGE = True
+# backward of the text cross-attention layers (at most 80 keys) on the native one-tile kernel (csrc/attn_short.hip; the forward
+# stays on the library kernel standin/attention.py picks); False = the library's backward
+# (tests/test_attn_short_route.py runs both)
+ATTN_SHORT_BWD = True
 
 
 def apply_ab_overrides(spec: str, namespace: dict) -> dict:
     """``LORA_AMD_AB="NAME=0,OTHER=1"``: the ONE measurement switch for same-box A/B runs — flips the module constants
     listed in ``allowed`` (and only those) without a code edit; every A/B log under profiles/ names the spec it ran with
     (a constant retired since then is an unknown name here)."""
-    allowed = ("CONCAT_GROUPS", "CONV3_FUSED", "MASTER_MERGE", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
+    allowed = ("ATTN_SHORT_BWD", "CONCAT_GROUPS", "CONV3_FUSED", "MASTER_MERGE", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
                "WS_DROPOUT_WIDE_BWD")
     done = {}
     for item in filter(None, (s.strip() for s in spec.split(","))):

@@ -22,6 +22,7 @@ try:
 except ImportError:  # pragma: no cover
     SDPBackend = sdpa_kernel = None
 
+from .. import _C  # noqa: E402
 from .._C import _TuneCache  # noqa: E402  (shared JSON cache of per-shape choices, LORA_AMD_TUNE_CACHE)
 
 _CHOICE = _TuneCache("sdpa")
@@ -33,6 +34,59 @@ def _padded(d: int) -> int:
     return 64 if d <= 64 else 128 if d <= 128 else 256 if d <= 256 else d
 
 
+def _library(q, k, v, scale: float, backend: Optional[str]):
+    if backend is None or sdpa_kernel is None or not q.is_cuda:
+        return F.scaled_dot_product_attention(q, k, v, scale=scale)
+    with sdpa_kernel(getattr(SDPBackend, backend)):
+        return F.scaled_dot_product_attention(q, k, v, scale=scale)
+
+
+class _ShortKeyBackward(torch.autograd.Function):
+    """The library's forward (the very call :func:`_library` makes, so the output bits do not change) with the backward of
+    ``csrc/attn_short.hip``: at most 80 keys are one tile, the softmax is recomputed from q and k, nothing of the forward
+    but q, k, v is kept."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, scale, backend):
+        with torch.no_grad():
+            o = _library(q, k, v, scale, backend)
+        ctx.save_for_backward(q, k, v)
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        q, k, v = ctx.saved_tensors
+        if go.stride(-1) != 1 or any(s % 8 for s in go.stride()[:3]) or go.data_ptr() % 16:
+            go = go.contiguous()
+        need_kv = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        dq, dk, dv = _C.attn_short_bwd(q, k, v, go, ctx.scale, need_kv=need_kv)
+        return (dq if ctx.needs_input_grad[0] else None, dk if ctx.needs_input_grad[1] else None,
+                dv if ctx.needs_input_grad[2] else None, None, None)
+
+
+ROUTES = {"native_bwd": 0, "library": 0}  # attention cores run since import, by the backward they were given
+
+
+def _short_bwd_eligible(q, k, v) -> bool:
+    from .. import ops
+
+    return (ops.ATTN_SHORT_BWD and q.is_cuda and _C.available() and torch.is_grad_enabled()
+            and (q.requires_grad or k.requires_grad or v.requires_grad)
+            and q.dim() == 4 and q.dtype == k.dtype == v.dtype and k.shape == v.shape and k.shape[-1] == q.shape[-1]
+            and _C.attn_short_bwd_supported(q.shape[2], k.shape[2], q.shape[3], q.dtype, q, k, v))
+
+
+def _core(q, k, v, scale: float, backend: Optional[str]):
+    """softmax(scale q k^T) v on the chosen library kernel; a problem the short-key kernel takes gets its backward from it."""
+    if _short_bwd_eligible(q, k, v):
+        ROUTES["native_bwd"] += 1
+        return _ShortKeyBackward.apply(q, k, v, scale, backend)
+    ROUTES["library"] += 1
+    return _library(q, k, v, scale, backend)
+
+
 def _run(q, k, v, backend: Optional[str], pad_to: int, pad_v: bool = True):
     """``pad_to`` > d zero-pads the head dimension of q and k (and of v when ``pad_v``; with v left as is the output
     comes back unpadded — one pad and one slice copy fewer each way — where the kernel accepts Dv != Dk)."""
@@ -42,11 +96,7 @@ def _run(q, k, v, backend: Optional[str], pad_to: int, pad_v: bool = True):
         q, k = F.pad(q, (0, pad_to - d)), F.pad(k, (0, pad_to - d))
         if pad_v:
             v = F.pad(v, (0, pad_to - d))
-    if backend is None or sdpa_kernel is None:
-        o = F.scaled_dot_product_attention(q, k, v, scale=scale)
-    else:
-        with sdpa_kernel(getattr(SDPBackend, backend)):
-            o = F.scaled_dot_product_attention(q, k, v, scale=scale)
+    o = _core(q, k, v, scale, backend)
     return o[..., :d] if (pad_to > d and pad_v) else o
 
 
@@ -136,11 +186,7 @@ def padded_choice(B: int, H: int, Sq: int, Sk: int, d: int, dtype, grad: bool):
 def sdpa_padded(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, d: int, backend: Optional[str]) -> torch.Tensor:
     """The attention core on tensors that already carry the padded head size (pad columns zero); ``d`` is the true
     head size (softmax scale)."""
-    scale = d ** -0.5
-    if backend is None or sdpa_kernel is None or not q.is_cuda:
-        return F.scaled_dot_product_attention(q, k, v, scale=scale)
-    with sdpa_kernel(getattr(SDPBackend, backend)):
-        return F.scaled_dot_product_attention(q, k, v, scale=scale)
+    return _core(q, k, v, d ** -0.5, backend)
 
 
 def choices():

@@ -741,6 +741,55 @@ def bench_hostops(args):
              lambda: (aten, lambda: aten().backward(go)), 3 * e, 5 * e)
 
 
+def bench_attn(args):
+    """Backward of the step's four text cross-attention shapes (B 4, H 8, 77 keys): csrc/attn_short.hip against the library
+    backward of the kernel the step picks, both graph-timed on the step's layouts, next to the algorithmic bytes
+    (Q + dO + dQ, K, V, dK, dV)."""
+    from lora_amd import ops
+    from lora_amd.standin import attention
+
+    B, H, Sk = 4, 8, 77
+    for Sq, D, d, backend in ((4096, 64, 40, "EFFICIENT_ATTENTION"), (1024, 80, 80, None), (256, 160, 160, None),
+                              (64, 160, 160, None)):
+        def mk(S):
+            if d < D:   # the head-padded copy F.pad makes: contiguous [B, H, S, D], pad columns zero
+                t = torch.randn(B, H, S, D, device=DEV, dtype=torch.bfloat16)
+                t[..., d:] = 0
+                return t
+            return torch.randn(B, S, H, D, device=DEV, dtype=torch.bfloat16).transpose(1, 2)   # the projections' rows
+        q, k, v, go = mk(Sq), mk(Sk), mk(Sk), mk(Sq)
+        scale = d ** -0.5
+        ql, kl, vl = (t.detach().requires_grad_(True) for t in (q, k, v))
+        ws = torch.empty(_C.attn_short_bwd_plan(B, H, Sq, Sk, D)[3], dtype=torch.uint8, device=DEV)
+        outs = [torch.empty_like(t) for t in (q, k, v)]
+        nbytes = 2 * D * B * H * (3 * Sq + 4 * Sk)
+        res = {"Sq": Sq, "Sk": Sk, "D": D, "plan": list(_C.attn_short_bwd_plan(B, H, Sq, Sk, D)), "bytes": nbytes}
+
+        # forward and backward are captured TOGETHER (as the step does): a backward whose forward ran outside the capture
+        # would be issued on the forward's stream, which is not the capturing one
+        def fwd():
+            with torch.no_grad():
+                attention._library(ql, kl, vl, scale, backend)
+
+        def fwd_bwd(on):
+            def run():
+                ops.ATTN_SHORT_BWD = on
+                attention._core(ql, kl, vl, scale, backend).backward(go)
+            return run
+
+        res["library_fwd_us"] = timeit(fwd, args.iters)[0] * 1e6
+        res["library_fwd_bwd_us"] = timeit(fwd_bwd(False), args.iters)[0] * 1e6
+        res["native_fwd_bwd_us"] = timeit(fwd_bwd(True), args.iters)[0] * 1e6
+        ops.ATTN_SHORT_BWD = True
+        res["library_bwd_us"] = res["library_fwd_bwd_us"] - res["library_fwd_us"]
+        res["native_bwd_us"] = timeit(lambda: _C.attn_short_bwd(q, k, v, go, scale, dq=outs[0], dk=outs[1], dv=outs[2],
+                                                                 workspace=ws), args.iters)[0] * 1e6
+        res["native_dq_only_us"] = timeit(lambda: _C.attn_short_bwd(q, k, v, go, scale, need_kv=False, dq=outs[0]),
+                                          args.iters)[0] * 1e6
+        res["native_x_byte_roof"] = res["native_bwd_us"] / (nbytes / 6.3e6)   # 6.3 TB/s: the copy ceiling
+        print(json.dumps({k_: (round(v_, 2) if isinstance(v_, float) else v_) for k_, v_ in res.items()}), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="merge,linear,ws,conv,hostops")
@@ -774,3 +823,5 @@ if __name__ == "__main__":
         bench_fmtrace(a)
     if "gemmlayout" in a.what:
         bench_gemm_layouts(a)
+    if "attn" in a.what.split(","):
+        bench_attn(a)
