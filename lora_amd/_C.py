@@ -24,62 +24,29 @@ ABI_VERSION = 7
 
 _DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 
-# every symbol include/lora_amd.h declares (tests check the .so exports them all)
-SYMBOLS = (
-    "lora_amd_abi_version", "lora_amd_last_error", "lora_amd_target_arch",
-    "lora_amd_merge_plan", "lora_amd_merge_batched", "lora_amd_merge_set_tuning", "lora_amd_merge_step_set_tuning", "lora_amd_rank16_mfma", "lora_amd_factors_mfma_set_tuning",
-    "lora_amd_merge_step_plan", "lora_amd_merge_step",
-    "lora_amd_rowdot", "lora_amd_rowdot_masked", "lora_amd_rank_update",
-    "lora_amd_colreduce_workspace", "lora_amd_colreduce",
-    "lora_amd_rowdot_batched", "lora_amd_colreduce_batched", "lora_amd_chol_inverse_batched",
-    "lora_amd_ragged_plan", "lora_amd_rowdot_ragged", "lora_amd_colreduce_ragged", "lora_amd_sub_ragged",
-    "lora_amd_rowdot16_planes_plan", "lora_amd_rowdot16_planes", "lora_amd_rowdot16_planes_packed", "lora_amd_thin_pack",
-    "lora_amd_split16_ragged", "lora_amd_split16_transpose",
-    "lora_amd_split16_residual", "lora_amd_thin_gram", "lora_amd_thin_apply", "lora_amd_thin_rotate", "lora_amd_thin_select", "lora_amd_thin_clamp",
-    "lora_amd_linear_plan", "lora_amd_linear_fwd", "lora_amd_linear_bwd_g", "lora_amd_linear_bwd_x",
-    "lora_amd_linear_bwd_factors", "lora_amd_linear_bwd_factors_drop", "lora_amd_linear_bwd_factors_heads",
-    "lora_amd_linear_factors_self_plan", "lora_amd_linear_factors_self_plan_rows", "lora_amd_linear_bwd_factors_self",
-    "lora_amd_linear_factors_self_ragged_plan", "lora_amd_linear_bwd_factors_self_ragged",
-    "lora_amd_factors_mfma_plan", "lora_amd_factor_pack_plan", "lora_amd_factor_pack",
-    "lora_amd_factors_mfma_ragged_plan", "lora_amd_linear_bwd_factors_mfma_ragged", "lora_amd_factors_mfma_block_map",
-    "lora_amd_linear_bwd_factors_mfma_ragged_mapped",
-    "lora_amd_linear_gemm_fwd_heads",
-    "lora_amd_reduce_batched", "lora_amd_linear_gemm_supported", "lora_amd_linear_gemm_fwd",
-    "lora_amd_ws_config", "lora_amd_ws_packed_elems", "lora_amd_ws_pack", "lora_amd_linear_ws", "lora_amd_linear_ws_heads",
-    "lora_amd_conv_plan", "lora_amd_conv_down_fwd", "lora_amd_conv_up_fwd", "lora_amd_conv_bwd_g", "lora_amd_conv_bwd_x",
-    "lora_amd_conv3_nhwc_plan", "lora_amd_conv3_nhwc_pack", "lora_amd_conv3_nhwc_down_fwd", "lora_amd_conv3_nhwc_bwd_dx",
-    "lora_amd_conv3_nhwc_bwd_down", "lora_amd_sum_parts",
-    "lora_amd_conv3_nhwc_pack_plan", "lora_amd_conv3_nhwc_pack_batched", "lora_amd_conv3_nhwc_fwd_fused",
-    "lora_amd_linear_bwd_g_blocks", "lora_amd_linear_bwd_g_folded",
-    "lora_amd_sumsq_workspace", "lora_amd_sumsq", "lora_amd_clip_adamw", "lora_amd_clip_adamw_dev",
-    "lora_amd_step_advance", "lora_amd_loss_scale_update", "lora_amd_ti_rows_step",
-    "lora_amd_groupnorm_workspace", "lora_amd_groupnorm_supported", "lora_amd_groupnorm_fwd", "lora_amd_groupnorm_bwd",
-    "lora_amd_geglu_fwd", "lora_amd_geglu_bwd",
-    "lora_amd_layernorm_supported", "lora_amd_layernorm_fwd", "lora_amd_layernorm_bwd",
-    "lora_amd_groupnorm_nhwc_workspace", "lora_amd_groupnorm_nhwc_fwd", "lora_amd_groupnorm_nhwc_bwd",
-    "lora_amd_add_layernorm_fwd", "lora_amd_add_layernorm_bwd",
-    "lora_amd_linear_gemm_fwd_rowscale", "lora_amd_rank_update_rowscale", "lora_amd_conv_up_fwd_rowscale",
-    "lora_amd_attn_short_bwd_supported", "lora_amd_attn_short_bwd_plan", "lora_amd_attn_short_bwd",
-)
-
-
 class HipExtensionMissing(RuntimeError):
     pass
 
 
 class AttnShortPlan(C.Structure):
     """lora_amd_attn_short_plan (include/lora_amd.h): run length, slab count and workspace of the short-key backward."""
+    c_struct = "lora_amd_attn_short_plan"
+    __slots__ = ()
     _fields_ = [("run_blocks", C.c_int32), ("slabs", C.c_int32), ("slab_bytes", C.c_int64),
                 ("workspace_bytes", C.c_int64)]
 
 
 class FactorsSelfPlan(C.Structure):
+    c_struct = "lora_amd_factors_self_plan_t"
+    __slots__ = ()
     _fields_ = [("supported", C.c_int32), ("rank_tile", C.c_int32), ("nparts", C.c_int32), ("reserved", C.c_int32),
                 ("up_part_floats", C.c_int64), ("down_part_floats", C.c_int64)]
 
 
 class SelfSite(C.Structure):
     """lora_amd_self_site (include/lora_amd.h): one adapter of the one-launch factor-gradient pass."""
+    c_struct = "lora_amd_self_site"
+    __slots__ = ()
     _fields_ = [
         ("g", C.c_void_p), ("x", C.c_void_p), ("down", C.c_void_p), ("up", C.c_void_p),
         ("up_part", C.c_void_p), ("down_part", C.c_void_p),
@@ -95,6 +62,8 @@ class SelfSite(C.Structure):
 
 
 class FactorsMfmaPlan(C.Structure):
+    c_struct = "lora_amd_factors_mfma_plan_t"
+    __slots__ = ()
     _fields_ = [("supported", C.c_int32), ("lds_class", C.c_int32), ("rank_tile", C.c_int32),
                 ("rows_per_block", C.c_int32), ("nparts", C.c_int32), ("lds_bytes", C.c_int32),
                 ("blocks_per_wg", C.c_int32), ("reserved", C.c_int32),
@@ -104,12 +73,16 @@ class FactorsMfmaPlan(C.Structure):
 
 class PackSite(C.Structure):
     """lora_amd_pack_site: the f32 factors of one adapter -> MFMA fragment packs."""
+    c_struct = "lora_amd_pack_site"
+    __slots__ = ()
     _fields_ = [("down", C.c_void_p), ("up", C.c_void_p), ("pk_down", C.c_void_p), ("pk_up", C.c_void_p),
                 ("N", C.c_int32), ("K", C.c_int32), ("r", C.c_int32), ("reserved", C.c_int32), ("begin", C.c_int64)]
 
 
 class FmSite(C.Structure):
     """lora_amd_fm_site: one adapter of the matrix-core factor-gradient pass."""
+    c_struct = "lora_amd_fm_site"
+    __slots__ = ()
     _fields_ = [
         ("g", C.c_void_p), ("x", C.c_void_p), ("pk_up", C.c_void_p), ("pk_down", C.c_void_p),
         ("up_part", C.c_void_p), ("down_part", C.c_void_p),
@@ -127,6 +100,8 @@ class FmSite(C.Structure):
 
 class RaggedDesc(C.Structure):
     """lora_amd_ragged_desc (include/lora_amd.h): one stack of same-shape matrices of a ragged launch."""
+    c_struct = "lora_amd_ragged_desc"
+    __slots__ = ()
     _fields_ = [
         ("x", C.c_void_p), ("f", C.c_void_p), ("out", C.c_void_p), ("partial", C.c_void_p),
         ("ldx", C.c_int64), ("stride_x", C.c_int64), ("stride_f", C.c_int64), ("stride_out", C.c_int64), ("M", C.c_int64),
@@ -138,46 +113,64 @@ class RaggedDesc(C.Structure):
 
 
 class SubDesc(C.Structure):
+    c_struct = "lora_amd_sub_desc"
+    __slots__ = ()
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("out", C.c_void_p), ("n", C.c_int64), ("begin", C.c_int64)]
 
 
 class PlanesDesc(C.Structure):
+    c_struct = "lora_amd_planes_desc"
+    __slots__ = ()
     _fields_ = [("hi", C.c_void_p), ("lo", C.c_void_p), ("f", C.c_void_p), ("out", C.c_void_p), ("M", C.c_int64),
                 ("C", C.c_int32), ("batch", C.c_int32), ("wps", C.c_int32), ("slabs_per_wg", C.c_int32),
                 ("wg_begin", C.c_int64)]
 
 
 class SplitTDesc(C.Structure):
+    c_struct = "lora_amd_splitt_desc"
+    __slots__ = ()
     _fields_ = [("src", C.c_void_p), ("hi", C.c_void_p), ("lo", C.c_void_p), ("thi", C.c_void_p), ("tlo", C.c_void_p),
                 ("batch", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("reserved", C.c_int32), ("tile_begin", C.c_int64)]
 
 
 class ResidDesc(C.Structure):
+    c_struct = "lora_amd_resid_desc"
+    __slots__ = ()
     _fields_ = [("tuned", C.c_void_p), ("base", C.c_void_p), ("hi", C.c_void_p), ("lo", C.c_void_p), ("thi", C.c_void_p),
                 ("tlo", C.c_void_p), ("N", C.c_int32), ("K", C.c_int32), ("tile_begin", C.c_int64)]
 
 
 class ThinSite(C.Structure):
+    c_struct = "lora_amd_thin_site"
+    __slots__ = ()
     _fields_ = [("off", C.c_int64), ("rows", C.c_int64), ("block_begin", C.c_int64), ("blocks", C.c_int32),
                 ("reserved", C.c_int32)]
 
 
 class ThinQSite(C.Structure):
+    c_struct = "lora_amd_thin_qsite"
+    __slots__ = ()
     _fields_ = [("off_u", C.c_int64), ("off_v", C.c_int64), ("n_u", C.c_int64), ("n_v", C.c_int64),
                 ("block_begin", C.c_int64), ("blocks", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ThinFinishDesc(C.Structure):
+    c_struct = "lora_amd_thin_finish"
+    __slots__ = ()
     _fields_ = [("part", C.c_void_p), ("counters", C.c_void_p), ("mode", C.c_int32), ("shift_rel", C.c_float),
                 ("linv_out", C.c_void_p), ("ritz_out", C.c_void_p), ("ubt", C.c_void_p), ("vb", C.c_void_p),
                 ("s_out", C.c_void_p), ("rank", C.c_int32), ("reserved", C.c_int32)]
 
 
 class SplitDesc(C.Structure):
+    c_struct = "lora_amd_split_desc"
+    __slots__ = ()
     _fields_ = [("src", C.c_void_p), ("hi", C.c_void_p), ("lo", C.c_void_p), ("n", C.c_int64), ("begin", C.c_int64)]
 
 
 class MergeSite(C.Structure):
+    c_struct = "lora_amd_merge_site"
+    __slots__ = ()
     _fields_ = [
         ("w_in", C.c_void_p), ("w_out", C.c_void_p), ("up", C.c_void_p), ("down", C.c_void_p),
         ("N", C.c_int32), ("K", C.c_int32), ("r", C.c_int32),
@@ -189,6 +182,8 @@ class MergeSite(C.Structure):
 
 class MstepSite(C.Structure):
     """lora_amd_mstep_site (include/lora_amd.h): one adapter of the in-step merge (W_eff and W_eff^T from one read of W)."""
+    c_struct = "lora_amd_mstep_site"
+    __slots__ = ()
     _fields_ = [
         ("w", C.c_void_p), ("up", C.c_void_p), ("down", C.c_void_p), ("out", C.c_void_p), ("out_t", C.c_void_p),
         ("ld_out", C.c_int64), ("ld_out_t", C.c_int64),
@@ -200,20 +195,28 @@ class MstepSite(C.Structure):
 
 
 class MergeSummary(C.Structure):
+    c_struct = "lora_amd_merge_summary"
+    __slots__ = ()
     _fields_ = [("total_tiles", C.c_int64), ("n_fast_sites", C.c_int32), ("rank_tile_fast", C.c_int32)]
 
 
 class AdamWGroup(C.Structure):
+    c_struct = "lora_amd_adamw_group"
+    __slots__ = ()
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr", C.c_float), ("weight_decay", C.c_float)]
 
 
 class LinearPlan(C.Structure):
+    c_struct = "lora_amd_linear_plan_t"
+    __slots__ = ()
     _fields_ = [("fused", C.c_int32), ("rank_tile", C.c_int32), ("nct_g", C.c_int32), ("nparts_up", C.c_int32),
                 ("nparts_down", C.c_int32), ("reserved", C.c_int32), ("gt_part_floats", C.c_int64),
                 ("up_part_floats", C.c_int64), ("down_part_floats", C.c_int64)]
 
 
 class ConvPlan(C.Structure):
+    c_struct = "lora_amd_conv_plan_t"
+    __slots__ = ()
     _fields_ = [("native", C.c_int32), ("cpw_in", C.c_int32), ("ngroups_in", C.c_int32), ("ngroups_out", C.c_int32),
                 ("split_in", C.c_int32), ("split_out", C.c_int32), ("rank_pad", C.c_int32), ("reserved", C.c_int32),
                 ("t_part_floats", C.c_int64), ("gt_part_floats", C.c_int64), ("up_part_floats", C.c_int64),
@@ -221,6 +224,8 @@ class ConvPlan(C.Structure):
 
 
 class Conv3NhwcPlan(C.Structure):
+    c_struct = "lora_amd_conv3_nhwc_plan_t"
+    __slots__ = ()
     _fields_ = [("native", C.c_int32), ("pt", C.c_int32), ("ksplit", C.c_int32), ("csplit", C.c_int32),
                 ("ks", C.c_int32), ("pr", C.c_int32), ("nsplit", C.c_int32), ("rank_pad", C.c_int32),
                 ("fwd_tiles", C.c_int32), ("reserved", C.c_int32),
@@ -229,6 +234,8 @@ class Conv3NhwcPlan(C.Structure):
 
 
 class Conv3PackSite(C.Structure):
+    c_struct = "lora_amd_conv3_pack_site"
+    __slots__ = ()
     _fields_ = [("down", C.c_void_p), ("up", C.c_void_p), ("pf", C.c_void_p), ("pd", C.c_void_p), ("pu", C.c_void_p),
                 ("r", C.c_int32), ("C_in", C.c_int32), ("C_out", C.c_int32), ("KS", C.c_int32), ("begin", C.c_int64)]
 
@@ -237,6 +244,8 @@ WS_MAX_SITES = 4
 
 
 class WsSite(C.Structure):
+    c_struct = "lora_amd_ws_site"
+    __slots__ = ()
     _fields_ = [("wp", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("down", C.c_void_p), ("up", C.c_void_p),
                 ("t_out", C.c_void_p), ("ldy", C.c_int64), ("N", C.c_int32), ("r", C.c_int32),
                 ("panel_begin", C.c_int32), ("flayout", C.c_int32), ("scale", C.c_float), ("t_scale", C.c_float),
@@ -245,9 +254,148 @@ class WsSite(C.Structure):
 
 
 class ReduceDesc(C.Structure):
+    c_struct = "lora_amd_reduce_desc"
+    __slots__ = ()
     _fields_ = [("part", C.c_void_p), ("out", C.c_void_p), ("begin", C.c_int64), ("nparts", C.c_int32),
                 ("RT", C.c_int32), ("C", C.c_int32), ("r", C.c_int32), ("layout", C.c_int32),
                 ("reserved", C.c_int32), ("scale", C.c_float), ("beta", C.c_float)]
+
+
+# every struct of the header: c_struct names it; empty __slots__ make a write to a non-field an AttributeError
+MIRRORS = (AttnShortPlan, FactorsSelfPlan, SelfSite, FactorsMfmaPlan, PackSite, FmSite, RaggedDesc, SubDesc,
+           PlanesDesc, SplitTDesc, ResidDesc, ThinSite, ThinQSite, ThinFinishDesc, SplitDesc, MergeSite, MstepSite,
+           MergeSummary, AdamWGroup, LinearPlan, ConvPlan, Conv3NhwcPlan, Conv3PackSite, WsSite, ReduceDesc)
+
+
+# Every function of include/lora_amd.h, in header order: (name, restype, argtypes).  This table is the only place a
+# prototype is restated; tests/test_capi_cpu.py parses the header and compares each entry with it.
+vp, i32, i64, f32, u64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
+cint, cstr, P = C.c_int, C.c_char_p, C.POINTER
+FUNCTIONS = (
+    ("lora_amd_abi_version", cint, ()),
+    ("lora_amd_last_error", cstr, ()),
+    ("lora_amd_target_arch", cstr, ()),
+    ("lora_amd_merge_plan", cint, (P(MergeSite), i32, i32, P(MergeSummary))),
+    ("lora_amd_merge_batched", cint, (vp, i32, P(MergeSummary), i32, i32, f32, i32, vp)),
+    ("lora_amd_merge_step_plan", cint, (P(MstepSite), i32, i32, P(i64))),
+    ("lora_amd_merge_step", cint, (vp, i32, i64, i32, i32, f32, i32, vp)),
+    ("lora_amd_merge_step_set_tuning", cint, (i32, i32)),
+    ("lora_amd_rank16_mfma", cint, (i32,)),
+    ("lora_amd_merge_set_tuning", cint, (i64, i64)),
+    ("lora_amd_rowdot", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32, vp)),
+    ("lora_amd_rank_update", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, f32, u64, u64, vp, vp)),
+    ("lora_amd_rank_update_rowscale", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32, i64, f32,
+        u64, u64, vp)),
+    ("lora_amd_rowdot_masked", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32, f32, u64, u64,
+        vp, vp)),
+    ("lora_amd_colreduce_workspace", sz, (i64, i32, i32)),
+    ("lora_amd_colreduce", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, f32, f32, f32, u64, u64, vp, vp, sz, vp)),
+    ("lora_amd_rowdot_batched", cint, (vp, i64, i64, vp, i64, vp, i64, i32, i64, i32, i32, i32, i32, i32, f32, vp)),
+    ("lora_amd_colreduce_batched", cint, (vp, i64, i64, vp, i64, vp, i64, i32, i64, i32, i32, i32, i32, f32, vp, sz,
+        vp)),
+    ("lora_amd_chol_inverse_batched", cint, (vp, vp, i32, i32, f32, vp)),
+    ("lora_amd_ragged_plan", cint, (i32, vp, i32, i32, P(i64), P(i64))),
+    ("lora_amd_rowdot_ragged", cint, (vp, i32, i64, i32, i32, f32, vp)),
+    ("lora_amd_colreduce_ragged", cint, (vp, i32, i64, i64, i32, i32, f32, vp)),
+    ("lora_amd_rowdot16_planes_plan", cint, (vp, i32, vp)),
+    ("lora_amd_rowdot16_planes", cint, (vp, i32, i64, i32, i32, vp)),
+    ("lora_amd_rowdot16_planes_packed", cint, (vp, i32, i64, i32, i32, vp)),
+    ("lora_amd_split16_ragged", cint, (vp, i32, i64, i32, vp)),
+    ("lora_amd_split16_transpose", cint, (vp, i32, i64, i32, vp)),
+    ("lora_amd_sub_ragged", cint, (vp, i32, i64, i32, vp)),
+    ("lora_amd_thin_gram", cint, (vp, vp, i64, vp, vp, vp, vp)),
+    ("lora_amd_thin_apply", cint, (vp, vp, i64, vp, vp, vp, vp, vp)),
+    ("lora_amd_thin_rotate", cint, (vp, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp)),
+    ("lora_amd_thin_pack", cint, (vp, vp, i64, vp, vp, i32, vp)),
+    ("lora_amd_thin_select", cint, (vp, vp, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp)),
+    ("lora_amd_thin_clamp", cint, (vp, vp, i64, vp, vp, vp, vp, vp, i32, vp)),
+    ("lora_amd_split16_residual", cint, (vp, i32, i64, i32, i32, vp, vp)),
+    ("lora_amd_linear_plan", cint, (i64, i32, i32, i32, P(LinearPlan))),
+    ("lora_amd_linear_fwd", cint, (vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, f32, u64,
+        u64, vp, vp)),
+    ("lora_amd_linear_bwd_g", cint, (vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, u64, u64, vp, vp)),
+    ("lora_amd_linear_bwd_g_blocks", cint, (i64, i32, i32, P(i64))),
+    ("lora_amd_linear_bwd_g_folded", cint, (vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, u64,
+        u64, vp, vp)),
+    ("lora_amd_linear_bwd_x", cint, (vp, i64, vp, i64, vp, i32, vp, vp, vp, i64, i32, i32, i32, i32, vp)),
+    ("lora_amd_linear_bwd_factors", cint, (vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32, vp)),
+    ("lora_amd_linear_bwd_factors_drop", cint, (vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32,
+        f32, u64, u64, vp, vp)),
+    ("lora_amd_linear_bwd_factors_heads", cint, (vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32,
+        i32, i32, i32, i32, vp)),
+    ("lora_amd_linear_gemm_supported", cint, (i64, i32, i32, i32, i32)),
+    ("lora_amd_linear_gemm_fwd", cint, (vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32,
+        f32, i32, i32, vp)),
+    ("lora_amd_ws_config", cint, (i32, P(i32), P(i32))),
+    ("lora_amd_ws_packed_elems", i64, (i32, i32)),
+    ("lora_amd_ws_pack", cint, (vp, i64, i64, i32, i32, i32, vp, vp)),
+    ("lora_amd_linear_ws", cint, (vp, i64, i64, i32, i32, P(WsSite), i32, i32, vp)),
+    ("lora_amd_linear_ws_heads", cint, (vp, i64, i64, i32, i32, i32, i32, P(WsSite), i32, i32, vp)),
+    ("lora_amd_linear_gemm_fwd_heads", cint, (vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32,
+        f32, f32, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_linear_gemm_fwd_rowscale", cint, (vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32,
+        f32, vp, i32, i64, i32, vp)),
+    ("lora_amd_linear_factors_self_plan", cint, (i64, i32, i32, i32, P(FactorsSelfPlan))),
+    ("lora_amd_linear_factors_self_plan_rows", cint, (i64, i32, i32, i32, i32, P(FactorsSelfPlan))),
+    ("lora_amd_linear_bwd_factors_self", cint, (vp, i64, vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32,
+        i32, i32, i32, vp)),
+    ("lora_amd_linear_factors_self_ragged_plan", cint, (vp, i32, i32, P(i64))),
+    ("lora_amd_linear_bwd_factors_self_ragged", cint, (vp, i32, i64, i32, i32, vp)),
+    ("lora_amd_reduce_batched", cint, (vp, i32, i64, vp)),
+    ("lora_amd_factors_mfma_plan", cint, (i64, i32, i32, i32, i32, i32, i32, P(FactorsMfmaPlan))),
+    ("lora_amd_factor_pack_plan", cint, (P(PackSite), i32, P(i64))),
+    ("lora_amd_factor_pack", cint, (vp, i32, i64, i32, vp)),
+    ("lora_amd_factors_mfma_ragged_plan", cint, (P(FmSite), i32, i32, i32, P(i64))),
+    ("lora_amd_linear_bwd_factors_mfma_ragged", cint, (vp, i32, i64, i32, i32, i32, i32, vp)),
+    ("lora_amd_factors_mfma_block_map", cint, (P(FmSite), i32, i64, P(i32))),
+    ("lora_amd_linear_bwd_factors_mfma_ragged_mapped", cint, (vp, i32, i64, vp, i32, i32, i32, i32, vp)),
+    ("lora_amd_factors_mfma_set_tuning", cint, (i32,)),
+    ("lora_amd_conv_plan", cint, (i32, i32, i32, i32, i32, i32, i32, P(ConvPlan))),
+    ("lora_amd_conv_down_fwd", cint, (vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_conv_up_fwd", cint, (vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, u64, u64, vp, vp)),
+    ("lora_amd_conv_up_fwd_rowscale", cint, (vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, i32, i64, f32,
+        u64, u64, vp)),
+    ("lora_amd_conv_bwd_g", cint, (vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, u64,
+        u64, vp, vp)),
+    ("lora_amd_conv_bwd_x", cint, (vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_conv3_nhwc_plan", cint, (i32, i32, i32, i32, i32, P(Conv3NhwcPlan))),
+    ("lora_amd_conv3_nhwc_pack", cint, (vp, i32, i32, i32, vp, vp, vp)),
+    ("lora_amd_conv3_nhwc_down_fwd", cint, (vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_conv3_nhwc_bwd_dx", cint, (vp, vp, vp, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_conv3_nhwc_bwd_down", cint, (vp, vp, vp, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_conv3_nhwc_pack_plan", cint, (P(Conv3PackSite), i32, P(i64))),
+    ("lora_amd_conv3_nhwc_pack_batched", cint, (vp, i32, i64, i32, vp)),
+    ("lora_amd_conv3_nhwc_fwd_fused", cint, (vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32,
+        f32, u64, u64, vp, vp)),
+    ("lora_amd_sum_parts", cint, (vp, i32, i64, vp, i64, vp)),
+    ("lora_amd_sumsq_workspace", sz, (i64,)),
+    ("lora_amd_sumsq", cint, (vp, i64, vp, vp, sz, vp)),
+    ("lora_amd_clip_adamw", cint, (vp, vp, vp, vp, i64, vp, i32, vp, f32, f32, f32, f32, f32, i64, i32, vp)),
+    ("lora_amd_clip_adamw_dev", cint, (vp, vp, vp, vp, i64, vp, i32, vp, f32, f32, f32, f32, f32, vp, vp, i32, vp)),
+    ("lora_amd_step_advance", cint, (vp, vp)),
+    ("lora_amd_loss_scale_update", cint, (vp, vp, vp, f32, f32, i32, vp)),
+    ("lora_amd_ti_rows_step", cint, (vp, vp, vp, i32, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32, f32, i64, f32,
+        f32, vp)),
+    ("lora_amd_groupnorm_workspace", sz, (i32, i32, i32, i32)),
+    ("lora_amd_groupnorm_supported", cint, (i32, i32, i32, i32)),
+    ("lora_amd_groupnorm_fwd", cint, (vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, f32, i32, i32, vp)),
+    ("lora_amd_groupnorm_bwd", cint, (vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_groupnorm_nhwc_workspace", sz, (i32, i32, i32, i32)),
+    ("lora_amd_groupnorm_nhwc_fwd", cint, (vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, f32, i32, i32, vp)),
+    ("lora_amd_groupnorm_nhwc_bwd", cint, (vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_layernorm_supported", cint, (i32,)),
+    ("lora_amd_layernorm_fwd", cint, (vp, vp, vp, vp, vp, i64, i32, f32, i32, vp)),
+    ("lora_amd_layernorm_bwd", cint, (vp, vp, vp, vp, vp, i64, i32, i32, vp)),
+    ("lora_amd_add_layernorm_fwd", cint, (vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp)),
+    ("lora_amd_add_layernorm_bwd", cint, (vp, vp, vp, vp, vp, vp, i64, i32, i32, vp)),
+    ("lora_amd_geglu_fwd", cint, (vp, i64, vp, i64, i64, i32, i32, vp)),
+    ("lora_amd_geglu_bwd", cint, (vp, i64, vp, i64, vp, i64, i64, i32, i32, vp)),
+    ("lora_amd_attn_short_bwd_supported", cint, (i64, i32, i32, i32, vp, i32)),
+    ("lora_amd_attn_short_bwd_plan", cint, (i32, i32, i64, i32, i32, P(AttnShortPlan))),
+    ("lora_amd_attn_short_bwd", cint, (vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, i32,
+        i32, f32, i32, vp, sz, vp)),
+)
+SYMBOLS = tuple(name for name, _, _ in FUNCTIONS)
 
 
 _lib: Optional[C.CDLL] = None
@@ -255,187 +403,9 @@ _load_error: Optional[str] = None
 
 
 def _declare(lib: C.CDLL) -> None:
-    vp, i32, i64, f32, u64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64, C.c_size_t
-    lib.lora_amd_abi_version.restype = C.c_int
-    lib.lora_amd_last_error.restype = C.c_char_p
-    lib.lora_amd_target_arch.restype = C.c_char_p
-    lib.lora_amd_merge_plan.argtypes = [C.POINTER(MergeSite), i32, i32, C.POINTER(MergeSummary)]
-    lib.lora_amd_merge_batched.argtypes = [vp, i32, C.POINTER(MergeSummary), i32, i32, f32, i32, vp]
-    lib.lora_amd_merge_step_plan.argtypes = [C.POINTER(MstepSite), i32, i32, C.POINTER(i64)]
-    lib.lora_amd_merge_step.argtypes = [vp, i32, i64, i32, i32, f32, i32, vp]
-    lib.lora_amd_merge_step_plan.restype = lib.lora_amd_merge_step.restype = C.c_int
-    lib.lora_amd_merge_set_tuning.argtypes = [i64, i64]
-    lib.lora_amd_merge_step_set_tuning.argtypes = [i32, i32]
-    lib.lora_amd_rank16_mfma.argtypes = [i32]
-    lib.lora_amd_rank16_mfma.restype = C.c_int
-    lib.lora_amd_rowdot.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32, vp]
-    lib.lora_amd_rowdot_masked.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32,
-                                           f32, u64, u64, vp, vp]
-    lib.lora_amd_rank_update.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, f32, u64, u64, vp, vp]
-    lib.lora_amd_colreduce_workspace.argtypes = [i64, i32, i32]
-    lib.lora_amd_colreduce_workspace.restype = sz
-    lib.lora_amd_colreduce.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, i32, f32, f32, f32, u64, u64, vp,
-                                       vp, sz, vp]
-    lib.lora_amd_rowdot_batched.argtypes = [vp, i64, i64, vp, i64, vp, i64, i32, i64, i32, i32, i32, i32, i32, f32, vp]
-    lib.lora_amd_colreduce_batched.argtypes = [vp, i64, i64, vp, i64, vp, i64, i32, i64, i32, i32, i32, i32, f32, vp, sz, vp]
-    lib.lora_amd_chol_inverse_batched.argtypes = [vp, vp, i32, i32, f32, vp]
-    lib.lora_amd_rowdot_batched.restype = lib.lora_amd_colreduce_batched.restype = C.c_int
-    lib.lora_amd_chol_inverse_batched.restype = C.c_int
-    lib.lora_amd_ragged_plan.argtypes = [i32, vp, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.lora_amd_rowdot_ragged.argtypes = [vp, i32, i64, i32, i32, f32, vp]
-    lib.lora_amd_colreduce_ragged.argtypes = [vp, i32, i64, i64, i32, i32, f32, vp]
-    lib.lora_amd_sub_ragged.argtypes = [vp, i32, i64, i32, vp]
-    lib.lora_amd_rowdot16_planes_plan.argtypes = [vp, i32, vp]
-    lib.lora_amd_rowdot16_planes.argtypes = [vp, i32, i64, i32, i32, vp]
-    lib.lora_amd_split16_ragged.argtypes = [vp, i32, i64, i32, vp]
-    lib.lora_amd_rowdot16_planes_plan.restype = lib.lora_amd_rowdot16_planes.restype = C.c_int
-    lib.lora_amd_rowdot16_planes_packed.argtypes = [vp, i32, i64, i32, i32, vp]
-    lib.lora_amd_thin_pack.argtypes = [vp, vp, i64, vp, vp, i32, vp]
-    lib.lora_amd_rowdot16_planes_packed.restype = lib.lora_amd_thin_pack.restype = C.c_int
-    lib.lora_amd_split16_ragged.restype = C.c_int
-    lib.lora_amd_split16_transpose.argtypes = [vp, i32, i64, i32, vp]
-    lib.lora_amd_split16_transpose.restype = C.c_int
-    lib.lora_amd_split16_residual.argtypes = [vp, i32, i64, i32, i32, vp, vp]
-    lib.lora_amd_split16_residual.restype = C.c_int
-    lib.lora_amd_thin_gram.argtypes = [vp, vp, i64, vp, vp, vp, vp]
-    lib.lora_amd_thin_apply.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
-    lib.lora_amd_thin_rotate.argtypes = [vp, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.lora_amd_thin_select.argtypes = [vp, vp, i64, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
-    lib.lora_amd_thin_clamp.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, i32, vp]
-    lib.lora_amd_thin_gram.restype = lib.lora_amd_thin_apply.restype = lib.lora_amd_thin_rotate.restype = C.c_int
-    lib.lora_amd_thin_select.restype = lib.lora_amd_thin_clamp.restype = C.c_int
-    lib.lora_amd_ragged_plan.restype = lib.lora_amd_rowdot_ragged.restype = C.c_int
-    lib.lora_amd_colreduce_ragged.restype = lib.lora_amd_sub_ragged.restype = C.c_int
-    lib.lora_amd_sumsq_workspace.argtypes = [i64]
-    lib.lora_amd_sumsq_workspace.restype = sz
-    lib.lora_amd_sumsq.argtypes = [vp, i64, vp, vp, sz, vp]
-    lib.lora_amd_clip_adamw.argtypes = [vp, vp, vp, vp, i64, vp, i32, vp, f32, f32, f32, f32, f32, i64, i32, vp]
-    lib.lora_amd_clip_adamw_dev.argtypes = [vp, vp, vp, vp, i64, vp, i32, vp, f32, f32, f32, f32, f32, vp, vp, i32, vp]
-    lib.lora_amd_loss_scale_update.argtypes = [vp, vp, vp, f32, f32, i32, vp]
-    lib.lora_amd_loss_scale_update.restype = C.c_int
-    lib.lora_amd_step_advance.argtypes = [vp, vp]
-    lib.lora_amd_ti_rows_step.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32, f32, i64, f32, f32,
-                                          vp]
-    lib.lora_amd_ti_rows_step.restype = C.c_int
-    lib.lora_amd_clip_adamw_dev.restype = lib.lora_amd_step_advance.restype = C.c_int
-    lib.lora_amd_linear_plan.argtypes = [i64, i32, i32, i32, C.POINTER(LinearPlan)]
-    lib.lora_amd_linear_fwd.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, f32, u64,
-                                        u64, vp, vp]
-    lib.lora_amd_linear_bwd_g.argtypes = [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, u64, u64, vp, vp]
-    lib.lora_amd_linear_bwd_x.argtypes = [vp, i64, vp, i64, vp, i32, vp, vp, vp, i64, i32, i32, i32, i32, vp]
-    lib.lora_amd_linear_bwd_factors.argtypes = [vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32, vp]
-    lib.lora_amd_linear_bwd_factors.restype = C.c_int
-    lib.lora_amd_linear_bwd_factors_drop.argtypes = [vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32,
-                                                     f32, u64, u64, vp, vp]
-    lib.lora_amd_linear_bwd_factors_drop.restype = C.c_int
-    lib.lora_amd_linear_bwd_factors_heads.argtypes = [vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32,
-                                                      i32, i32, i32, i32, vp]
-    lib.lora_amd_linear_bwd_factors_heads.restype = C.c_int
-    lib.lora_amd_linear_factors_self_plan.argtypes = [i64, i32, i32, i32, C.POINTER(FactorsSelfPlan)]
-    lib.lora_amd_linear_bwd_factors_self.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32,
-                                                     i32, i32, i32, i32, vp]
-    lib.lora_amd_linear_factors_self_plan.restype = lib.lora_amd_linear_bwd_factors_self.restype = C.c_int
-    lib.lora_amd_linear_factors_self_plan_rows.argtypes = [i64, i32, i32, i32, i32, C.POINTER(FactorsSelfPlan)]
-    lib.lora_amd_linear_factors_self_plan_rows.restype = C.c_int
-    lib.lora_amd_linear_factors_self_ragged_plan.argtypes = [vp, i32, i32, C.POINTER(C.c_int64)]
-    lib.lora_amd_linear_bwd_factors_self_ragged.argtypes = [vp, i32, i64, i32, i32, vp]
-    lib.lora_amd_linear_factors_self_ragged_plan.restype = lib.lora_amd_linear_bwd_factors_self_ragged.restype = C.c_int
-    lib.lora_amd_factors_mfma_plan.argtypes = [i64, i32, i32, i32, i32, i32, i32, C.POINTER(FactorsMfmaPlan)]
-    lib.lora_amd_factor_pack_plan.argtypes = [C.POINTER(PackSite), i32, C.POINTER(i64)]
-    lib.lora_amd_factor_pack.argtypes = [vp, i32, i64, i32, vp]
-    lib.lora_amd_factors_mfma_ragged_plan.argtypes = [C.POINTER(FmSite), i32, i32, i32, C.POINTER(i64)]
-    lib.lora_amd_linear_bwd_factors_mfma_ragged.argtypes = [vp, i32, i64, i32, i32, i32, i32, vp]
-    lib.lora_amd_factors_mfma_block_map.argtypes = [C.POINTER(FmSite), i32, i64, C.POINTER(i32)]
-    lib.lora_amd_linear_bwd_factors_mfma_ragged_mapped.argtypes = [vp, i32, i64, vp, i32, i32, i32, i32, vp]
-    lib.lora_amd_factors_mfma_block_map.restype = lib.lora_amd_linear_bwd_factors_mfma_ragged_mapped.restype = C.c_int
-    for name in ("lora_amd_factors_mfma_plan", "lora_amd_factor_pack_plan", "lora_amd_factor_pack",
-                 "lora_amd_factors_mfma_ragged_plan", "lora_amd_linear_bwd_factors_mfma_ragged"):
-        getattr(lib, name).restype = C.c_int
-    lib.lora_amd_linear_gemm_fwd_heads.argtypes = [vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32,
-                                                   f32, f32, i32, i32, i32, i32, i32, i32, vp]
-    lib.lora_amd_linear_gemm_fwd_heads.restype = C.c_int
-    lib.lora_amd_reduce_batched.argtypes = [vp, i32, i64, vp]
-    lib.lora_amd_linear_gemm_supported.argtypes = [i64, i32, i32, i32, i32]
-    lib.lora_amd_linear_gemm_fwd.argtypes = [vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, i32,
-                                             i32, vp]
-    lib.lora_amd_linear_gemm_supported.restype = lib.lora_amd_linear_gemm_fwd.restype = C.c_int
-    lib.lora_amd_linear_gemm_fwd_rowscale.argtypes = [vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32,
-                                                      f32, vp, i32, i64, i32, vp]
-    lib.lora_amd_rank_update_rowscale.argtypes = [vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32, i64, f32,
-                                                  u64, u64, vp]
-    lib.lora_amd_conv_up_fwd_rowscale.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp, i32, i64, f32,
-                                                  u64, u64, vp]
-    for name in ("lora_amd_linear_gemm_fwd_rowscale", "lora_amd_rank_update_rowscale", "lora_amd_conv_up_fwd_rowscale"):
-        getattr(lib, name).restype = C.c_int
-    lib.lora_amd_ws_config.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
-    lib.lora_amd_ws_packed_elems.argtypes = [i32, i32]
-    lib.lora_amd_ws_packed_elems.restype = i64
-    lib.lora_amd_ws_pack.argtypes = [vp, i64, i64, i32, i32, i32, vp, vp]
-    lib.lora_amd_linear_ws.argtypes = [vp, i64, i64, i32, i32, C.POINTER(WsSite), i32, i32, vp]
-    lib.lora_amd_linear_ws_heads.argtypes = [vp, i64, i64, i32, i32, i32, i32, C.POINTER(WsSite), i32, i32, vp]
-    lib.lora_amd_ws_config.restype = lib.lora_amd_ws_pack.restype = lib.lora_amd_linear_ws.restype = C.c_int
-    lib.lora_amd_linear_ws_heads.restype = C.c_int
-    lib.lora_amd_conv_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(ConvPlan)]
-    lib.lora_amd_conv_down_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-    lib.lora_amd_conv_up_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, u64, u64, vp, vp]
-    lib.lora_amd_conv_bwd_g.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, u64,
-                                        u64, vp, vp]
-    lib.lora_amd_conv_bwd_x.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
-    lib.lora_amd_conv3_nhwc_plan.argtypes = [i32, i32, i32, i32, i32, C.POINTER(Conv3NhwcPlan)]
-    lib.lora_amd_conv3_nhwc_pack.argtypes = [vp, i32, i32, i32, vp, vp, vp]
-    lib.lora_amd_conv3_nhwc_down_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.lora_amd_conv3_nhwc_bwd_dx.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.lora_amd_conv3_nhwc_bwd_down.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.lora_amd_sum_parts.argtypes = [vp, i32, i64, vp, i64, vp]
-    lib.lora_amd_conv3_nhwc_pack_plan.argtypes = [C.POINTER(Conv3PackSite), i32, C.POINTER(i64)]
-    lib.lora_amd_conv3_nhwc_pack_batched.argtypes = [vp, i32, i64, i32, vp]
-    lib.lora_amd_conv3_nhwc_fwd_fused.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32,
-                                                  u64, u64, vp, vp]
-    lib.lora_amd_linear_bwd_g_blocks.argtypes = [i64, i32, i32, C.POINTER(i64)]
-    lib.lora_amd_linear_bwd_g_folded.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, u64,
-                                                 u64, vp, vp]
-    for name in ("lora_amd_conv3_nhwc_plan", "lora_amd_conv3_nhwc_pack", "lora_amd_conv3_nhwc_down_fwd",
-                 "lora_amd_conv3_nhwc_bwd_dx", "lora_amd_conv3_nhwc_bwd_down", "lora_amd_sum_parts",
-                 "lora_amd_conv3_nhwc_pack_plan", "lora_amd_conv3_nhwc_pack_batched", "lora_amd_conv3_nhwc_fwd_fused",
-                 "lora_amd_linear_bwd_g_blocks", "lora_amd_linear_bwd_g_folded"):
-        getattr(lib, name).restype = C.c_int
-    lib.lora_amd_groupnorm_workspace.argtypes = [i32, i32, i32, i32]
-    lib.lora_amd_groupnorm_workspace.restype = sz
-    lib.lora_amd_groupnorm_supported.argtypes = [i32, i32, i32, i32]
-    lib.lora_amd_groupnorm_fwd.argtypes = [vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, f32, i32, i32, vp]
-    lib.lora_amd_groupnorm_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp]
-    lib.lora_amd_geglu_fwd.argtypes = [vp, i64, vp, i64, i64, i32, i32, vp]
-    lib.lora_amd_geglu_bwd.argtypes = [vp, i64, vp, i64, vp, i64, i64, i32, i32, vp]
-    lib.lora_amd_groupnorm_nhwc_workspace.argtypes = [i32, i32, i32, i32]
-    lib.lora_amd_groupnorm_nhwc_workspace.restype = sz
-    lib.lora_amd_groupnorm_nhwc_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, f32, i32, i32, vp]
-    lib.lora_amd_groupnorm_nhwc_bwd.argtypes = [vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp]
-    lib.lora_amd_groupnorm_nhwc_fwd.restype = lib.lora_amd_groupnorm_nhwc_bwd.restype = C.c_int
-    lib.lora_amd_add_layernorm_fwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp]
-    lib.lora_amd_add_layernorm_bwd.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]
-    lib.lora_amd_add_layernorm_fwd.restype = lib.lora_amd_add_layernorm_bwd.restype = C.c_int
-    lib.lora_amd_layernorm_supported.argtypes = [i32]
-    lib.lora_amd_layernorm_fwd.argtypes = [vp, vp, vp, vp, vp, i64, i32, f32, i32, vp]
-    lib.lora_amd_layernorm_bwd.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, vp]
-    lib.lora_amd_attn_short_bwd_supported.argtypes = [i64, i32, i32, i32, vp, i32]
-    lib.lora_amd_attn_short_bwd_plan.argtypes = [i32, i32, i64, i32, i32, C.POINTER(AttnShortPlan)]
-    lib.lora_amd_attn_short_bwd.argtypes = [vp, vp] * 7 + [i32, i32, i64, i32, i32, f32, i32, vp, sz, vp]
-    for name in ("lora_amd_attn_short_bwd_supported", "lora_amd_attn_short_bwd_plan", "lora_amd_attn_short_bwd"):
-        getattr(lib, name).restype = C.c_int
-    for name in ("lora_amd_groupnorm_supported", "lora_amd_groupnorm_fwd", "lora_amd_groupnorm_bwd",
-                 "lora_amd_geglu_fwd", "lora_amd_geglu_bwd", "lora_amd_layernorm_supported",
-                 "lora_amd_layernorm_fwd", "lora_amd_layernorm_bwd"):
-        getattr(lib, name).restype = C.c_int
-    for name in ("lora_amd_conv_plan", "lora_amd_conv_down_fwd", "lora_amd_conv_up_fwd", "lora_amd_conv_bwd_g",
-                 "lora_amd_conv_bwd_x"):
-        getattr(lib, name).restype = C.c_int
-    for name in ("lora_amd_linear_plan", "lora_amd_linear_fwd", "lora_amd_linear_bwd_g", "lora_amd_linear_bwd_x",
-                 "lora_amd_reduce_batched"):
-        getattr(lib, name).restype = C.c_int
-    for name in ("lora_amd_merge_plan", "lora_amd_merge_batched", "lora_amd_merge_set_tuning", "lora_amd_rowdot",
-                 "lora_amd_rowdot_masked", "lora_amd_rank_update", "lora_amd_colreduce", "lora_amd_sumsq",
-                 "lora_amd_clip_adamw"):
-        getattr(lib, name).restype = C.c_int
+    for name, restype, argtypes in FUNCTIONS:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, list(argtypes)
 
 
 def load() -> Optional[C.CDLL]:
@@ -504,6 +474,11 @@ def _dev_check(*ts: torch.Tensor) -> None:
             raise ValueError("lora_amd kernels take device tensors only")
 
 
+def table_to_device(arr, device) -> torch.Tensor:
+    """The bytes of a host descriptor table (a ctypes array, or bytes) as a uint8 device tensor: one copy."""
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
 # ----------------------------------------------------------------------------- merge (K3)
 class MergePlan:
     """Planned descriptor table for one (w_dtype, ab_dtype) group of sites, resident on the device."""
@@ -549,8 +524,7 @@ class MergePlan:
         _check(lib.lora_amd_merge_plan(arr, n, dtype_code(self.w_dtype), C.byref(self.summary)), "lora_amd_merge_plan")
         self.n_sites, self.total_tiles = n, self.summary.total_tiles
         self.host = arr
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
-        self.table = raw.to(self.device)
+        self.table = table_to_device(arr, self.device)
 
     def launch(self, alpha: float = 1.0, rounding: int = ROUND_REFERENCE) -> None:
         lib = require()
@@ -626,10 +600,7 @@ def merge_set_tuning(tile_elems: int = 0, blocks_per_cu: int = 0) -> None:
 
 def factors_mfma_set_tuning(narrow: int = -1) -> int:
     """Kernel of class-1 tables of the matrix-core factor pass (0 wide, 1 narrow / ring 2, 2 narrow / ring 4); returns the previous."""
-    lib = require()
-    lib.lora_amd_factors_mfma_set_tuning.argtypes = [C.c_int32]
-    lib.lora_amd_factors_mfma_set_tuning.restype = C.c_int
-    return int(lib.lora_amd_factors_mfma_set_tuning(int(narrow)))
+    return int(require().lora_amd_factors_mfma_set_tuning(int(narrow)))
 
 
 def rank16_mfma(enable: int = -1) -> int:
@@ -776,15 +747,29 @@ def chol_inverse_batched(gram: torch.Tensor, shift_rel: float = 0.0, out: Option
 RAGGED_ROWDOT, RAGGED_COLREDUCE = 0, 1
 
 
-class RaggedProgram:
-    """Descriptor tables of a sequence of ragged launches over persistent buffers (``cli_svd.distill_model``): every
-    table is planned on the host as it is declared, ALL of them go to the device in one copy (``upload``), and a launch
-    is then one C call with a pointer into that buffer — no per-launch allocation, planning or host-to-device traffic."""
+class _TableProgram:
+    """Planned descriptor tables kept on the host, each padded to 64 bytes, and sent to the device in ONE copy."""
 
     def __init__(self, device):
         self.device = device
-        self._blobs, self._meta, self._size = [], [], 0
-        self._dev = None
+        self._blobs, self._meta, self._size, self._dev = [], [], 0, None
+
+    def _append(self, arr) -> int:
+        """Adds a planned table; returns its byte offset in the uploaded buffer."""
+        off, blob = self._size, bytes(arr)
+        blob += b"\0" * ((-len(blob)) % 64)
+        self._blobs.append(blob)
+        self._size += len(blob)
+        return off
+
+    def upload(self):
+        self._dev = table_to_device(b"".join(self._blobs), self.device)
+
+
+class RaggedProgram(_TableProgram):
+    """Descriptor tables of a sequence of ragged launches over persistent buffers (``cli_svd.distill_model``): every
+    table is planned on the host as it is declared, ALL of them go to the device in one copy (``upload``), and a launch
+    is then one C call with a pointer into that buffer — no per-launch allocation, planning or host-to-device traffic."""
 
     def table(self, op: int, r: int, rows) -> int:
         """rows: per stack (x [B, M, K], f [B, ...], out [B, ...], partial or None).  Returns the table's handle."""
@@ -804,16 +789,8 @@ class RaggedProgram:
                 raise ValueError("ragged colreduce: workspace too small")
         g1, g2 = C.c_int64(0), C.c_int64(0)
         _check(lib.lora_amd_ragged_plan(op, arr, len(rows), r, C.byref(g1), C.byref(g2)), "lora_amd_ragged_plan")
-        off = self._size
-        blob = bytes(arr)
-        pad = (-len(blob)) % 64
-        self._blobs.append(blob + b"\0" * pad)
-        self._size += len(blob) + pad
-        self._meta.append((op, r, len(rows), off, g1.value, g2.value))
+        self._meta.append((op, r, len(rows), self._append(arr), g1.value, g2.value))
         return len(self._meta) - 1
-
-    def upload(self):
-        self._dev = torch.frombuffer(bytearray(b"".join(self._blobs)), dtype=torch.uint8).to(self.device)
 
     def run(self, handle: int, layout: int, scale: float = 1.0) -> None:
         lib = require()
@@ -826,7 +803,7 @@ class RaggedProgram:
                    "lora_amd_colreduce_ragged")
 
 
-class PlanesProgram:
+class PlanesProgram(_TableProgram):
     """Descriptor tables of the matrix-core skinny products over (hi, lo) 16-bit planes (``lora_amd_rowdot16_planes``):
     declared once (``table``), uploaded in one copy, each run one C call.  rows: per shape group (hi [B, M, C], lo, f [B, C, r]
     f32, out [B, M, r] f32)."""
@@ -834,10 +811,10 @@ class PlanesProgram:
     def __init__(self, device, r: int, plane_dtype: torch.dtype = torch.bfloat16, packed: bool = False):
         """``packed``: the factor of every row is given as fragments (``thin_pack``): a 16-bit tensor [B, C * 32] (hi / lo
         1 KB blocks per 32 rows of the [C, 16] factor) instead of f32 [B, C, r]; r = 16."""
-        self.device, self.r, self.dt, self.packed = device, int(r), plane_dtype, bool(packed)
+        super().__init__(device)
+        self.r, self.dt, self.packed = int(r), plane_dtype, bool(packed)
         if packed and self.r != 16:
             raise ValueError("PlanesProgram: packed factors are 16 columns wide")
-        self._blobs, self._meta, self._size, self._dev = [], [], 0, None
 
     def table(self, rows) -> int:
         lib = require()
@@ -854,15 +831,8 @@ class PlanesProgram:
             d.hi, d.lo, d.f, d.out, d.M, d.C, d.batch = hi.data_ptr(), lo.data_ptr(), f.data_ptr(), out.data_ptr(), M, Cc, B
         grid = C.c_int64(0)
         _check(lib.lora_amd_rowdot16_planes_plan(arr, len(rows), C.byref(grid)), "lora_amd_rowdot16_planes_plan")
-        blob = bytes(arr)
-        pad = (-len(blob)) % 64
-        self._blobs.append(blob + b"\0" * pad)
-        self._meta.append((len(rows), self._size, grid.value))
-        self._size += len(blob) + pad
+        self._meta.append((len(rows), self._append(arr), grid.value))
         return len(self._meta) - 1
-
-    def upload(self):
-        self._dev = torch.frombuffer(bytearray(b"".join(self._blobs)), dtype=torch.uint8).to(self.device)
 
     def run(self, handle: int, hi_only: bool = False) -> None:
         n, off, grid = self._meta[handle]
@@ -1021,7 +991,7 @@ def split16_ragged(srcs, his, los) -> None:
             raise ValueError("split16_ragged: contiguous f32 sources and same-size 16-bit planes (numel % 8 == 0) expected")
         d.src, d.hi, d.lo, d.n, d.begin = s_.data_ptr(), h.data_ptr(), l.data_ptr(), s_.numel(), blocks
         blocks += (s_.numel() + 4095) // 4096
-    dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(his[0].device)
+    dev = table_to_device(arr, his[0].device)
     _check(lib.lora_amd_split16_ragged(dev.data_ptr(), len(srcs), blocks, dtype_code(dt), _stream()), "lora_amd_split16_ragged")
 
 
@@ -1041,7 +1011,7 @@ def split16_transpose(stacks, his, los, this, tlos) -> None:
         d.src, d.hi, d.lo, d.thi, d.tlo = x.data_ptr(), h.data_ptr(), l.data_ptr(), th.data_ptr(), tl.data_ptr()
         d.batch, d.N, d.K, d.tile_begin = B, N, K, tiles
         tiles += B * (-(-N // 64)) * (-(-K // 64))
-    dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(his[0].device)
+    dev = table_to_device(arr, his[0].device)
     _check(lib.lora_amd_split16_transpose(dev.data_ptr(), len(stacks), tiles, dtype_code(dt), _stream()), "lora_amd_split16_transpose")
 
 
@@ -1063,7 +1033,7 @@ def sub_ragged(pairs, outs) -> None:
             raise ValueError("sub_ragged: contiguous tensors expected")
         d.a, d.b, d.out, d.n, d.begin = a.data_ptr(), b.data_ptr(), o.data_ptr(), a.numel(), blocks
         blocks += (a.numel() + 4095) // 4096
-    dev = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(outs[0].device)
+    dev = table_to_device(arr, outs[0].device)
     _check(lib.lora_amd_sub_ragged(dev.data_ptr(), len(pairs), blocks, dtype_code(dt), _stream()), "lora_amd_sub_ragged")
     # `dev` goes back to the caching allocator on return; the pool hands it out again only to work that is ordered after
     # this launch on the same stream
@@ -1087,7 +1057,7 @@ def make_adamw_groups(groups: Sequence[Tuple[int, int, float, float]], device) -
     arr = (AdamWGroup * len(groups))()
     for i, (b, e, lr, wd) in enumerate(groups):
         arr[i].begin, arr[i].end, arr[i].lr, arr[i].weight_decay = int(b), int(e), float(lr), float(wd)
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    return table_to_device(arr, device)
 
 
 def clip_adamw(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, groups_dev: torch.Tensor,
@@ -1399,10 +1369,6 @@ def linear_bwd_factors_mfma_ragged(table_dev: torch.Tensor, n: int, grid: int, l
            "lora_amd_linear_bwd_factors_mfma_ragged")
 
 
-def table_to_device(arr, device) -> torch.Tensor:
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
-
-
 def make_reduce_table(rows: Sequence[Tuple[torch.Tensor, torch.Tensor, int, int, int, int, int, float, float]],
                       device) -> Tuple[torch.Tensor, int, int]:
     """rows: (part, out, nparts, RT, C, r, layout, scale, beta) -> (device table, n, total work items)."""
@@ -1412,7 +1378,7 @@ def make_reduce_table(rows: Sequence[Tuple[torch.Tensor, torch.Tensor, int, int,
         d.part, d.out, d.begin = part.data_ptr(), out.data_ptr(), begin
         d.nparts, d.RT, d.C, d.r, d.layout, d.scale, d.beta = nparts, RT, Cc, r, layout, scale, beta
         begin += r * Cc
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device), len(rows), begin
+    return table_to_device(arr, device), len(rows), begin
 
 
 def reduce_batched(table: torch.Tensor, n: int, total: int) -> None:

@@ -41,7 +41,7 @@ def test_xs_forward_matches_oracle(M, K, N, r, dt):
 @pytest.mark.parametrize("M,K,N", [(16384, 320, 960), (4096, 640, 640), (300, 320, 100), (2304, 640, 5120)])
 def test_xs_plain_product_on_a_packed_weight(M, K, N):
     """site.down == NULL: Y = X W^T + b (what a merged-weight site runs) from the packed operand AND from the row-major
-    weight itself (site.reserved = 1); the accumulate flag of lora_amd_linear_ws is refused."""
+    weight itself (site.y_heads = 1); the accumulate flag of lora_amd_linear_ws is refused."""
     dt = "bf16"
     x, w, b = rnd((M, K), dt, 1.0, seed=1), rnd((N, K), dt, 0.05, seed=2), rnd((N,), dt, 0.5, seed=3)
     y, t = XS.linear_xs(x, dict(wp=_C.ws_pack(w), N=N, bias=b))

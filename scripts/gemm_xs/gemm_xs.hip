@@ -25,7 +25,7 @@
 //     rows / columns out of range store to a trash line — so the next panel's DMA is never drained behind them);
 //   * blocks that share rows are 8 apart in the grid (same XCD by the observed b % 8 placement): the other column groups'
 //     input comes out of that XCD's L2.
-// Same entry contract as lora_amd_linear_ws (one site), same packed weight (or the row-major weight itself: site.reserved = 1);
+// Same entry contract as lora_amd_linear_ws (one site), same packed weight (or the row-major weight itself: site.y_heads = 1);
 // the two kernels are routed per shape.
 // Measured (profiles/r05_kbench_xs.log): at (16384, 320, 320) the library GEMM, the weight-stationary kernel and this one all
 // take 12-13 us for 21 MB — launch, load, multiply and store phases of ONE wave of workgroups do not overlap, the problem is
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256, 1) void linear_xs_kernel(const XsArgs a) {
   const S *x = reinterpret_cast<const S *>(a.x);
   const int p_begin = cg * a.pg, p_end = min(p_begin + a.pg, a.npanels);
   const int64_t row0 = ((int64_t)rb * 4 + wave) * (16 * SL);
-  const bool rowmajor = st.reserved == 1;            // the weight itself ([N, K] rows) instead of the packed operand
+  const bool rowmajor = st.y_heads == 1;             // the weight itself ([N, K] rows) instead of the packed operand
 
   // panel pn -> LDS buffer `buf`: 1 KB fragment images dealt to the waves
   const S *wbase = reinterpret_cast<const S *>(st.wp);
@@ -412,7 +412,7 @@ extern "C" int lora_amd_linear_xs(const void *x, int64_t ldx, int64_t M, int32_t
                      (!lora || (((uintptr_t)q.down % 16) == 0 && ((uintptr_t)q.up % 16) == 0)),
                  LORA_AMD_EINVAL, "linear_xs: N, ldy must be multiples of 4, pointers aligned");
   LORA_AMD_CHECK(q.dropout_p >= 0.f && q.dropout_p < 1.f, LORA_AMD_EINVAL, "linear_xs: dropout p=%f", q.dropout_p);
-  LORA_AMD_CHECK(q.reserved == 0 || q.reserved == 1, LORA_AMD_EINVAL, "linear_xs: reserved = 0 (packed weight) or 1 (row-major)");
+  LORA_AMD_CHECK(q.y_heads == 0 || q.y_heads == 1, LORA_AMD_EINVAL, "linear_xs: y_heads = 0 (packed weight) or 1 (row-major)");
   const int fl = q.flayout;
   LORA_AMD_CHECK(fl == 0 || fl == 3, LORA_AMD_EINVAL,
                  "linear_xs: factor layout 0 (forward) or 3 (input gradient); no accumulate form (use lora_amd_linear_ws)");

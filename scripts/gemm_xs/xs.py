@@ -66,7 +66,7 @@ def linear_xs(x: torch.Tensor, s: dict):
     bias = s.get("bias")
     d.wp, d.bias, d.y, d.down, d.up, d.t_out = s["wp"].data_ptr(), _ptr(bias), y.data_ptr(), _ptr(down), _ptr(up), _ptr(t)
     d.ldy, d.N, d.r, d.panel_begin, d.flayout = y.stride(0), N, r, 0, fl
-    d.reserved = 1 if s.get("rowmajor") else 0   # ``wp`` = the [N, K] weight itself (contiguous rows) instead of its pack
+    d.y_heads = 1 if s.get("rowmajor") else 0   # ``wp`` = the [N, K] weight itself (contiguous rows) instead of its pack
     d.scale, d.t_scale = float(s.get("scale", 1.0)), float(s.get("t_scale", 1.0))
     off_s, off_p = _off(s.get("off", 0))
     d.dropout_p, d.seed, d.offset, d.offset_dev = float(s.get("p", 0.0)), int(s.get("seed", 0)), off_s, off_p

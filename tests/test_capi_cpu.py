@@ -15,6 +15,149 @@ def _header_symbols():
     return sorted(set(re.findall(r"\b(lora_amd_[a-z0-9_]+)\s*\(", src)))
 
 
+HEADER_DIR = os.path.join(REPO, "include")
+
+
+def _header_prototypes():
+    """[(return type, name, [parameter text])] of every function of include/lora_amd.h, in header order (comments,
+    preprocessor lines and the bodies of structs and enums stripped first)."""
+    src = open(os.path.join(HEADER_DIR, "lora_amd.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+    src = re.sub(r"\{[^{}]*\}", "", src)
+    out = []
+    for ret, name, args in re.findall(r"([\w\s*]+?)\b(lora_amd_[a-z0-9_]+)\s*\(([^;{()]*)\)\s*;", src):
+        params = [] if args.strip() == "void" else [" ".join(a.split()) for a in args.split(",")]
+        out.append((" ".join(ret.split()), name, params))
+    return out
+
+
+_C_SCALARS = {"int": ("i", 4), "int32_t": ("i", 4), "uint32_t": ("u", 4), "int64_t": ("i", 8), "uint64_t": ("u", 8),
+              "size_t": ("u", 8), "float": ("f", 4)}
+
+
+def _scalar_kind(t):
+    """(signedness or float, bytes) of a ctypes scalar: c_size_t is c_uint64 here, so compare by this, not by spelling."""
+    code = getattr(t, "_type_", None)
+    if not isinstance(code, str) or code not in "ilqILQf":
+        return None
+    return ("f" if code == "f" else "i" if code.islower() else "u", C.sizeof(t))
+
+
+def _matches(ctype, c_text, is_param):
+    """Does the ctypes type declare the C parameter (or return type) ``c_text``?"""
+    words = c_text.replace("*", " * ").split()
+    if is_param:
+        words = words[:-1]                               # the parameter's name
+    words = [w for w in words if w != "const"]
+    if words.count("*") > 1 or not words:
+        return False
+    if "*" not in words:
+        return len(words) == 1 and words[0] in _C_SCALARS and _scalar_kind(ctype) == _C_SCALARS[words[0]]
+    base = words[0]
+    if base == "char":
+        return ctype is C.c_char_p
+    if ctype is C.c_void_p:
+        return True
+    target = getattr(ctype, "_type_", None)              # POINTER(T)._type_ is T
+    if not isinstance(target, type) or base == "void":
+        return False
+    if base in _C_SCALARS:
+        return _scalar_kind(target) == _C_SCALARS[base]
+    return getattr(target, "c_struct", None) == base     # a POINTER to another struct's mirror is a failure
+
+
+def test_declaration_table_matches_the_header_prototypes():
+    """_C.FUNCTIONS restates every prototype of the header: same functions in the same order, same number of arguments, the
+    same kind per position and the same return kind.  Needs neither the library nor a GPU."""
+    protos = _header_prototypes()
+    assert len(protos) >= 106, f"header parse found only {len(protos)} prototypes"
+    assert len({n for _, n, _ in protos}) == len(protos), "a prototype was parsed twice"
+    table ={name: (restype, argtypes) for name, restype, argtypes in _C.FUNCTIONS}
+    assert len(table) == len(_C.FUNCTIONS), "a function is listed twice"
+    extra = sorted(set(table) - {n for _, n, _ in protos})
+    assert not extra, f"_C.FUNCTIONS has entries the header lacks: {extra}"
+    bad = []
+    for ret, name, params in protos:
+        if name not in table:
+            bad.append(f"{name}: no table entry")
+            continue
+        restype, argtypes = table[name]
+        if not _matches(restype, ret, False):
+            bad.append(f"{name}: returns `{ret}`, table says {restype}")
+        if len(argtypes) != len(params):
+            bad.append(f"{name}: {len(params)} parameters, table has {len(argtypes)}")
+            continue
+        bad += [f"{name}: parameter {i} `{p}`, table says {t}" for i, (t, p) in enumerate(zip(argtypes, params))
+                if not _matches(t, p, True)]
+    assert not bad, "\n".join(bad)
+    assert [n for n, _, _ in _C.FUNCTIONS] == [n for _, n, _ in protos], "table is not in header order"
+    assert _C.SYMBOLS == tuple(n for _, n, _ in protos)
+
+
+def _host_compiler():
+    """$CXX, else the first of c++ / g++ / clang++ on PATH, else the hipcc of lora_amd/csrc/Makefile (on a plain .cpp)."""
+    import shutil
+
+    if os.environ.get("CXX"):
+        return os.environ["CXX"].split()
+    for cc in ("c++", "g++", "clang++"):
+        if shutil.which(cc):
+            return [cc]
+    mk = open(os.path.join(REPO, "lora_amd", "csrc", "Makefile")).read()
+    hipcc = os.environ.get("HIPCC") or re.search(r"^HIPCC\s*\?=\s*(\S+)", mk, flags=re.M).group(1)
+    assert shutil.which(hipcc), "no C++ compiler found (CXX, c++, g++, clang++, hipcc)"
+    return [hipcc]
+
+
+def test_every_struct_mirror_has_the_layout_the_compiler_gives_the_header(tmp_path):
+    """sizeof of every struct of include/lora_amd.h, and offsetof and size of every field, as a C++ compiler sees them,
+    against the ctypes mirrors of _C.MIRRORS; and every struct of the header has a mirror."""
+    import subprocess
+
+    src = open(os.path.join(HEADER_DIR, "lora_amd.h")).read()
+    structs = re.findall(r"typedef\s+struct\s+(lora_amd_\w+)", src)
+    assert len(structs) >= 25 and len(set(structs)) == len(structs)
+    mirrored = [m.c_struct for m in _C.MIRRORS]
+    assert sorted(mirrored) == sorted(structs), "structs of the header and _C.MIRRORS differ"
+    lines = ["#include <cstddef>", "#include <cstdio>", '#include "lora_amd.h"', "int main() {"]
+    want = []
+    for m in _C.MIRRORS:
+        lines.append(f'  std::printf("%zu\\n", sizeof({m.c_struct}));')
+        want.append((m.c_struct, "sizeof", C.sizeof(m)))
+        for field in m._fields_:
+            f = getattr(m, field[0])
+            lines.append(f'  std::printf("%zu %zu\\n", offsetof({m.c_struct}, {field[0]}), '
+                         f"sizeof((({m.c_struct} *)0)->{field[0]}));")
+            want.append((m.c_struct, field[0], (f.offset, f.size)))
+    lines += ["  return 0;", "}"]
+    cpp, exe = tmp_path / "layout.cpp", tmp_path / "layout"
+    cpp.write_text("\n".join(lines) + "\n")
+    subprocess.run(_host_compiler() + ["-I", HEADER_DIR, str(cpp), "-o", str(exe)], check=True)
+    got = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")[:-1]
+    assert len(got) == len(want) >= 300
+    bad = []
+    for (struct, what, value), line in zip(want, got):
+        nums = [int(v) for v in line.split()]
+        if (nums[0] if what == "sizeof" else tuple(nums)) != value:
+            bad.append(f"{struct}.{what}: header {line}, mirror {value}")
+    assert not bad, "\n".join(bad)
+
+
+def test_writing_a_name_that_is_no_field_of_a_mirror_raises():
+    """A mirror takes its fields only (empty __slots__): a stale field name is an AttributeError, on an instance and on an
+    element of an array, instead of a Python attribute the kernel never sees."""
+    assert len(_C.MIRRORS) >= 25
+    for m in _C.MIRRORS:
+        assert "not_a_field" not in [f[0] for f in m._fields_]
+        for obj in (m(), (m * 2)()[1]):
+            with pytest.raises(AttributeError):
+                obj.not_a_field = 1
+            first = m._fields_[0][0]
+            setattr(obj, first, 3)
+            assert getattr(obj, first) == 3
+
+
 def test_library_loads_and_exports_header_symbols():
     lib = _C.require()
     declared = _header_symbols()
