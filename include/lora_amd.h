@@ -903,6 +903,26 @@ int lora_amd_groupnorm_nhwc_bwd(const void *x, const void *gout, const void *gam
                                 void *workspace, size_t workspace_bytes, int32_t B, int32_t C, int32_t HW,
                                 int32_t groups, int32_t act, int32_t dtype, void *stream);
 
+/* The per-(sample, channel) term every ResnetBlock2D adds in front of its norm2, for all blocks in ONE launch:
+ *   out[out_offset + b * N + n] = float(rn(rn(dot(silu(temb[b]), weight[n]) + bias[n]) + conv_bias[n]))
+ * with silu(temb) rounded to the activation dtype first and rn = rounding to the activation dtype (the roundings of
+ * silu -> linear -> + conv bias -> .float(); conv_bias NULL: that add is skipped).  Site i owns the contiguous [B][N] f32
+ * block at out_offset, which is the `addend` of lora_amd_groupnorm_nhwc_fwd as it stands.  The table lives in device
+ * memory; row_begin is the running sum of N over the sites before this one (total_rows = the sum over all), N >= 1.
+ * weight [N][K] row-contiguous and temb [B][K] in the activation dtype, 16-byte (f32: 32-byte) aligned; K % 8 == 0 and
+ * B * K <= 15360 (the LDS image of silu(temb)); at most 256 sites.  Nothing outside the sites' blocks is written. */
+typedef struct lora_amd_temb_site {
+  const void *weight;    /* time_emb_proj.weight [N][K]                                     */
+  const void *bias;      /* time_emb_proj.bias [N]                                          */
+  const void *conv_bias; /* conv1.bias [N], or NULL                                         */
+  int32_t N;             /* output channels of the block                                    */
+  int32_t row_begin;     /* first row of this site in the launch                            */
+  int64_t out_offset;    /* element offset of the site's [B][N] block in `out`              */
+} lora_amd_temb_site;
+int lora_amd_temb_addends_supported(int32_t B, int32_t K, int32_t dtype);
+int lora_amd_temb_addends(const lora_amd_temb_site *sites_dev, int32_t n_sites, int64_t total_rows, const void *temb,
+                          float *out, int32_t B, int32_t K, int32_t dtype, void *stream);
+
 /* LayerNorm over the last dimension of row-contiguous x [M, K] (K % 8 == 0, K <= 2560; gamma / beta in the activation
  * dtype, frozen).  stats [M][2] f32 = (mean, rstd).  One launch each way. */
 int lora_amd_layernorm_supported(int32_t K);

@@ -261,10 +261,18 @@ class ReduceDesc(C.Structure):
                 ("reserved", C.c_int32), ("scale", C.c_float), ("beta", C.c_float)]
 
 
+class TembSite(C.Structure):
+    """lora_amd_temb_site: one ResnetBlock2D of the one-launch time-embedding addends."""
+    c_struct = "lora_amd_temb_site"
+    __slots__ = ()
+    _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("conv_bias", C.c_void_p), ("N", C.c_int32),
+                ("row_begin", C.c_int32), ("out_offset", C.c_int64)]
+
+
 # every struct of the header: c_struct names it; empty __slots__ make a write to a non-field an AttributeError
 MIRRORS = (AttnShortPlan, FactorsSelfPlan, SelfSite, FactorsMfmaPlan, PackSite, FmSite, RaggedDesc, SubDesc,
            PlanesDesc, SplitTDesc, ResidDesc, ThinSite, ThinQSite, ThinFinishDesc, SplitDesc, MergeSite, MstepSite,
-           MergeSummary, AdamWGroup, LinearPlan, ConvPlan, Conv3NhwcPlan, Conv3PackSite, WsSite, ReduceDesc)
+           MergeSummary, AdamWGroup, LinearPlan, ConvPlan, Conv3NhwcPlan, Conv3PackSite, WsSite, ReduceDesc, TembSite)
 
 
 # Every function of include/lora_amd.h, in header order: (name, restype, argtypes).  This table is the only place a
@@ -383,6 +391,8 @@ FUNCTIONS = (
     ("lora_amd_groupnorm_nhwc_workspace", sz, (i32, i32, i32, i32)),
     ("lora_amd_groupnorm_nhwc_fwd", cint, (vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, f32, i32, i32, vp)),
     ("lora_amd_groupnorm_nhwc_bwd", cint, (vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_temb_addends_supported", cint, (i32, i32, i32)),
+    ("lora_amd_temb_addends", cint, (vp, i32, i64, vp, vp, i32, i32, i32, vp)),
     ("lora_amd_layernorm_supported", cint, (i32,)),
     ("lora_amd_layernorm_fwd", cint, (vp, vp, vp, vp, vp, i64, i32, f32, i32, vp)),
     ("lora_amd_layernorm_bwd", cint, (vp, vp, vp, vp, vp, i64, i32, i32, vp)),
@@ -2240,6 +2250,68 @@ def groupnorm_nhwc_bwd(x: torch.Tensor, gout: torch.Tensor, gamma: torch.Tensor,
                                                  1 if act else 0, dtype_code(x.dtype), _stream()),
            "lora_amd_groupnorm_nhwc_bwd")
     return dx
+
+
+# ----------------------------------------------------------------------------- time-embedding addends (hostops.hip)
+TEMB_MAX_SITES = 256
+
+
+def temb_addends_supported(B: int, K: int, dtype: torch.dtype) -> bool:
+    """K % 8 == 0 and B * K <= 15360 (the LDS image of silu(temb)), one of the three activation dtypes."""
+    return dtype in _DT and bool(require().lora_amd_temb_addends_supported(B, K, _DT[dtype]))
+
+
+class TembTable:
+    """The device table of one launch of ``temb_addends``: ``sites`` = [(weight [N, K], bias [N], conv_bias [N] or None)],
+    all in one activation dtype on one device.  Site i owns ``out[offsets[i] : offsets[i] + B * N_i]`` (offsets are
+    multiples of 8 floats, in site order); the table holds pointers only, the values are read by every launch."""
+
+    def __init__(self, sites, B: int):
+        if not 0 < len(sites) <= TEMB_MAX_SITES:
+            raise ValueError(f"temb_addends: {len(sites)} sites (1..{TEMB_MAX_SITES})")
+        w0 = sites[0][0]
+        self.B, self.K, self.dtype, self.device = int(B), int(w0.shape[1]), w0.dtype, w0.device
+        align = 32 if self.dtype == torch.float32 else 16
+        arr = (TembSite * len(sites))()
+        self.offsets, self.widths = [], []
+        rows = off = 0
+        for q, (w, b, cb) in zip(arr, sites):
+            N = int(w.shape[0])
+            for t, shape in ((w, (N, self.K)), (b, (N,)), (cb, (N,))):
+                if t is None:
+                    continue
+                _dev_check(t)
+                if tuple(t.shape) != shape or t.dtype != self.dtype or t.device != self.device or not t.is_contiguous():
+                    raise ValueError("temb_addends: a site's tensors are contiguous [N, K] / [N] of one dtype and device")
+            if N < 1 or w.data_ptr() % align:
+                raise ValueError("temb_addends: empty site or unaligned weight")
+            q.weight, q.bias, q.conv_bias = w.data_ptr(), b.data_ptr(), _ptr(cb)
+            q.N, q.row_begin, q.out_offset = N, rows, off
+            self.offsets.append(off)
+            self.widths.append(N)
+            rows += N
+            off += -(-self.B * N // 8) * 8
+        self.n, self.rows, self.out_floats = len(sites), rows, off
+        self.ptrs = tuple(t.data_ptr() for site in sites for t in site if t is not None)
+        self.table = table_to_device(arr, self.device)
+
+    def slices(self, out: torch.Tensor):
+        """The [B, N_i] views of ``out`` in site order."""
+        return [out[o:o + self.B * n].view(self.B, n) for o, n in zip(self.offsets, self.widths)]
+
+
+def temb_addends(table: TembTable, temb: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One launch: every site's f32 addend block from ``temb`` [B, K]; returns the flat buffer (see TembTable.slices)."""
+    _dev_check(temb, out)
+    if tuple(temb.shape) != (table.B, table.K) or temb.dtype != table.dtype or not temb.is_contiguous():
+        raise ValueError("temb_addends: temb must be a contiguous [B, K] tensor of the table's dtype")
+    if out is None:
+        out = torch.empty(table.out_floats, dtype=torch.float32, device=temb.device)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < table.out_floats:
+        raise ValueError("temb_addends: out must be a contiguous float32 buffer of table.out_floats elements")
+    _check(require().lora_amd_temb_addends(table.table.data_ptr(), table.n, table.rows, temb.data_ptr(), out.data_ptr(),
+                                           table.B, table.K, dtype_code(table.dtype), _stream()), "lora_amd_temb_addends")
+    return out
 
 
 def add_layernorm_fwd(x: torch.Tensor, res: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,

@@ -895,6 +895,118 @@ __global__ __launch_bounds__(kHT) void gn_nhwc_bwd_finalize_kernel(const float *
   }
 }
 
+// ---- time-embedding addends of every ResnetBlock2D in one launch ------------------------------------------------------
+// Each block adds t = time_emb_proj(silu(temb)) + conv1.bias per (sample, channel) in front of its norm2; all of them depend
+// on temb and frozen parameters only.  One ragged launch over a table of sites replaces silu + skinny GEMM + bias add +
+// widening copy per block.  The kernel is a weight stream (sum N_i rows of K elements, read once): silu(temb) [B][K] sits
+// in LDS (rounded to the activation dtype as the separate silu's output is), a wave carries kTembRows weight rows through
+// the K loop together (one 16-byte chunk per lane, row and step) against up to BT samples (4 or 8: the products are the
+// kernel's VALU work, a batch of 4 must not pay for 8), then a butterfly folds the lanes.  Row g of the launch belongs to the site with row_begin <= g < row_begin + N; a wave's rows may straddle sites.
+constexpr int kTembRows = 4;     // weight rows a wave streams together
+constexpr int kTembGroups = 2;   // such row groups per wave (amortises the silu prologue)
+constexpr int kTembKU = 2;       // 64-chunk K steps in flight
+constexpr int kTembMaxSites = kHT;
+constexpr int kTembMaxImage = 15360;  // B * K elements: the f32 image is 60 KB of the 64 KB a workgroup may ask for
+constexpr int kTembBlockRows = (kHT / kWave) * kTembRows * kTembGroups;
+
+template <class E, int BT>
+__global__ __launch_bounds__(kHT) void temb_addends_kernel(const lora_amd_temb_site *__restrict__ sites, int n_sites,
+                                                           const typename E::storage *__restrict__ temb,
+                                                           float *__restrict__ out, int B, int K) {
+  using S = typename E::storage;
+  extern __shared__ __attribute__((aligned(32))) unsigned char s_raw[];
+  __shared__ int s_begin[kTembMaxSites];
+  S *s_x = reinterpret_cast<S *>(s_raw);  // [B][K] = round_E(silu(temb))
+  const int c8 = K / 8;
+  for (int i = threadIdx.x; i < B * c8; i += kHT) {
+    float v[8];
+    load8<E>(temb + (int64_t)i * 8, v);
+    Chunk8<E> c;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) c.v[e] = E::from_f(v[e] / (1.f + expf(-v[e])));  // the form ATen's silu evaluates
+    *reinterpret_cast<Chunk8<E> *>(s_x + (size_t)i * 8) = c;
+  }
+  if ((int)threadIdx.x < n_sites) s_begin[threadIdx.x] = gl(sites)[threadIdx.x].row_begin;
+  __syncthreads();
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  int si = 0;
+  for (int grp = 0; grp < kTembGroups; ++grp) {
+    const int64_t g0 = ((int64_t)blockIdx.x * (kHT / kWave) + wave) * (kTembRows * kTembGroups) + grp * kTembRows;
+    const S *wp[kTembRows];
+    float *op[kTembRows];
+    float bias_t[kTembRows], bias_c[kTembRows];
+    int n_of[kTembRows];
+    bool live[kTembRows], has_c[kTembRows];
+#pragma unroll
+    for (int j = 0; j < kTembRows; ++j) {
+      const int64_t g = g0 + j;
+      while (si + 1 < n_sites && g >= s_begin[si + 1]) ++si;
+      const lora_amd_temb_site LORA_AMD_AS_GLOBAL *q = gl(sites) + si;
+      const int64_t loc = g - s_begin[si];
+      n_of[j] = q->N;
+      live[j] = loc < n_of[j];  // past the last site's rows: stream row 0 of it, store nothing
+      const int64_t r = live[j] ? loc : 0;
+      wp[j] = reinterpret_cast<const S *>(q->weight) + r * K;
+      bias_t[j] = E::to_f(*gl(reinterpret_cast<const S *>(q->bias) + r));
+      has_c[j] = q->conv_bias != nullptr;
+      bias_c[j] = has_c[j] ? E::to_f(*gl(reinterpret_cast<const S *>(q->conv_bias) + r)) : 0.f;
+      op[j] = out + q->out_offset + r;
+    }
+    for (int bt = 0; bt < B; bt += BT) {
+      float acc[kTembRows][BT];
+#pragma unroll
+      for (int j = 0; j < kTembRows; ++j)
+#pragma unroll
+        for (int b = 0; b < BT; ++b) acc[j][b] = 0.f;
+      for (int c0 = 0; c0 < c8; c0 += kWave * kTembKU) {
+        Raw8<E> wr[kTembKU][kTembRows];
+#pragma unroll
+        for (int u = 0; u < kTembKU; ++u) {
+          const int c = c0 + u * kWave + lane, cs = c < c8 ? c : 0;
+#pragma unroll
+          for (int j = 0; j < kTembRows; ++j) wr[u][j] = load8_raw<E>(wp[j] + (int64_t)cs * 8);
+        }
+        LORA_AMD_LOADS_ISSUED();
+#pragma unroll
+        for (int u = 0; u < kTembKU; ++u) {
+          const int c = c0 + u * kWave + lane;
+          const bool okc = c < c8;
+          const int cs = okc ? c : 0;
+          float w[kTembRows][8];
+#pragma unroll
+          for (int j = 0; j < kTembRows; ++j) unpack8_sel<E>(wr[u][j], okc, w[j]);
+#pragma unroll
+          for (int b = 0; b < BT; ++b) {
+            const int bb = min(bt + b, B - 1);  // samples past B repeat the last one; their sums are not stored
+            const Chunk8<E> xc = *reinterpret_cast<const Chunk8<E> *>(s_x + (size_t)bb * K + (size_t)cs * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              const float xv = E::to_f(xc.v[e]);
+#pragma unroll
+              for (int j = 0; j < kTembRows; ++j) acc[j][b] = fmaf(w[j][e], xv, acc[j][b]);
+            }
+          }
+        }
+      }
+      // lanes 0..3 of the wave receive the totals of samples bt + 4 * h + idx4(lane); they apply the two bias adds with
+      // the roundings of the sequence this replaces: r1 = rn_E(dot + bias_t), r2 = rn_E(r1 + bias_c), stored as f32
+#pragma unroll
+      for (int j = 0; j < kTembRows; ++j) {
+#pragma unroll
+        for (int h = 0; h < BT / 4; ++h) {
+          const float tot = wave_sum4(acc[j][4 * h], acc[j][4 * h + 1], acc[j][4 * h + 2], acc[j][4 * h + 3], lane);
+          const int b = bt + 4 * h + idx4(lane);
+          if (lane < 4 && live[j] && b < B) {
+            float r = round_to<E>(tot + bias_t[j]);
+            if (has_c[j]) r = round_to<E>(r + bias_c[j]);
+            *gl(op[j] + (int64_t)b * n_of[j]) = r;
+          }
+        }
+      }
+    }
+  }
+}
+
 static inline bool aligned_for(const void *p, int dt) { return ((uintptr_t)p % (dt == LORA_AMD_F32 ? 32 : 16)) == 0; }
 
 }  // namespace lora_amd
@@ -1133,4 +1245,32 @@ extern "C" int lora_amd_groupnorm_nhwc_bwd(const void *x, const void *gout, cons
     });
   });
   return check_launch("lora_amd_groupnorm_nhwc_bwd");
+}
+
+// ---- time-embedding addends entry points ------------------------------------------------------------------------------
+extern "C" int lora_amd_temb_addends_supported(int32_t B, int32_t K, int32_t dtype) {
+  return B > 0 && K > 0 && K % 8 == 0 && (int64_t)B * K <= kTembMaxImage && dtype_ok(dtype) ? 1 : 0;
+}
+
+extern "C" int lora_amd_temb_addends(const lora_amd_temb_site *sites_dev, int32_t n_sites, int64_t total_rows,
+                                     const void *temb, float *out, int32_t B, int32_t K, int32_t dtype, void *stream) {
+  LORA_AMD_CHECK(lora_amd_temb_addends_supported(B, K, dtype), LORA_AMD_EINVAL,
+                 "temb_addends: B=%d K=%d dtype=%d not supported (K %% 8 == 0, B * K <= %d)", B, K, dtype, kTembMaxImage);
+  LORA_AMD_CHECK(n_sites >= 0 && n_sites <= kTembMaxSites && total_rows >= 0 && total_rows < (1ll << 31),
+                 LORA_AMD_EINVAL, "temb_addends: %d sites / %lld rows (at most %d sites)", n_sites, (long long)total_rows,
+                 kTembMaxSites);
+  if (n_sites == 0 || total_rows == 0) return LORA_AMD_OK;
+  LORA_AMD_CHECK(sites_dev && temb && out, LORA_AMD_EINVAL, "temb_addends: null pointer");
+  LORA_AMD_CHECK(aligned_for(temb, dtype) && ((uintptr_t)out % 4) == 0 && ((uintptr_t)sites_dev % 8) == 0, LORA_AMD_EINVAL,
+                 "temb_addends: unaligned tensor");
+  const dim3 grid((unsigned)((total_rows + kTembBlockRows - 1) / kTembBlockRows)), block(kHT);
+  const size_t lds = (size_t)B * K * dtype_size(dtype);
+  by_dtype(dtype, [&](auto e) {
+    using S = typename decltype(e)::storage;
+    by_int<4, 8>(B <= 4 ? 4 : 8, [&](auto bt) {  // samples per pass over the weights
+      hipLaunchKernelGGL((temb_addends_kernel<decltype(e), decltype(bt)::value>), grid, block, lds, (hipStream_t)stream,
+                         sites_dev, n_sites, (const S *)temb, out, B, K);
+    });
+  });
+  return check_launch("lora_amd_temb_addends");
 }

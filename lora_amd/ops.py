@@ -578,13 +578,17 @@ MASTER_MERGE = True
 # stays on the library kernel standin/attention.py picks); False = the library's backward
 # (tests/test_attn_short_route.py runs both)
 ATTN_SHORT_BWD = True
+# the time-embedding term of every ResnetBlock2D (silu, time_emb_proj, + conv1.bias, widening) from ONE launch at the top of
+# the UNet forward (csrc/hostops.hip temb_addends); False = the four launches per block
+# (tests/test_resnet_glue_route.py runs both)
+TEMB_ONE_LAUNCH = True
 
 
 def apply_ab_overrides(spec: str, namespace: dict) -> dict:
     """``LORA_AMD_AB="NAME=0,OTHER=1"``: the ONE measurement switch for same-box A/B runs — flips the module constants
     listed in ``allowed`` (and only those) without a code edit; every A/B log under profiles/ names the spec it ran with
     (a constant retired since then is an unknown name here)."""
-    allowed = ("ATTN_SHORT_BWD", "CONCAT_GROUPS", "CONV3_FUSED", "MASTER_MERGE", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
+    allowed = ("ATTN_SHORT_BWD", "CONCAT_GROUPS", "CONV3_FUSED", "MASTER_MERGE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
                "WS_DROPOUT_WIDE_BWD")
     done = {}
     for item in filter(None, (s.strip() for s in spec.split(","))):

@@ -21,7 +21,9 @@ import torch.nn.functional as F
 
 from . import attention
 from .attention import sdpa
+from . import fused
 from .fused import add_layer_norm, geglu, group_norm_act, layer_norm
+from .. import _C, ops
 from torch.utils.checkpoint import checkpoint
 
 
@@ -33,6 +35,17 @@ class UNetOutput:
 
     def __getitem__(self, i):
         return (self.sample,)[i]
+
+
+class TembAddends:
+    """``temb`` together with the finished norm2 addend [B, C_out] (f32) of every ResnetBlock2D that the one launch at the
+    top of the forward covers (``UNet2DConditionModel._temb_addends``); a block that is not in ``addends`` computes its own
+    from ``temb``.  Travels in the ``temb`` argument of the blocks, through ``checkpoint`` as well (a recompute reads the
+    forward's values again)."""
+    __slots__ = ("temb", "addends")
+
+    def __init__(self, temb: torch.Tensor, addends: dict):
+        self.temb, self.addends = temb, addends
 
 
 class Timesteps(nn.Module):
@@ -247,7 +260,18 @@ class ResnetBlock2D(nn.Module):
         self.conv_shortcut = nn.Conv2d(in_channels, out_channels, 1) if in_channels != out_channels else None
 
     def forward(self, x, temb):
+        """``temb``: a tensor or :class:`TembAddends`."""
         n1 = group_norm_act(x, self.norm1)  # GroupNorm + SiLU as HIP passes (fused.py)
+        t = None
+        if isinstance(temb, TembAddends):
+            t, temb = temb.addends.get(self), temb.temb
+        if t is not None:
+            # silu, the projection and both biases came out of the one launch at the top of the forward, as the f32 [B, C]
+            # term norm2 takes
+            c1 = self.conv1
+            h = F.conv2d(n1, c1.weight, None, c1.stride, c1.padding, c1.dilation, c1.groups)
+            h = self.conv2(self.dropout(group_norm_act(h, self.norm2, addend=t)))
+            return (x if self.conv_shortcut is None else self.conv_shortcut(x)) + h
         t = self.time_emb_proj(self.nonlinearity(temb))  # [B, C_out]
         if type(self.conv1) is nn.Conv2d and self.conv1.bias is not None:
             # the convolution's bias and the time embedding are both per-(sample, channel) terms in front of norm2:
@@ -393,6 +417,8 @@ class UNet2DConditionModel(nn.Module):
         self.conv_act = nn.SiLU()
         self.conv_out = nn.Conv2d(ch[0], out_channels, 3, padding=1)
         self._grad_ckpt = False
+        self._resnets = None
+        self._temb_table = None   # _C.TembTable of the eligible blocks: pointers only, rebuilt when one of them changes
 
     @property
     def device(self):
@@ -416,6 +442,40 @@ class UNet2DConditionModel(nn.Module):
             return checkpoint(blk, *a, use_reentrant=False)
         return blk(*a)
 
+    def _temb_addends(self, temb: torch.Tensor, nhwc: bool):
+        """``temb`` or, where the one-launch kernel applies (ops.TEMB_ONE_LAUNCH), a :class:`TembAddends` with the norm2
+        addend of every eligible ResnetBlock2D: plain ``time_emb_proj`` / ``conv1`` with biases, frozen, in temb's dtype.
+        The per-block path stays for everything else: CPU, LORA_AMD_HOSTOPS=0, NCHW activations, a trained temb or
+        projection, an unsupported shape."""
+        if not (ops.TEMB_ONE_LAUNCH and fused._ENABLED and nhwc and temb.is_cuda and temb.dim() == 2
+                and temb.is_contiguous() and not (torch.is_grad_enabled() and temb.requires_grad)
+                and temb.dtype in fused._DTYPES and _C.temb_addends_supported(temb.shape[0], temb.shape[1], temb.dtype)):
+            return temb
+        if self._resnets is None:  # the blocks themselves are never replaced, only their children
+            self._resnets = [m for m in self.modules() if isinstance(m, ResnetBlock2D)]
+        blocks, sites = [], []
+        for m in self._resnets:
+            lin, c1 = m.time_emb_proj, m.conv1
+            if type(lin) is not nn.Linear or type(c1) is not nn.Conv2d or lin.bias is None or c1.bias is None:
+                continue
+            ps = (lin.weight, lin.bias, c1.bias)
+            if any(p.requires_grad and torch.is_grad_enabled() for p in ps) or any(
+                    p.dtype != temb.dtype or p.device != temb.device or not p.is_contiguous() for p in ps):
+                continue
+            if lin.in_features != temb.shape[1] or lin.weight.data_ptr() % 32:
+                continue
+            blocks.append(m)
+            sites.append(ps)
+        if not sites or len(sites) > _C.TEMB_MAX_SITES:
+            return temb
+        ptrs = tuple(p.data_ptr() for ps in sites for p in ps)
+        tab = self._temb_table
+        if tab is None or tab.ptrs != ptrs or tab.B != temb.shape[0] or tab.dtype != temb.dtype \
+                or tab.device != temb.device:
+            tab = self._temb_table = _C.TembTable(sites, temb.shape[0])
+        out = _C.temb_addends(tab, temb.detach())
+        return TembAddends(temb, dict(zip(blocks, tab.slices(out))))
+
     def forward(self, sample, timestep, encoder_hidden_states) -> UNetOutput:
         if not torch.is_tensor(timestep):
             timestep = torch.tensor([timestep], dtype=torch.long, device=sample.device)
@@ -424,6 +484,7 @@ class UNet2DConditionModel(nn.Module):
         timestep = timestep.expand(sample.shape[0])
         temb = self.time_embedding(self.time_proj(timestep).to(self.time_embedding.linear_1.weight.dtype))
         h = self.conv_in(sample)
+        temb = self._temb_addends(temb, h.is_contiguous(memory_format=torch.channels_last) and not h.is_contiguous())
         skips = [h]
         for blk in self.down_blocks:
             h, outs = self._run(blk, h, temb, encoder_hidden_states)

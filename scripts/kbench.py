@@ -790,6 +790,35 @@ def bench_attn(args):
         print(json.dumps({k_: (round(v_, 2) if isinstance(v_, float) else v_) for k_, v_ in res.items()}), flush=True)
 
 
+# out channels of SD1.5's 22 ResnetBlock2D in module order (down 8, up 12, mid 2): 20 160 rows of time_emb_proj weight
+SD15_RESNET_WIDTHS = [320, 320, 640, 640, 1280, 1280, 1280, 1280] + [1280] * 6 + [640] * 3 + [320] * 3 + [1280, 1280]
+
+
+def bench_temb(args):
+    """The time-embedding addends of every ResnetBlock2D: the one ragged launch (csrc/hostops.hip) against the ATen sequence
+    it replaces (silu, skinny GEMM, + conv bias, widening copy per block: 88 launches), at SD1.5's table, next to the time
+    the weight stream takes at the 6.29 TB/s copy ceiling."""
+    F = torch.nn.functional
+    K = 1280
+    for B, dt in ((4, torch.bfloat16), (8, torch.bfloat16)):
+        temb = torch.randn(B, K, device=DEV, dtype=dt)
+        sites = [((torch.randn(n, K, device=DEV) * K ** -0.5).to(dt), torch.randn(n, device=DEV).to(dt),
+                  torch.randn(n, device=DEV).to(dt)) for n in SD15_RESNET_WIDTHS]
+        table = _C.TembTable(sites, B)
+        out = torch.empty(table.out_floats, dtype=torch.float32, device=DEV)
+
+        def aten():
+            return [(F.linear(F.silu(temb), w, b) + cb).to(torch.float32) for w, b, cb in sites]
+
+        nbytes = sum(w.numel() + 2 * w.shape[0] for w, _, _ in sites) * temb.element_size() + 4 * B * table.rows
+        res = {"op": "temb_addends", "B": B, "K": K, "sites": table.n, "rows": table.rows, "bytes": nbytes,
+               "floor_us": nbytes / 6.29e6,
+               "hip_us": timeit(lambda: _C.temb_addends(table, temb, out=out), args.iters)[0] * 1e6,
+               "aten_88_launches_us": timeit(aten, args.iters, inner=5)[0] * 1e6}
+        res["hip_x_floor"] = res["hip_us"] / res["floor_us"]
+        print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in res.items()}), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="merge,linear,ws,conv,hostops")
@@ -825,3 +854,5 @@ if __name__ == "__main__":
         bench_gemm_layouts(a)
     if "attn" in a.what.split(","):
         bench_attn(a)
+    if "temb" in a.what.split(","):
+        bench_temb(a)
