@@ -891,7 +891,7 @@ int lora_amd_groupnorm_bwd(const void *x, const void *gout, const void *gamma, c
                            int32_t C, int32_t HW, int32_t groups, int32_t act, int32_t dtype, void *stream);
 
 /* The same for channels_last activations (memory [B][HW][C], C % 8 == 0): aff [B][4][C] f32 receives the per-channel
- * (gamma*rstd, beta - mean*gamma*rstd, mean, rstd) the backward needs.  Three launches each way.
+ * (gamma*rstd, beta - mean*gamma*rstd, mean, rstd) the backward needs.  Three launches each way (one on the small maps, below).
  * `addend` [B][C] f32 (or NULL) is added to x before the normalisation (time-embedding projection + the bias of the
  * producing convolution in ResnetBlock2D) at no streaming cost; it is folded into aff, the backward needs no change
  * (the gradient w.r.t. the addend is the per-(sample, channel) sum of dx). */
@@ -902,6 +902,14 @@ int lora_amd_groupnorm_nhwc_fwd(const void *x, const void *gamma, const void *be
 int lora_amd_groupnorm_nhwc_bwd(const void *x, const void *gout, const void *gamma, const float *aff, void *dx,
                                 void *workspace, size_t workspace_bytes, int32_t B, int32_t C, int32_t HW,
                                 int32_t groups, int32_t act, int32_t dtype, void *stream);
+/* Where a bundle of lcm(C / groups, 8) channels of one sample fits in one workgroup's registers (maps up to 32x32 forward,
+ * 16x16 backward at SD1.5's widths), the two entry points above run ONE resident launch instead of three; same arguments,
+ * same aff, the workspace is then left untouched.  The choice depends on the geometry only.  Host-only hooks:
+ * lora_amd_groupnorm_nhwc_resident: 0 sends every geometry to the streaming kernels (the parity twin), 1 (default) routes by
+ * geometry, < 0 only reads; returns the previous value.  lora_amd_groupnorm_nhwc_route: 1 if that launch would run resident
+ * under the current setting, 0 for streaming, LORA_AMD_EINVAL for a geometry the entry points refuse. */
+int lora_amd_groupnorm_nhwc_resident(int32_t enable);
+int lora_amd_groupnorm_nhwc_route(int32_t B, int32_t C, int32_t HW, int32_t groups, int32_t dtype, int32_t backward);
 
 /* The per-(sample, channel) term every ResnetBlock2D adds in front of its norm2, for all blocks in ONE launch:
  *   out[out_offset + b * N + n] = float(rn(rn(dot(silu(temb[b]), weight[n]) + bias[n]) + conv_bias[n]))

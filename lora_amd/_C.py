@@ -391,6 +391,8 @@ FUNCTIONS = (
     ("lora_amd_groupnorm_nhwc_workspace", sz, (i32, i32, i32, i32)),
     ("lora_amd_groupnorm_nhwc_fwd", cint, (vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, f32, i32, i32, vp)),
     ("lora_amd_groupnorm_nhwc_bwd", cint, (vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_groupnorm_nhwc_resident", cint, (i32,)),
+    ("lora_amd_groupnorm_nhwc_route", cint, (i32, i32, i32, i32, i32, i32)),
     ("lora_amd_temb_addends_supported", cint, (i32, i32, i32)),
     ("lora_amd_temb_addends", cint, (vp, i32, i64, vp, vp, i32, i32, i32, vp)),
     ("lora_amd_layernorm_supported", cint, (i32,)),
@@ -2250,6 +2252,19 @@ def groupnorm_nhwc_bwd(x: torch.Tensor, gout: torch.Tensor, gamma: torch.Tensor,
                                                  1 if act else 0, dtype_code(x.dtype), _stream()),
            "lora_amd_groupnorm_nhwc_bwd")
     return dx
+
+
+def groupnorm_nhwc_resident(enable: int = -1) -> int:
+    """Resident (one-launch) form of the channels_last GroupNorm on / off; < 0 only reads; returns the previous setting."""
+    return int(require().lora_amd_groupnorm_nhwc_resident(int(enable)))
+
+
+def groupnorm_nhwc_route(B: int, C_: int, HW: int, groups: int, dtype: torch.dtype, backward: bool) -> bool:
+    """True if ``groupnorm_nhwc_fwd`` / ``_bwd`` of this geometry runs the resident kernel under the current setting."""
+    rc = int(require().lora_amd_groupnorm_nhwc_route(B, C_, HW, groups, dtype_code(dtype), 1 if backward else 0))
+    if rc < 0:
+        _check(rc, "lora_amd_groupnorm_nhwc_route")
+    return rc == 1
 
 
 # ----------------------------------------------------------------------------- time-embedding addends (hostops.hip)

@@ -5,7 +5,9 @@
 //   GroupNorm (+ SiLU)   ResnetBlock2D.norm1/norm2 + nonlinearity, Transformer2DModel.norm, conv_norm_out
 //                        ATen: 4 launches forward (moments, fused params, normalise, silu), 5 backward, and it
 //                        keeps the normalised tensor AND the SiLU input alive for backward.
-//                        Here: 2 launches each way (slice statistics, apply), only x and [B,G] (mean, rstd) kept.
+//                        Here: NCHW 2 launches each way (slice statistics, apply), only x and [B,G] (mean, rstd) kept;
+//                        channels_last 3 each way (statistics, finalize, apply), or ONE where a bundle of groups fits in
+//                        a workgroup's registers (maps up to 32x32); only x and the per-channel aff [B,4,C] kept.
 //   GEGLU gate           GEGLU.forward right behind the adapted `proj` (lora_diffusion/lora.py:14 targets GEGLU):
 //                        h * gelu(gate): ATen = chunk, gelu, mul (5 tensor passes) forward and
 //                        gelu_backward, 2 mul, cat (13 passes) backward.  Here: one launch each way (3 / 5 passes);
@@ -16,6 +18,7 @@
 // that ~1000 workgroups are in flight even when B*G = 128.  Affine parameters are frozen (the reference trains only
 // the LoRA factors), so no dgamma / dbeta is produced; callers that train them must use the library path.
 #include <algorithm>
+#include <atomic>
 
 #include "common.hpp"
 
@@ -574,7 +577,8 @@ static inline int ln_logL(int c8) {
 // pixel (contiguous runs of cw * 16 bytes).  Statistics are per channel and per pixel slice (shifted sums -> mean, M2),
 // a tiny finalize kernel folds slices and the group's channels together (Chan) and expands the result per channel:
 //   aff[b][0][c] = gamma*rstd, aff[b][1][c] = beta - mean*gamma*rstd, aff[b][2][c] = mean, aff[b][3][c] = rstd
-// so that the apply kernels are pure per-channel affine maps.  3 + 3 launches; MIOpen's NHWC kernels then need no
+// so that the apply kernels are pure per-channel affine maps.  3 + 3 launches (1 + 1 on the maps the resident form further
+// down holds); MIOpen's NHWC kernels then need no
 // NCHW<->NHWC transposes around them and the transformer blocks read the activations as tokens without a copy.
 constexpr int kNU = 4;  // pixels in flight per thread
 
@@ -895,6 +899,269 @@ __global__ __launch_bounds__(kHT) void gn_nhwc_bwd_finalize_kernel(const float *
   }
 }
 
+// ---- resident form: one launch each way on the small maps ----------------------------------------------------------------
+// Where a whole (sample, bundle of groups) fits in one workgroup's registers, the statistics, the affine map and the store
+// (forward), or both reductions and dx (backward), come from ONE read of each operand.  A bundle is lcm(cpg, 8) adjacent
+// channels: a whole number of groups and of 16-byte chunks.  The mapping is the streaming kernels' (thread = pixel slot x
+// chunk of the bundle); a thread keeps its NP pixels' chunks raw in registers.  One workgroup owns everything it reduces:
+// no workgroup waits for, counts or signals another, and the workspace is not touched.  Every fold runs in a fixed order
+// (two launches give the same bits): per-thread channel sums -> LDS -> T / groups threads per group -> wave butterfly.
+constexpr int kResMaxChunks = 32;  // chunks per bundle (256 channels)
+constexpr int kResMaxGroups = 8;   // groups per bundle = lcm(cpg, 8) / cpg <= 8
+
+// a / b for 0 <= a < 2^22, 1 <= b: one reciprocal and a correction step instead of the ~35-instruction integer division
+// (a resident kernel is a latency chain; a dozen divisions in front of its loads were a third of its time)
+__device__ inline int res_div(int a, int b) {
+  int q = (int)((float)a * fast_rcp((float)b));
+  const int r = a - q * b;
+  q += r >= b ? 1 : (r < 0 ? -1 : 0);
+  return q;
+}
+
+struct ResBlock {
+  int b, slot, cl, col;
+  bool active;
+  int64_t base;  // element offset of (b, pixel 0, this thread's chunk)
+  int grp[8];    // bundle-local group of each of the chunk's channels
+};
+__device__ inline ResBlock res_block(int C, int HW, int cpg, int nch, int nslots) {
+  ResBlock k;
+  const int nb = res_div(C >> 3, nch);
+  k.b = res_div(blockIdx.x, nb);
+  const int bun = blockIdx.x - k.b * nb;
+  k.slot = res_div(threadIdx.x, nch);
+  k.cl = threadIdx.x - k.slot * nch;
+  k.active = k.slot < nslots;
+  k.col = bun * nch + k.cl;
+  k.base = (int64_t)k.b * HW * C + (int64_t)k.col * 8;
+  int g = res_div(k.cl * 8, cpg), r = k.cl * 8 - g * cpg;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    k.grp[e] = g;
+    if (++r == cpg) {
+      r = 0;
+      ++g;
+    }
+  }
+  return k;
+}
+
+template <int T, int NQ>
+struct ResLds {
+  float red[NQ][T * 8];  // [slot][bundle channel]
+  float wp[NQ][T / 32];  // wave (or half-wave) partials, a group's side by side
+};
+
+// Sums of s[q] over the bundle's pixel slots and each group's channels -> gs[q][group of the bundle], visible to every
+// thread on return.  T / groups threads fold one group: a strided walk over its (slot, channel) entries, a butterfly over
+// the wave, then the group's wave partials in order; fin maps the total to what the threads read (mean, rstd).
+template <int T, int NQ, class Fin>
+__device__ inline void res_group_sum(const float (&s)[NQ][8], const ResBlock &k, int bch, int nslots, int cpg,
+                                     ResLds<T, NQ> &l, float (*gs)[kResMaxGroups], Fin fin) {
+  const int tid = threadIdx.x;
+  __syncthreads();  // the previous fold's readers are done
+  if (k.active) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) st8f(l.red[q] + (size_t)tid * 8, s[q]);
+  }
+  __syncthreads();
+  const int ng = res_div(bch, cpg);  // 1, 2, 4 or 8
+  const int lg = ng == 1 ? 0 : ng == 2 ? 1 : ng == 4 ? 2 : 3;
+  const int L = T >> lg, g = tid >> (__builtin_ctz(T) - lg), lane = tid - g * L;
+  const int n = nslots * cpg, dq = res_div(L, cpg), dr = L - dq * cpg;
+  int sl = res_div(lane, cpg), c = lane - sl * cpg;
+  float a[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) a[q] = 0.f;
+#pragma unroll 4
+  for (int i = lane; i < n; i += L) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) a[q] += l.red[q][sl * bch + g * cpg + c];
+    sl += dq;
+    c += dr;
+    if (c >= cpg) {
+      c -= cpg;
+      ++sl;
+    }
+  }
+  const int W = L < 64 ? L : 64;  // T / 8 >= 32
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    if (off < W) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) a[q] += __shfl_xor(a[q], off, 64);
+    }
+  }
+  if ((tid & (W - 1)) == 0) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) l.wp[q][tid >> (W == 64 ? 6 : 5)] = a[q];
+  }
+  __syncthreads();
+  if (tid < ng) {
+    const int P = L >> (W == 64 ? 6 : 5);
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      float t = 0.f;
+      for (int i = 0; i < P; ++i) t += l.wp[q][tid * P + i];
+      gs[q][tid] = fin(t);
+    }
+  }
+  __syncthreads();
+}
+
+template <class E, bool ACT, int T, int NP>
+__global__ __launch_bounds__(T) void gn_nhwc_res_fwd_kernel(const typename E::storage *__restrict__ x,
+                                                            const typename E::storage *__restrict__ gamma,
+                                                            const typename E::storage *__restrict__ beta,
+                                                            const float *__restrict__ addend,
+                                                            typename E::storage *__restrict__ y, float *__restrict__ aff,
+                                                            int C, int HW, int cpg, int nch, int nslots, float eps) {
+  __shared__ __attribute__((aligned(16))) ResLds<T, 1> l;
+  __shared__ float gs[2][kResMaxGroups];
+  const ResBlock k = res_block(C, HW, cpg, nch, nslots);
+  Raw8<E> raw[NP];
+#pragma unroll
+  for (int u = 0; u < NP; ++u) {
+    const int p = k.slot + u * nslots;
+    raw[u] = load8_raw<E>(x + k.base + (int64_t)(k.active && p < HW ? p : 0) * C);
+  }
+  float gam[8], bet[8], add[8];
+  unpack8_sel<E>(load8_raw<E>(gamma + (int64_t)k.col * 8), true, gam);
+  unpack8_sel<E>(load8_raw<E>(beta + (int64_t)k.col * 8), true, bet);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) add[e] = 0.f;
+  if (addend != nullptr) ld8f_sel(addend + (int64_t)k.b * C + (int64_t)k.col * 8, true, add);
+  LORA_AMD_LOADS_ISSUED();
+  const int bch = nch * 8;
+  const float inv_n = 1.f / ((float)HW * (float)cpg);
+  float s[1][8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s[0][e] = k.slot == 0 ? (float)HW * add[e] : 0.f;  // the addend's share of the channel total
+#pragma unroll
+  for (int u = 0; u < NP; ++u) {
+    float v[8];
+    unpack8_sel<E>(raw[u], k.active && k.slot + u * nslots < HW, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[0][e] += v[e];
+  }
+  res_group_sum<T, 1>(s, k, bch, nslots, cpg, l, &gs[0], [=](float t) { return t * inv_n; });  // group means
+  float sh[8];  // add - mean: the shift of x in front of the normalisation
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    sh[e] = add[e] - gs[0][k.grp[e]];
+    s[0][e] = 0.f;
+  }
+#pragma unroll
+  for (int u = 0; u < NP; ++u) {
+    float v[8];
+    unpack8_sel<E>(raw[u], true, v);
+    if (k.active && k.slot + u * nslots < HW) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float d = v[e] + sh[e];
+        s[0][e] = fmaf(d, d, s[0][e]);
+      }
+    }
+  }
+  res_group_sum<T, 1>(s, k, bch, nslots, cpg, l, &gs[1], [=](float t) { return rsqrtf(t * inv_n + eps); });
+  float ga[8], bb[8], mn[8], rs[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    rs[e] = gs[1][k.grp[e]];
+    ga[e] = gam[e] * rs[e];
+    bb[e] = fmaf(sh[e], ga[e], bet[e]);
+    mn[e] = -sh[e];
+  }
+  if (k.slot == 0) {
+    float *o = aff + (int64_t)k.b * 4 * C + (int64_t)k.col * 8;
+    st8f(o, ga);
+    st8f(o + C, bb);
+    st8f(o + 2 * C, mn);
+    st8f(o + 3 * C, rs);
+  }
+#pragma unroll
+  for (int u = 0; u < NP; ++u) {
+    const int p = k.slot + u * nslots;
+    if (k.active && p < HW) {
+      float v[8], o[8];
+      unpack8_sel<E>(raw[u], true, v);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float z = fmaf(v[e], ga[e], bb[e]);
+        o[e] = ACT ? z * sigmoidf(z) : z;
+      }
+      store8<E>(y + k.base + (int64_t)p * C, o);
+    }
+  }
+}
+
+template <class E, bool ACT, int T, int NP>
+__global__ __launch_bounds__(T) void gn_nhwc_res_bwd_kernel(const typename E::storage *__restrict__ x,
+                                                            const typename E::storage *__restrict__ gout,
+                                                            const typename E::storage *__restrict__ gamma,
+                                                            const float *__restrict__ aff,
+                                                            typename E::storage *__restrict__ dx, int C, int HW, int cpg,
+                                                            int nch, int nslots) {
+  __shared__ __attribute__((aligned(16))) ResLds<T, 2> l;
+  __shared__ float gs[2][kResMaxGroups];
+  const ResBlock k = res_block(C, HW, cpg, nch, nslots);
+  Raw8<E> xr[NP], gr[NP];
+#pragma unroll
+  for (int u = 0; u < NP; ++u) {
+    const int p = k.slot + u * nslots;
+    const int64_t off = k.base + (int64_t)(k.active && p < HW ? p : 0) * C;
+    xr[u] = load8_raw<E>(x + off);
+    gr[u] = load8_raw<E>(gout + off);
+  }
+  float ga[8], be[8], mean[8], rstd[8], gam[8];
+  const float *ab = aff + (int64_t)k.b * 4 * C + (int64_t)k.col * 8;
+  ld8f_sel(ab, true, ga);
+  ld8f_sel(ab + C, true, be);
+  ld8f_sel(ab + 2 * C, true, mean);
+  ld8f_sel(ab + 3 * C, true, rstd);
+  unpack8_sel<E>(load8_raw<E>(gamma + (int64_t)k.col * 8), true, gam);
+  LORA_AMD_LOADS_ISSUED();
+  const int bch = nch * 8;
+  float s[2][8];  // sum t, sum t * xh
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s[0][e] = s[1][e] = 0.f;
+#pragma unroll
+  for (int u = 0; u < NP; ++u) {
+    float v[8], go[8], t[8], xh[8];
+    unpack8_sel<E>(xr[u], true, v);
+    unpack8_sel<E>(gr[u], true, go);
+    gn_nhwc_terms<E, ACT>(v, go, ga, be, mean, rstd, gam, t, xh);
+    if (k.active && k.slot + u * nslots < HW) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        s[0][e] += t[e];
+        s[1][e] = fmaf(t[e], xh[e], s[1][e]);
+      }
+    }
+  }
+  const float inv_n = 1.f / ((float)HW * (float)cpg);
+  res_group_sum<T, 2>(s, k, bch, nslots, cpg, l, gs, [=](float t) { return t * inv_n; });
+  float c1[8], c2[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    c1[e] = gs[0][k.grp[e]];
+    c2[e] = gs[1][k.grp[e]];
+  }
+#pragma unroll
+  for (int u = 0; u < NP; ++u) {
+    const int p = k.slot + u * nslots;
+    if (k.active && p < HW) {
+      float v[8], go[8], t[8], xh[8], o[8];
+      unpack8_sel<E>(xr[u], true, v);
+      unpack8_sel<E>(gr[u], true, go);
+      gn_nhwc_terms<E, ACT>(v, go, ga, be, mean, rstd, gam, t, xh);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = rstd[e] * (t[e] - c1[e] - xh[e] * c2[e]);
+      store8<E>(dx + k.base + (int64_t)p * C, o);
+    }
+  }
+}
+
 // ---- time-embedding addends of every ResnetBlock2D in one launch ------------------------------------------------------
 // Each block adds t = time_emb_proj(silu(temb)) + conv1.bias per (sample, channel) in front of its norm2; all of them depend
 // on temb and frozen parameters only.  One ragged launch over a table of sites replaces silu + skinny GEMM + bias add +
@@ -1188,6 +1455,78 @@ extern "C" size_t lora_amd_groupnorm_nhwc_workspace(int32_t B, int32_t C, int32_
   return q.ok ? (gn_nhwc_part_floats(q, B, C) + (size_t)B * 2 * C) * sizeof(float) : 0;
 }
 
+// Resident route (gn_nhwc_res_*_kernel).  The (workgroup size, pixels per thread) forms that exist, in the order tried.
+// A thread's raw registers are NP chunks of 4 (16-bit) or 8 (f32) dwords, twice that backward; they must leave room for
+// the working set (five per-channel vectors, the sums, one pixel's terms) inside the 256 registers a lane of a 512-thread
+// workgroup has.  The bounds are the compiler's verdict, not an estimate: profiles/gn_resident_resources.txt lists every
+// instantiation with scratch 0.  Forms that spilled when tried (1024 threads x 8 or 16 pixels forward, 512 x 16 16-bit
+// backward) do not exist; their geometries stay on the streaming kernels.
+struct GnResForm {
+  int T, NP;
+};
+constexpr GnResForm kResForms[] = {{256, 2}, {512, 4}, {512, 8}, {512, 16}};
+constexpr int kResNForms = (int)(sizeof(kResForms) / sizeof(kResForms[0]));
+constexpr int res_raw_regs(int form, int esize, bool bwd) { return kResForms[form].NP * esize * 2 * (bwd ? 2 : 1); }
+constexpr bool res_form_fits(int form, int esize, bool bwd) { return res_raw_regs(form, esize, bwd) <= (bwd ? 64 : 128); }
+
+struct GnResPlan {
+  int form, cpg, nch, nslots;  // form < 0: no resident form holds this geometry
+  unsigned grid;
+};
+static GnResPlan gn_nhwc_res_plan(int B, int C, int HW, int G, int dtype, bool bwd) {
+  GnResPlan p{-1, 0, 0, 0, 0};
+  p.cpg = C / G;
+  int bch = p.cpg;
+  while (bch % 8) bch += p.cpg;  // lcm(cpg, 8)
+  p.nch = bch / 8;
+  if (p.nch > kResMaxChunks || (int64_t)B * (C / bch) >= (1 << 22)) return p;  // res_div's range
+  p.grid = (unsigned)(B * (C / bch));
+  for (int f = 0; f < kResNForms; ++f) {
+    const int nslots = std::min(kResForms[f].T / p.nch, HW);
+    if (!res_form_fits(f, dtype_size(dtype), bwd) || (int64_t)nslots * kResForms[f].NP < HW) continue;
+    p.form = f;
+    p.nslots = nslots;
+    break;
+  }
+  return p;
+}
+
+static std::atomic<int> g_gn_resident{1};
+
+// The measured half of the rule (profiles/gn_resident_kbench.txt, graph-timed per geometry of the flagship step): the
+// resident launch beat the three streaming launches at every geometry a form holds, so capacity alone decides.
+static bool gn_nhwc_res_faster(int B, int C, int HW, int G, int dtype, bool bwd) {
+  (void)B, (void)C, (void)HW, (void)G, (void)dtype, (void)bwd;
+  return true;
+}
+
+// 1 = resident, 0 = streaming; a pure function of the geometry (a captured graph replays the same kernels everywhere)
+static int gn_nhwc_route(int B, int C, int HW, int G, int dtype, int dir) {
+  if (!g_gn_resident.load(std::memory_order_relaxed)) return 0;
+  return gn_nhwc_res_plan(B, C, HW, G, dtype, dir != 0).form >= 0 && gn_nhwc_res_faster(B, C, HW, G, dtype, dir != 0) ? 1 : 0;
+}
+
+extern "C" int lora_amd_groupnorm_nhwc_resident(int32_t enable) {
+  const int prev = g_gn_resident.load(std::memory_order_relaxed);
+  if (enable >= 0) g_gn_resident.store(enable ? 1 : 0, std::memory_order_relaxed);
+  return prev;
+}
+
+extern "C" int lora_amd_groupnorm_nhwc_route(int32_t B, int32_t C, int32_t HW, int32_t groups, int32_t dtype,
+                                             int32_t backward) {
+  LORA_AMD_CHECK(gn_nhwc_geo(B, C, HW, groups).ok, LORA_AMD_EINVAL,
+                 "groupnorm_nhwc_route: geometry B=%d C=%d HW=%d groups=%d not supported", B, C, HW, groups);
+  LORA_AMD_CHECK(dtype_ok(dtype), LORA_AMD_EINVAL, "groupnorm_nhwc_route: bad dtype %d", dtype);
+  return gn_nhwc_route(B, C, HW, groups, dtype, backward);
+}
+
+// f(int_c<form>) for the plan's form
+template <class F>
+static void res_by_form(int form, F &&f) {
+  by_int<0, 1, 2, 3>(form, f);
+  static_assert(kResNForms == 4, "res_by_form lists every form");
+}
+
 #define GN_NHWC_CHECKS(name)                                                                                          \
   const GnNhwcGeo q = gn_nhwc_geo(B, C, HW, groups);                                                                  \
   LORA_AMD_CHECK(q.ok, LORA_AMD_EINVAL, name ": geometry B=%d C=%d HW=%d groups=%d not supported", B, C, HW, groups); \
@@ -1207,6 +1546,23 @@ extern "C" int lora_amd_groupnorm_nhwc_fwd(const void *x, const void *gamma, con
   LORA_AMD_CHECK(x && gamma && beta && y && aff && workspace, LORA_AMD_EINVAL, "groupnorm_nhwc_fwd: null pointer");
   LORA_AMD_CHECK(aligned_for(x, dtype) && aligned_for(y, dtype) && ((uintptr_t)aff % 32) == 0, LORA_AMD_EINVAL,
                  "groupnorm_nhwc_fwd: unaligned tensor");
+  if (gn_nhwc_route(B, C, HW, groups, dtype, 0)) {
+    const GnResPlan p = gn_nhwc_res_plan(B, C, HW, groups, dtype, false);
+    by_dtype(dtype, [&](auto e) {
+      by_bool(act != 0, [&](auto a) {
+        res_by_form(p.form, [&](auto f) {
+          using E = decltype(e);
+          using S = typename E::storage;
+          constexpr int F = decltype(f)::value;
+          if constexpr (res_form_fits(F, (int)sizeof(S), false))
+            hipLaunchKernelGGL((gn_nhwc_res_fwd_kernel<E, decltype(a)::value, kResForms[F].T, kResForms[F].NP>), dim3(p.grid),
+                               dim3(kResForms[F].T), 0, st, (const S *)x, (const S *)gamma, (const S *)beta, addend, (S *)y,
+                               aff, C, HW, p.cpg, p.nch, p.nslots, eps);
+        });
+      });
+    });
+    return check_launch("lora_amd_groupnorm_nhwc_fwd");
+  }
   by_dtype(dtype, [&](auto e) {
     using E = decltype(e);
     using S = typename E::storage;
@@ -1230,6 +1586,23 @@ extern "C" int lora_amd_groupnorm_nhwc_bwd(const void *x, const void *gout, cons
   LORA_AMD_CHECK(aligned_for(x, dtype) && aligned_for(gout, dtype) && aligned_for(dx, dtype) &&
                      aligned_for(gamma, dtype) && ((uintptr_t)aff % 32) == 0,
                  LORA_AMD_EINVAL, "groupnorm_nhwc_bwd: unaligned tensor");
+  if (gn_nhwc_route(B, C, HW, groups, dtype, 1)) {
+    const GnResPlan p = gn_nhwc_res_plan(B, C, HW, groups, dtype, true);
+    by_dtype(dtype, [&](auto e) {
+      by_bool(act != 0, [&](auto a) {
+        res_by_form(p.form, [&](auto f) {
+          using E = decltype(e);
+          using S = typename E::storage;
+          constexpr int F = decltype(f)::value;
+          if constexpr (res_form_fits(F, (int)sizeof(S), true))
+            hipLaunchKernelGGL((gn_nhwc_res_bwd_kernel<E, decltype(a)::value, kResForms[F].T, kResForms[F].NP>), dim3(p.grid),
+                               dim3(kResForms[F].T), 0, st, (const S *)x, (const S *)gout, (const S *)gamma, aff, (S *)dx, C,
+                               HW, p.cpg, p.nch, p.nslots);
+        });
+      });
+    });
+    return check_launch("lora_amd_groupnorm_nhwc_bwd");
+  }
   by_dtype(dtype, [&](auto e) {
     by_bool(act != 0, [&](auto a) {
       using E = decltype(e);

@@ -582,13 +582,17 @@ ATTN_SHORT_BWD = True
 # the UNet forward (csrc/hostops.hip temb_addends); False = the four launches per block
 # (tests/test_resnet_glue_route.py runs both)
 TEMB_ONE_LAUNCH = True
+# channels-last GroupNorm of the maps a workgroup can hold in registers as ONE launch each way (csrc/hostops.hip
+# gn_nhwc_res_*_kernel; the library routes by geometry); False = the three streaming launches everywhere
+# (tests/test_gn_resident_route.py and tests/test_gpu_gn_resident.py run both)
+GN_RESIDENT = True
 
 
 def apply_ab_overrides(spec: str, namespace: dict) -> dict:
     """``LORA_AMD_AB="NAME=0,OTHER=1"``: the ONE measurement switch for same-box A/B runs — flips the module constants
     listed in ``allowed`` (and only those) without a code edit; every A/B log under profiles/ names the spec it ran with
     (a constant retired since then is an unknown name here)."""
-    allowed = ("ATTN_SHORT_BWD", "CONCAT_GROUPS", "CONV3_FUSED", "MASTER_MERGE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
+    allowed = ("ATTN_SHORT_BWD", "CONCAT_GROUPS", "CONV3_FUSED", "GN_RESIDENT", "MASTER_MERGE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
                "WS_DROPOUT_WIDE_BWD")
     done = {}
     for item in filter(None, (s.strip() for s in spec.split(","))):
@@ -600,6 +604,8 @@ def apply_ab_overrides(spec: str, namespace: dict) -> dict:
 
 
 apply_ab_overrides(os.environ.get("LORA_AMD_AB", ""), globals())
+if not GN_RESIDENT and _C.load() is not None:  # a library-side route: the setting has to be there before the first launch
+    _C.groupnorm_nhwc_resident(0)
 
 # Rounding of the in-step merge of 16-bit weights (csrc/merge_step.hip): "dither" (default) = nearest with a fixed
 # per-element dither, so that a delta below half an ulp of the frozen weight survives in the row sums; "once" = nearest even

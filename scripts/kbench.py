@@ -819,6 +819,62 @@ def bench_temb(args):
         print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in res.items()}), flush=True)
 
 
+# GroupNorm sites of the flagship step at batch 4 (SD1.5, 512^2): (C, map side, sites); all with 32 groups
+SD15_GN_SITES = [(1280, 8, 12), (2560, 8, 3), (640, 16, 1), (1280, 16, 11), (1920, 16, 1), (2560, 16, 2), (320, 32, 1),
+                 (640, 32, 11), (960, 32, 1), (1280, 32, 1), (1920, 32, 1), (320, 64, 13), (640, 64, 2), (960, 64, 1)]
+
+
+def bench_gn(args):
+    """channels_last GroupNorm (+SiLU, + addend) per geometry of the step and direction: the three streaming launches
+    (lora_amd_groupnorm_nhwc_resident off) against the one resident launch where the library has a form for the geometry,
+    next to the floor (bytes / 6.29 TB/s: forward 2 passes over the tensor, backward 3), the route the library takes,
+    and the relative L2 error of both routes against float64."""
+    F = torch.nn.functional
+    B, G, dt = 4, 32, torch.bfloat16
+    tot = {"fwd": [0.0, 0.0], "bwd": [0.0, 0.0]}
+    for C, side, n_sites in SD15_GN_SITES:
+        HW = side * side
+        x = (torch.randn(B, side, side, C, device=DEV) * 1.5 + torch.randn(1, 1, 1, C, device=DEV) * 3.0).to(dt).permute(0, 3, 1, 2)
+        gout = torch.randn(B, side, side, C, device=DEV).to(dt).permute(0, 3, 1, 2)
+        gamma, beta = (torch.randn(C, device=DEV) * 0.5 + 1).to(dt), (torch.randn(C, device=DEV) * 0.3).to(dt)
+        add = torch.randn(B, C, device=DEV) * 2.0
+        xr = x.double().contiguous().requires_grad_(True)
+        yr = F.silu(F.group_norm(xr + add.double()[:, :, None, None], G, gamma.double(), beta.double(), 1e-5))
+        yr.backward(gout.double().contiguous())
+        nbytes = x.numel() * x.element_size()
+        prev = _C.groupnorm_nhwc_resident(1)
+        try:
+            _, aff = _C.groupnorm_nhwc_fwd(x, gamma, beta, G, 1e-5, True, add)
+            for name, bwd, passes in (("fwd", False, 2), ("bwd", True, 3)):
+                _C.groupnorm_nhwc_resident(1)
+                has_form = _C.groupnorm_nhwc_route(B, C, HW, G, dt, bwd)
+                fn = ((lambda: _C.groupnorm_nhwc_bwd(x, gout, gamma, aff, G, True)) if bwd else
+                      (lambda: _C.groupnorm_nhwc_fwd(x, gamma, beta, G, 1e-5, True, add)))
+                want = xr.grad if bwd else yr.detach()
+                res = {"op": "gn_nhwc_" + name, "B": B, "C": C, "map": side, "sites": n_sites, "MB": round(nbytes / 1e6, 2),
+                       "floor_us": passes * nbytes / 6.29e6}
+                for tag, on in (("streaming", 0), ("resident", 1)):
+                    if on and not has_form:
+                        continue
+                    _C.groupnorm_nhwc_resident(on)
+                    got = fn()
+                    got = got[0] if isinstance(got, tuple) else got
+                    res[tag + "_l2"] = float((got.double() - want).norm() / want.norm())
+                    res[tag + "_us"] = timeit(fn, args.iters)[0] * 1e6
+                res["route"] = "resident" if has_form else "streaming (no form holds it)"
+                if has_form:
+                    res["resident_x_floor"] = res["resident_us"] / res["floor_us"]
+                    res["gain_us_per_step"] = n_sites * (res["streaming_us"] - res["resident_us"])
+                    res["l2_ratio"] = res["resident_l2"] / res["streaming_l2"]
+                tot[name][0] += n_sites * res["streaming_us"]
+                tot[name][1] += n_sites * res["resident_us" if has_form else "streaming_us"]
+                print(json.dumps({k: (float(f"{v:.4g}") if isinstance(v, float) else v) for k, v in res.items()}), flush=True)
+        finally:
+            _C.groupnorm_nhwc_resident(prev)
+    print(json.dumps({"op": "gn_nhwc_step_sum_us", **{k: {"all_streaming": round(v[0], 1), "routed": round(v[1], 1)}
+                                                      for k, v in tot.items()}}), flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="merge,linear,ws,conv,hostops")
@@ -856,3 +912,5 @@ if __name__ == "__main__":
         bench_attn(a)
     if "temb" in a.what.split(","):
         bench_temb(a)
+    if "gn" in a.what.split(","):
+        bench_gn(a)
