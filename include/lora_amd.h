@@ -123,6 +123,10 @@ int lora_amd_merge_batched(const lora_amd_merge_site *sites_dev, int32_t n_sites
  * hash(dither_key, n, k) in [0, 1) ulp — P(round away from zero) = frac((W + delta) / ulp), exactly W where delta = 0,
  * identical from step to step: a delta below half an ulp of the frozen weight survives in the sum over a row instead of
  * vanishing element by element.  tiles_k / tile_begin are filled by the plan (host, no GPU needed).
+ * Ranks: 1 <= r <= LORA_AMD_MAX_RANK per site.  A table whose largest rank is at most 16 runs the register kernel (the r x 8
+ * block of `down` of a column owner in VGPRs); a table with a site above 16 runs the chunked kernel (the rank walked in chunks
+ * of 8, `down` re-read per chunk, the sums kept in registers; same tiles, layouts and roundings, the fma chain in the same rank
+ * order: ranks that are zero change no bit).  src_f32 tables stop at rank 16 (LORA_AMD_EUNSUPPORTED from the plan above it).
  * src_f32 (the field that was `reserved`; same offset): 0 = w has the output dtype (zero-initialised tables: as before);
  * 1 = w is the frozen f32 MASTER [N, K] (f32 models under 16-bit autocast): the value is fmaf(alpha, up down, W32) rounded
  * ONCE to the 16-bit output dtype, 4 + 2 + 2 bytes per element with out_t instead of 2 + 2 + 2.  Where W and alpha up down

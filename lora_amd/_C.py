@@ -550,7 +550,8 @@ class MergeStepPlan:
     where W_eff / W_eff^T go.  ``sites``: dicts with ``w`` [N, K], ``up`` [N, r], ``down`` [r, K], ``out`` (2-D view whose
     row stride is ld_out), ``out_t`` (2-D view or None), ``row_heads`` / ``col_heads`` = (d, D) or None, ``key`` (dither).
     The plan's dtype is the 16-bit dtype of ``out``; ``w`` has that dtype or is the f32 master (``src_f32``), the same for
-    every site of a plan."""
+    every site of a plan.  Ranks 1..64; a plan with a site above rank 16 launches the chunked kernel for all its sites
+    (``rank_max``), and f32 masters stop at rank 16."""
 
     def __init__(self, sites):
         if not sites:

@@ -288,6 +288,190 @@ __global__ __launch_bounds__(kMsThreads) void merge_step_kernel(const lora_amd_m
   }
 }
 
+// ---- ranks 17 .. LORA_AMD_MAX_RANK: the same tile, site struct, layouts and roundings; what changes is where the factors
+// live.  r x 8 floats of `down` per thread do not fit the register file past rank 16, so the thread walks the rank in
+// chunks of 8 — its 8 x 8 block of `down` re-read per chunk (L2-resident: the tile's columns of `down` are r TC 4 bytes)
+// into one of TWO register blocks, the next chunk's loads in flight under this chunk's fmas — and keeps the p[4][8] sums of
+// its rows across the chunks: every element's chain is still fmaf(up[n][j], down[j][k], p) for j = 0 .. r - 1 in rank order
+// from p = 0, so a site whose ranks past 16 are zero gives the bits of merge_step_kernel on its first 16 (fma(0, x, p) = p).
+// A tile is walked in passes of 4 rows per thread (64 or 128 rows: one or two passes per geometry); the rows of `up` of a
+// pass sit in LDS at the rank rounded up to 8 (zero-filled).  16-bit sources only: an f32 master wants the f64 re-formation
+// over all ranks, which this kernel does not carry (the plan refuses such tables).
+// __launch_bounds__(256, 2): two 64-register blocks of `down`, 32 sums and the W chunks fit two waves per SIMD (at most 254
+// VGPRs, no scratch: profiles/merged_wide_resources.txt); without the bound the nearest-even two-pass forms took one more.
+constexpr int kMsWideU = 4;       // rows per thread and pass
+constexpr int kMsWideChunk = 8;   // ranks per register block
+
+template <class EW, int DITHER, int TR, int TC>
+__global__ __launch_bounds__(kMsThreads, 2) void merge_step_wide_kernel(const lora_amd_mstep_site *__restrict__ sites,
+                                                                     int n_sites, float alpha) {
+  using SW = typename EW::storage;
+  constexpr int C8 = TC / 8, SLOTS = kMsThreads / C8, U = kMsWideU, PR = U * SLOTS, PASSES = TR / PR;
+  constexpr int PITCH = TC * 2 + 4, CH = PR / 8, RC = kMsWideChunk;
+  static_assert(PASSES >= 1 && PASSES * PR == TR && (CH & (CH - 1)) == 0, "tile geometry");
+  __shared__ int64_t s_begin[kMsMaxSitesLds];
+  __shared__ __attribute__((aligned(16))) float s_up[PR * LORA_AMD_MAX_RANK];
+  __shared__ __attribute__((aligned(16))) unsigned char s_img[PR * PITCH];
+  const int tid = threadIdx.x;
+  const int64_t tile = blockIdx.x;
+  int si;
+  if (n_sites <= kMsMaxSitesLds) {
+    for (int i = tid; i < n_sites; i += kMsThreads) s_begin[i] = sites[i].tile_begin;
+    __syncthreads();
+    int lo = 0, hi = n_sites - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (s_begin[mid] <= tile) lo = mid; else hi = mid - 1;
+    }
+    si = lo;
+  } else {
+    int lo = 0, hi = n_sites - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (sites[mid].tile_begin <= tile) lo = mid; else hi = mid - 1;
+    }
+    si = lo;
+  }
+  const lora_amd_mstep_site s = sites[si];
+  const int r = s.r, rp = (r + RC - 1) / RC * RC;   // rp: LDS pitch of a row of `up` (<= LORA_AMD_MAX_RANK)
+  const int64_t tl = tile - s.tile_begin;
+  const int tn = (int)(tl / s.tiles_k), tk = (int)(tl - (int64_t)tn * s.tiles_k);
+  const int col0 = tk * TC;
+  const int ncol8 = min(TC, s.K - col0) >> 3;      // 16-byte chunks of this tile (K % 8 == 0)
+  const int cl = tid % C8, slot = tid / C8;         // C8 chunk columns x SLOTS row slots
+  const bool live = cl < ncol8;
+  const int col = col0 + (live ? cl : 0) * 8;      // idle lanes of a ragged last column tile stay inside the row
+  const unsigned ucol = (unsigned)col;
+  SW *wout = reinterpret_cast<SW *>(s.out) + ms_map(col, s.col_d, s.col_D);
+  SW *wt = reinterpret_cast<SW *>(s.out_t);
+
+  // ranks jb .. jb + 7 of this thread's 8 columns of `down` (f32 [r, K]); rows past r read as zero
+  auto load_down = [&](float (&fc)[RC][8], int jb) {
+#pragma unroll
+    for (int j = 0; j < RC; ++j) {
+      if (jb + j < r) {
+        const float *dr = s.down + (int64_t)(jb + j) * s.K;   // uniform row base + the lane's 32-bit column offset
+        const float4 a = gl_ld4(dr + ucol);
+        const float4 b = gl_ld4(dr + ucol + 4u);
+        fc[j][0] = a.x; fc[j][1] = a.y; fc[j][2] = a.z; fc[j][3] = a.w;
+        fc[j][4] = b.x; fc[j][5] = b.y; fc[j][6] = b.z; fc[j][7] = b.w;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) fc[j][i] = 0.f;
+      }
+    }
+  };
+
+#pragma unroll 1
+  for (int ps = 0; ps < PASSES; ++ps) {
+    const int row0 = tn * TR + ps * PR;
+    const int nrows = min(PR, s.N - row0);           // block-uniform
+    if (nrows <= 0) break;
+    if (ps) __syncthreads();                         // the pass before has read s_up and s_img
+    // the pass's rows of `up` (f32 [N, r]) -> LDS [nrows][rp]
+    for (int i = tid; i < nrows * rp; i += kMsThreads) {
+      const int rl = i / rp, j = i - rl * rp;
+      s_up[i] = j < r ? gl(s.up)[(int64_t)(row0 + rl) * r + j] : 0.f;
+    }
+    __syncthreads();
+
+    float fa[RC][8], fb[RC][8];
+    load_down(fa, 0);
+    const SW *win = reinterpret_cast<const SW *>(s.w) + (int64_t)row0 * s.K + col;
+    su32x4 w[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int rl = slot + u * SLOTS;
+      const bool ok = live && rl < nrows;
+      w[u] = __builtin_nontemporal_load(gl(reinterpret_cast<const su32x4 *>(win + (int64_t)(ok ? rl : 0) * s.K)));
+    }
+    float p[U][8];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) p[u][i] = 0.f;
+    }
+    // rows at or past nrows read LDS words of no row (inside s_up: (slot + u SLOTS) rp + jb + j < PR rp); never stored
+    auto fma_chunk = [&](const float (&fc)[RC][8], int jb) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const float *upr = s_up + (slot + u * SLOTS) * rp + jb;
+#pragma unroll
+        for (int j = 0; j < RC; ++j) {
+          const float uj = upr[j];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) p[u][i] = fmaf(uj, fc[j][i], p[u][i]);
+        }
+      }
+    };
+    for (int jb = 0; jb < r; jb += 2 * RC) {
+      const bool second = jb + RC < r;
+      if (second) load_down(fb, jb + RC);
+      fma_chunk(fa, jb);
+      if (second) {
+        if (jb + 2 * RC < r) load_down(fa, jb + 2 * RC);
+        fma_chunk(fb, jb + RC);
+      }
+    }
+
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int rl = slot + u * SLOTS;
+      if (!(live && rl < nrows)) continue;
+      float wf[8];
+      union { su32x4 v; SW e[8]; } in;
+      in.v = w[u];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) wf[i] = EW::to_f(in.e[i]);
+      const int n = row0 + rl;
+      uint32_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      if constexpr (DITHER == 1) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = ms_dither16((uint32_t)n * (uint32_t)s.K + (uint32_t)(col + i), (uint32_t)s.dither_key);
+      } else if constexpr (DITHER == 2) {
+        const MsDither8 h = ms_dither_chunk((uint32_t)n * (uint32_t)s.K + (uint32_t)col, (uint32_t)s.dither_key);
+        d[0] = ms_dither_pick<0>(h); d[1] = ms_dither_pick<1>(h); d[2] = ms_dither_pick<2>(h); d[3] = ms_dither_pick<3>(h);
+        d[4] = ms_dither_pick<4>(h); d[5] = ms_dither_pick<5>(h); d[6] = ms_dither_pick<6>(h); d[7] = ms_dither_pick<7>(h);
+      }
+      uint32_t b[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) b[i] = ms_round<EW, DITHER != 0>(fmaf(alpha, p[u][i], wf[i]), d[i]);
+      su32x4 o;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[i] = b[2 * i] | (b[2 * i + 1] << 16);
+      __builtin_nontemporal_store(o, gl(reinterpret_cast<su32x4 *>(wout + (int64_t)ms_map(n, s.row_d, s.row_D) * s.ld_out)));
+      if (wt != nullptr) {
+        uint32_t *img = reinterpret_cast<uint32_t *>(s_img + rl * PITCH + cl * 16);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) img[i] = o[i];
+      }
+    }
+    if (wt == nullptr) continue;   // site-uniform
+    __syncthreads();
+    // the pass's image column-wise, as merge_step_kernel writes its tile's
+    const int nk = ncol8 * 8, nchunks = (nrows + 7) >> 3;
+    for (int t = tid; t < nk * CH; t += kMsThreads) {
+      const int kq = t / (4 * CH), rem = t % (4 * CH);  // 4 columns per group of 4 CH tasks
+      const int k = kq * 4 + (rem & 3), ch = rem >> 2;
+      if (ch >= nchunks) continue;
+      const unsigned char *src = s_img + (ch * 8) * PITCH + k * 2;
+      unsigned short e[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) e[i] = *reinterpret_cast<const unsigned short *>(src + i * PITCH);
+      const int n0 = row0 + ch * 8;
+      su32x4 o;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[i] = (uint32_t)e[2 * i] | ((uint32_t)e[2 * i + 1] << 16);
+      SW *dst = wt + (int64_t)ms_map(col0 + k, s.col_d, s.col_D) * s.ld_out_t + ms_map(n0, s.row_d, s.row_D);
+      if (n0 + 8 <= s.N) {
+        __builtin_nontemporal_store(o, gl(reinterpret_cast<su32x4 *>(dst)));
+      } else {
+        for (int i = 0; i < s.N - n0; ++i) gl(reinterpret_cast<unsigned short *>(dst))[i] = e[i];
+      }
+    }
+  }
+}
+
 }  // namespace lora_amd
 
 using namespace lora_amd;
@@ -307,7 +491,10 @@ extern "C" int lora_amd_merge_step_plan(lora_amd_mstep_site *sites, int32_t n, i
                    sites[0].src_f32);
     LORA_AMD_CHECK(s.N > 0 && s.K > 0 && s.K % 8 == 0 && s.N % 8 == 0, LORA_AMD_EINVAL,
                    "merge_step_plan: site %d: N = %d, K = %d must be multiples of 8", i, s.N, s.K);
-    LORA_AMD_CHECK(s.r >= 1 && s.r <= 16, LORA_AMD_ERANK, "merge_step_plan: site %d: rank %d outside [1,16]", i, s.r);
+    LORA_AMD_CHECK(s.r >= 1 && s.r <= LORA_AMD_MAX_RANK, LORA_AMD_ERANK, "merge_step_plan: site %d: rank %d outside [1,%d]", i,
+                   s.r, LORA_AMD_MAX_RANK);
+    LORA_AMD_CHECK(s.r <= 16 || !s.src_f32, LORA_AMD_EUNSUPPORTED,
+                   "merge_step_plan: site %d: rank %d on an f32 master (src_f32 tables: rank <= 16)", i, s.r);
     LORA_AMD_CHECK(s.w && s.up && s.down && s.out, LORA_AMD_EINVAL, "merge_step_plan: site %d: null pointer", i);
     LORA_AMD_CHECK(map_ok(s.row_d, s.row_D, s.N) && map_ok(s.col_d, s.col_D, s.K), LORA_AMD_EINVAL,
                    "merge_step_plan: site %d: bad head layout", i);
@@ -335,10 +522,25 @@ extern "C" int lora_amd_merge_step(const lora_amd_mstep_site *sites_dev, int32_t
   LORA_AMD_CHECK(ms_tile >= 0 && ms_tile < 4 && (plan_value >> (kMsSrcF32Bit + 1)) == 0, LORA_AMD_EINVAL, "merge_step: not a value of lora_amd_merge_step_plan");
   LORA_AMD_CHECK(sites_dev && n >= 1 && total_tiles >= 1 && total_tiles < (1ll << 31), LORA_AMD_EINVAL, "merge_step: bad argument");
   LORA_AMD_CHECK(w_dtype == LORA_AMD_F16 || w_dtype == LORA_AMD_BF16, LORA_AMD_EINVAL, "merge_step: 16-bit output weights only");
-  LORA_AMD_CHECK(rank_max >= 1 && rank_max <= 16, LORA_AMD_ERANK, "merge_step: rank %d outside [1,16]", rank_max);
+  LORA_AMD_CHECK(rank_max >= 1 && rank_max <= LORA_AMD_MAX_RANK, LORA_AMD_ERANK, "merge_step: rank %d outside [1,%d]", rank_max,
+                 LORA_AMD_MAX_RANK);
   LORA_AMD_CHECK(rounding == LORA_AMD_ROUND_ONCE || rounding == LORA_AMD_ROUND_DITHER, LORA_AMD_EINVAL,
                  "merge_step: rounding must be ROUND_ONCE or ROUND_DITHER, got %d", rounding);
   hipStream_t st = (hipStream_t)stream;
+  if (rank_max > 16) {   // a table with a site of rank 17 .. 64: the chunked kernel (any rank of [1, 64] per site)
+    LORA_AMD_CHECK(!src32, LORA_AMD_EUNSUPPORTED, "merge_step: rank %d on f32 masters (src_f32 tables: rank <= 16)", rank_max);
+    const int dm = rounding == LORA_AMD_ROUND_DITHER ? g_ms_dither : 0;
+    by_dtype<f16_t, bf16_t>(w_dtype, [&](auto e) {
+      by_int<0, 1, 2, 3>(ms_tile, [&](auto ti) {
+        by_int<0, 1, 2>(dm, [&](auto dv) {
+          constexpr MsTile tg = kMsTiles[decltype(ti)::value];
+          hipLaunchKernelGGL((merge_step_wide_kernel<decltype(e), decltype(dv)::value, tg.tr, tg.tc>),
+                             dim3((unsigned)total_tiles), dim3(kMsThreads), 0, st, sites_dev, n, alpha);
+        });
+      });
+    });
+    return check_launch("lora_amd_merge_step");
+  }
   const int RT = rank_max <= 4 ? 4 : rank_max <= 8 ? 8 : 16;
   const bool dith = rounding == LORA_AMD_ROUND_DITHER;
   const int dmode = dith ? g_ms_dither : 0;

@@ -586,13 +586,18 @@ TEMB_ONE_LAUNCH = True
 # gn_nhwc_res_*_kernel; the library routes by geometry); False = the three streaming launches everywhere
 # (tests/test_gn_resident_route.py and tests/test_gpu_gn_resident.py run both)
 GN_RESIDENT = True
+# maskless Linear adapters of rank 17..64 on the step's merged weights (csrc/merge_step.hip merge_step_wide_kernel: the
+# in-step merge walks the rank in chunks; factor gradients on the rowdot / colreduce primitives in the site's backward);
+# False = the frozen GEMM + primitives route of LoraLinearFunction, forward and backward
+# (tests/test_gpu_merged_wide.py runs both)
+MERGED_WIDE = True
 
 
 def apply_ab_overrides(spec: str, namespace: dict) -> dict:
     """``LORA_AMD_AB="NAME=0,OTHER=1"``: the ONE measurement switch for same-box A/B runs — flips the module constants
     listed in ``allowed`` (and only those) without a code edit; every A/B log under profiles/ names the spec it ran with
     (a constant retired since then is an unknown name here)."""
-    allowed = ("ATTN_SHORT_BWD", "CONCAT_GROUPS", "CONV3_FUSED", "GN_RESIDENT", "MASTER_MERGE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
+    allowed = ("ATTN_SHORT_BWD", "CONCAT_GROUPS", "CONV3_FUSED", "GN_RESIDENT", "MASTER_MERGE", "MERGED_WIDE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
                "WS_DROPOUT_WIDE_BWD")
     done = {}
     for item in filter(None, (s.strip() for s in spec.split(","))):
@@ -638,7 +643,9 @@ class MergedWeights:
     input gradient the dense GEMM ``G W_eff``, and the parameter gradients of ALL sites one
     ``linear_bwd_factors_self_ragged`` launch after the backward (``flush_factors``; without a trainer state: one
     ``linear_bwd_factors_self`` launch per site, in its backward).
-    Eligible: device tensors, dropout not in effect, no selector, frozen weight, f32 factors, rank <= 16.
+    Eligible: device tensors, dropout not in effect, no selector, frozen weight, f32 factors, rank <= 16 — or rank 17..64
+    on 16-bit weights in the compute dtype (``MERGED_WIDE``: same merge launch form, chunked kernel; factor gradients on the
+    primitives in the site's backward, not deferred).
 
     f32-resident frozen weights under 16-bit autocast (``master_site``): ``lookup`` / ``lookup_group`` are handed the f32
     Parameter itself; the scratch weights take the compute dtype and the in-step merge reads the master (``src_f32``) — no
@@ -831,7 +838,8 @@ class MergedWeights:
         self._plans = None
 
     def refresh(self) -> None:
-        """ONE merge launch per (weight dtype, source type, scale) group — one in practice — over every registered site."""
+        """ONE merge launch per (weight dtype, source type, scale, rank above 16) group — one in practice — over every
+        registered site (ranks 17..64 run the chunked kernel: their sites never share a table with the others)."""
         if self._state is not None:
             self._fresh_at = self._state.step_count
         if not self.entries:
@@ -843,11 +851,12 @@ class MergedWeights:
             step_groups, old_groups = {}, {}
             for e in self.entries.values():
                 if e["step"]:
-                    step_groups.setdefault((e["w_eff"].dtype, e["src_f32"], e["scale"]), []).append(self._msite(e))
+                    wide = e["module"].lora_down.weight.shape[0] > 16
+                    step_groups.setdefault((e["w_eff"].dtype, e["src_f32"], e["scale"], wide), []).append(self._msite(e))
                 else:
                     for st in e["sites"]:
                         old_groups.setdefault((st[0].dtype, e["scale"]), []).append(st)
-            self._plans = [(_C.MergeStepPlan(sites), alpha, MERGE_ROUNDING) for (_, _, alpha), sites in step_groups.items()]
+            self._plans = [(_C.MergeStepPlan(sites), alpha, MERGE_ROUNDING) for (_, _, alpha, _), sites in step_groups.items()]
             self._plans += [(_C.MergePlan(sites), alpha, _C.ROUND_ONCE) for (_, alpha), sites in old_groups.items()]
         for plan, alpha, rounding in self._plans:
             plan.launch(alpha, rounding)
@@ -1002,6 +1011,8 @@ def _merged_factor_grads(g2, x2, down, up, scale, sink, out_heads, in_heads, K, 
     ``linear_bwd_factors_self`` launch here.  Returns (d_down, d_up) — None when they leave through ``sink``."""
     M, r = x2.shape[0], down.shape[0]
     down_c, up_c = down.contiguous(), up.contiguous()
+    if r > 16:
+        return _wide_factor_grads(g2, x2, down_c, up_c, scale, sink, out_heads, in_heads, K, N, tag)
     mw = getattr(getattr(sink, "owner", None), "merged", None)
     if mw is not None and mw.defer_factors:
         plan = _deferred_plan(sink, g2, x2, down_c, up_c) if _C.FACTORS_MFMA_MODE == "all" else None
@@ -1016,6 +1027,27 @@ def _merged_factor_grads(g2, x2, down, up, scale, sink, out_heads, in_heads, K, 
     _C.linear_bwd_factors_self(g2, x2, down_c, up_c, up_part, down_part, scale, g_heads=out_heads, x_heads=in_heads)
     _log("bwd", f"{tag}_dx+factors_self", M, K, N, r)
     return _finish(sink, site, w, down, up)
+
+
+def _wide_factor_grads(g2, x2, down, up, scale, sink, out_heads, in_heads, K, N, tag):
+    """Both factor gradients of a merged-weight site of rank 17..64, at once (no deferred pass takes these ranks): the
+    ``primitives`` branch of :func:`_linear_backward` — T = X down^T, dUp = scale G^T T, Gt = scale G up, dDown = Gt^T X —
+    accumulated into ``sink`` (beta = 1) when there is one.  Head-padded G / X are unpacked first: against zero-padded factor
+    views on the padded rows the copies measured 11-28 % faster (the primitives then read 5/8 of the columns;
+    profiles/merged_wide_kbench.txt)."""
+    M, r = x2.shape[0], down.shape[0]
+    if out_heads:
+        g2 = unpack_heads(g2, out_heads)
+    if in_heads:
+        x2 = unpack_heads(x2, in_heads)
+    t = rowdot_any(x2, down, _C.FACTOR_RK, 1.0)
+    gt = rowdot_any(g2, up, _C.FACTOR_KR, scale, None, True)
+    _log("bwd", f"{tag}_dx+factors_primitives", M, K, N, r)
+    if sink is not None:
+        colreduce_any(g2, t, _C.FACTOR_KR, scale, out=sink.up_grad, beta=1.0)
+        colreduce_any(x2, gt, _C.FACTOR_RK, 1.0, out=sink.down_grad, beta=1.0)
+        return None, None
+    return colreduce_any(x2, gt, _C.FACTOR_RK, 1.0).to(down.dtype), colreduce_any(g2, t, _C.FACTOR_KR, scale).to(up.dtype)
 
 
 class LoraLinearMergedFunction(torch.autograd.Function):
@@ -1152,6 +1184,12 @@ def merged_ok(x: torch.Tensor, weight: torch.Tensor, down: torch.Tensor, up: tor
     for hl in (in_heads, out_heads):
         if hl is not None and (hl[1] % 8 or hl[2] % 8 or hl[2] < hl[1]):
             return False
+    if r > 16 and MERGED_WIDE:
+        # ranks 17..64: the merge's own preconditions (csrc/merge_step.hip; pointers were checked above) — 16-bit weights
+        # in the compute dtype (the chunked kernel takes no f32 master), N and K in 16-byte chunks; the factor gradients
+        # run on the rank <= 64 primitives, which take any shape
+        return (r <= _C.MAX_RANK and not master and x.dtype in (torch.bfloat16, torch.float16)
+                and N % 8 == 0 and K % 8 == 0)
     return bool(_C.factors_self_plan(M, K, N, r).supported)
 
 

@@ -100,7 +100,16 @@ def mstep_plan(tens):
 
 def bench_mstep(args):
     """The in-step merge (lora_amd_merge_step) on the 144 Linear sites of the SD1.5 UNet, W_eff^T for the sites whose input
-    takes a gradient (all but the cross-attention k / v): tile geometry x dither form x rounding."""
+    takes a gradient (all but the cross-attention k / v): tile geometry x dither form x rounding.  ``--rank`` 17..64 times the
+    chunked kernel of those ranks; the call then opens with the rank-16 table at the default geometry (the line to read the
+    others against) and has no f32-master leg (the plan refuses masters above rank 16)."""
+    if args.rank > 16:
+        plan = mstep_plan(mstep_tensors(16))
+        med, best = timeit(lambda: plan.launch(0.7, _C.ROUND_DITHER), iters=args.iters)
+        print(json.dumps(dict(kernel="merge_step", rank=16, tile="128x128", dither="per chunk", sites=plan.n_sites,
+                              tiles=plan.total_tiles, MB=plan.bytes_algorithmic / 1e6, us=med * 1e6, best_us=best * 1e6,
+                              GBs=plan.bytes_algorithmic / med / 1e9, frac8=plan.bytes_algorithmic / med / 8e12)), flush=True)
+        del plan
     tens = mstep_tensors(args.rank)
     for tile in (0, 1, 2, 3):
         for dith, rounding in ((2, _C.ROUND_DITHER), (1, _C.ROUND_DITHER), (2, _C.ROUND_ONCE)):
@@ -108,11 +117,13 @@ def bench_mstep(args):
             plan = mstep_plan(tens)
             med, best = timeit(lambda: plan.launch(0.7, rounding), iters=args.iters)
             gbs = plan.bytes_algorithmic / med / 1e9
-            print(json.dumps(dict(kernel="merge_step", tile=("128x64", "64x128", "128x128", "256x64")[tile],
+            print(json.dumps(dict(kernel="merge_step", rank=args.rank, tile=("128x64", "64x128", "128x128", "256x64")[tile],
                                   dither={1: "per element", 2: "per chunk"}[dith] if rounding == _C.ROUND_DITHER else "none",
                                   sites=plan.n_sites, tiles=plan.total_tiles, MB=plan.bytes_algorithmic / 1e6,
                                   us=med * 1e6, best_us=best * 1e6, GBs=gbs, frac8=gbs / 8000)), flush=True)
     _C.merge_step_set_tuning(2, 2)
+    if args.rank > 16:
+        return
     # the same table read from f32 MASTERS (src_f32: 4 + 2 + 2 bytes per element instead of 2 + 2 + 2) next to the 16-bit
     # sources, default geometry and rounding, both legs in this one call (three alternating rounds, the median of each)
     plans = {"bf16": mstep_plan(tens), "f32": mstep_plan(mstep_tensors(args.rank, torch.float32))}
