@@ -606,20 +606,32 @@ int lora_amd_reduce_batched(const lora_amd_reduce_desc *descs_dev, int32_t n, in
  * the narrower operand fit 6 resident (row step, column group) pairs per wave (rows x columns <= 64 x 320 or 32 x 640) — the
  * kernel that runs three workgroups per CU; 2 = up to 10 pairs (64 x 640, 32 x 1280), two per CU.  One launch per class; a
  * table planned for class 2 may hold class-1 sites (they then run the two-per-CU kernel).
- * Shapes: N, K multiples of 32, rank <= 16; anything else: supported = 0, use the _self_ragged pass. */
+ * Shapes: N, K multiples of 32, rank <= 16 (<= 64 with LORA_AMD_FM_PLAN_WIDE); anything else: supported = 0, use the
+ * _self_ragged pass (ranks above 16: the primitives). */
 typedef struct lora_amd_factors_mfma_plan_t {
   int32_t supported, lds_class, rank_tile, rows_per_block, nparts, lds_bytes;
   int32_t blocks_per_wg, reserved;          /* row blocks one workgroup walks: nparts = ceil(ceil(M / rows) / blocks_per_wg) */
   int64_t up_part_floats, down_part_floats;
   int64_t pack_up_elems, pack_down_elems;   /* elements (activation dtype) of the two fragment packs of a site */
 } lora_amd_factors_mfma_plan_t;
-/* rows: 0 = the planner's choice (64, else 32), else 32 / 64 tried first.  flags: reserved (0). */
+/* rows: 0 = the planner's choice (64, else 32), else 32 / 64 tried first.
+ * flags: bit 0 is reserved for a dropout site (same geometry).  Bit 1, LORA_AMD_FM_PLAN_WIDE: ranks 1..64 are accepted; a rank
+ * above 16 runs as ns = ceil(r / 16) independent rank-16 SLICES on the same G and X (dUp[:, j] depends on row j of down only,
+ * dDown[j, :] on column j of up only), one workgroup per (row block, slice).  The geometry (lds_class, rows_per_block,
+ * lds_bytes) is that of the shape at rank 16; rank_tile = 16 ns; nparts stays the number of row blocks; the slabs are
+ * [nparts][16 ns][C] (slice s owns rows 16 s .. 16 s + 15 of every block), *_part_floats = nparts * rank_tile * C;
+ * pack_*_elems = ns * (2 C 16 + 8).  Without the bit a rank above 16 is supported = 0, as is a rank above 64 with it. */
+#define LORA_AMD_FM_PLAN_WIDE 2
 int lora_amd_factors_mfma_plan(int64_t M, int32_t K, int32_t N, int32_t r, int32_t act_dtype, int32_t rows, int32_t flags,
                                lora_amd_factors_mfma_plan_t *out);
 /* f32 masters -> fragment packs: pk[split][c/8][RT][8] in the activation dtype (RT = the rank tile 4 / 8 / 16 of r; ABI 7 — it was
  * [16] whatever the rank: a rank-4 pack is a quarter of the bytes now), split 0 = rounded value, split 1 = the remainder, ranks
  * r .. RT - 1 zero; pk_down from down [r, K], pk_up from up [N, r]; sizes from lora_amd_factors_mfma_plan (pack_*_elems =
- * 2 C RT + 8).  `begin` is filled by the plan (host). */
+ * 2 C RT + 8).  `begin` is filled by the plan (host).
+ * Ranks 17..64: ns = ceil(r / 16) consecutive rank-16 packs [slice][split][c/8][16][8], EACH followed by its own 16-byte tail
+ * (ns * (2 C 16 + 8) elements): slice s is bit for bit the pack of down[16 s : 16 s + 16] / up[:, 16 s : 16 s + 16] zero-padded
+ * to 16 ranks (f16: its own power of two); up is read in place at row stride r.  Work items of a site:
+ * ((N + K) / 8) * RT * ns. */
 typedef struct lora_amd_pack_site {
   const float *down, *up;
   void *pk_down, *pk_up;
@@ -647,14 +659,22 @@ typedef struct lora_amd_fm_site {
   /* nn.Dropout(p) on the branch (lora.py:45, 57): p > 0 makes G enter as mask (.) G with the forward's mask regenerated from
    * (seed, offset + *offset_dev) — the caller folds 1 / (1 - p) into `scale`; T = X down^T is unaffected */
   float dropout_p;
-  int32_t reserved;
+  int32_t reserved;               /* caller: 0.  Ranks 17..64: the plan leaves the kernel's slice order here */
   uint64_t seed, offset;
   const uint64_t *offset_dev;
 } lora_amd_fm_site;
+/* A table is narrow (every rank <= 16, one rank tile) or WIDE (every rank in 17..64, any mix of slice counts): a mixed one is
+ * LORA_AMD_ERANK, a wide site with dropout_p > 0 LORA_AMD_EUNSUPPORTED.  A wide site owns nrb * ns consecutive blocks of the
+ * grid (nrb = ceil(M / rows_per_block)) and its slabs are [nparts][16 ns][C] (lora_amd_factors_mfma_plan, LORA_AMD_FM_PLAN_WIDE). */
 int lora_amd_factors_mfma_ragged_plan(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype, int32_t lds_class,
                                       int64_t *grid);
-/* masked: 0 = no site of the table has dropout_p > 0; 1 = the kernel that regenerates the dropout mask on G (sites with
- * dropout_p = 0 in such a table run unmasked) */
+/* masked: a flags word.  Bit 0 (LORA_AMD_FM_TABLE_MASKED): 0 = no site of the table has dropout_p > 0; 1 = the kernel that
+ * regenerates the dropout mask on G (sites with dropout_p = 0 in such a table run unmasked).  Bit 1 (LORA_AMD_FM_TABLE_WIDE):
+ * the table was planned from sites of rank 17..64 (a workgroup is one (row block, 16-rank slice) of its site) — the caller's
+ * promise: the launcher cannot see the device table, and a wide table launched without the bit reads past its rows.  Both
+ * bits: LORA_AMD_EUNSUPPORTED. */
+#define LORA_AMD_FM_TABLE_MASKED 1
+#define LORA_AMD_FM_TABLE_WIDE 2
 /* rows_per_block (ABI 6): the block height (32 / 64) every site of the table was planned with — a compile-time constant of
  * the kernel — or 0 for a class-2 table that holds sites of both heights (one launch, the workgroup enters its site's
  * instantiation); a class-1 table has one height (lora_amd_factors_mfma_ragged_plan refuses a mixed one). */
@@ -671,7 +691,8 @@ int lora_amd_linear_bwd_factors_mfma_ragged_mapped(const lora_amd_fm_site *sites
 /* Tuning / test hook: which kernel a table of class 1 (64-row blocks) runs — 0 = the 10-pair kernel every class can take (two
  * workgroups per CU, two column groups in flight per wave), 1 / 2 = the 6-pair kernel at three workgroups per CU with 1 / 2
  * groups in flight, 3 / 4 / 5 = the 6-pair kernel at two per CU with 2 / 3 / 4 groups in flight; < 0 only reads.  Returns the
- * previous value. */
+ * previous value.  Bit 8 (tables of rank 17..64, read when such a table is PLANNED): 0 = the ns slice workgroups of a row block
+ * are adjacent in the grid, 1 = strided by the site's row-block count (the default: 5 - 7 % faster over the SD1.5 tables). */
 int lora_amd_factors_mfma_set_tuning(int32_t narrow);
 
 

@@ -21,6 +21,9 @@ FACTOR_RK, FACTOR_KR = 0, 1
 ROUND_REFERENCE, ROUND_ONCE, ROUND_DITHER = 0, 1, 2
 MAX_RANK = 64
 ABI_VERSION = 7
+# the matrix-core factor pass at ranks 17..64: the plan's flag (lora_amd_factors_mfma_plan) and the launchers' flags word
+FM_PLAN_WIDE = 2
+FM_TABLE_MASKED, FM_TABLE_WIDE = 1, 2
 
 _DT = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
 
@@ -1287,15 +1290,18 @@ FACTORS_MFMA = FACTORS_MFMA_MODE != "none"
 _mfma_plan_cache = {}
 
 
-def factors_mfma_plan(M: int, K: int, N: int, r: int, act_dtype: torch.dtype, rows: int = 0) -> FactorsMfmaPlan:
+def factors_mfma_plan(M: int, K: int, N: int, r: int, act_dtype: torch.dtype, rows: int = 0,
+                      wide: bool = False) -> FactorsMfmaPlan:
     """Geometry of a site in the matrix-core factor pass (csrc/factor_mfma.hip): ``supported`` = 0 for f32 activations,
-    N / K not multiples of 32, rank > 16 or a row block that does not fit the LDS."""
-    key = (M, K, N, r, act_dtype, rows)
+    N / K not multiples of 32, rank > 16 or a row block that does not fit the LDS.  ``wide``: ranks up to 64 are taken as
+    ceil(r / 16) rank-16 slices (``FM_PLAN_WIDE``: the rank-16 geometry, slabs and packs of 16 ceil(r / 16) ranks)."""
+    key = (M, K, N, r, act_dtype, rows, bool(wide))
     pl = _mfma_plan_cache.get(key)
     if pl is None:
         pl = FactorsMfmaPlan()
         if act_dtype in (torch.float16, torch.bfloat16):
-            _check(require().lora_amd_factors_mfma_plan(M, K, N, r, dtype_code(act_dtype), rows, 0, C.byref(pl)),
+            _check(require().lora_amd_factors_mfma_plan(M, K, N, r, dtype_code(act_dtype), rows, FM_PLAN_WIDE if wide else 0,
+                                                        C.byref(pl)),
                    "lora_amd_factors_mfma_plan")
         _mfma_plan_cache[key] = pl
     return pl
@@ -1323,7 +1329,8 @@ def factors_mfma_table(sites, act_dtype: torch.dtype, lds_class: int):
     """Host half of the matrix-core pass: ``sites`` = [(g, x, pk_down, pk_up, up_part, down_part, scale, g_heads,
     x_heads, r, plan[, (p, seed, offset)])] of one LDS class and rank tile (``plan`` = the site's ``factors_mfma_plan``;
     the optional last item = nn.Dropout on the branch: ``scale`` is then multiplied by 1 / (1 - p) here) -> (planned ctypes
-    table, grid)."""
+    table, grid).  Sites of rank 17..64 (``plan`` taken with ``wide=True``) make a WIDE table: any mix of slice counts, no
+    site of rank <= 16 beside them; it is launched with ``wide=True``."""
     arr = (FmSite * len(sites))()
     for q, site in zip(arr, sites):
         g, x, pk_down, pk_up, up_part, down_part, scale, g_heads, x_heads, r, plan = site[:11]
@@ -1367,18 +1374,20 @@ def factors_mfma_table_bytes(arr, grid: int) -> Tuple[bytes, int]:
 
 
 def linear_bwd_factors_mfma_ragged(table_dev: torch.Tensor, n: int, grid: int, lds_class: int,
-                                   act_dtype: torch.dtype, masked: bool = False, rows: int = 64, map_offset: int = 0) -> None:
+                                   act_dtype: torch.dtype, masked: bool = False, rows: int = 64, map_offset: int = 0,
+                                   wide: bool = False) -> None:
     """``rows``: the block height (``plan.rows_per_block``) of EVERY site of the table (one per table, ABI 6).
-    ``map_offset`` > 0: the table buffer holds the block -> site map at that byte offset (``factors_mfma_table_bytes``)."""
+    ``map_offset`` > 0: the table buffer holds the block -> site map at that byte offset (``factors_mfma_table_bytes``).
+    ``wide``: the table was planned from sites of rank 17..64 (``FM_TABLE_WIDE``; not with ``masked``)."""
+    flags = (FM_TABLE_MASKED if masked else 0) | (FM_TABLE_WIDE if wide else 0)
     if map_offset:
         _check(require().lora_amd_linear_bwd_factors_mfma_ragged_mapped(table_dev.data_ptr(), n, grid,
                                                                         table_dev.data_ptr() + int(map_offset), lds_class,
-                                                                        int(rows), dtype_code(act_dtype), int(bool(masked)),
-                                                                        _stream()),
+                                                                        int(rows), dtype_code(act_dtype), flags, _stream()),
                "lora_amd_linear_bwd_factors_mfma_ragged_mapped")
         return
     _check(require().lora_amd_linear_bwd_factors_mfma_ragged(table_dev.data_ptr(), n, grid, lds_class, int(rows),
-                                                             dtype_code(act_dtype), int(bool(masked)), _stream()),
+                                                             dtype_code(act_dtype), flags, _stream()),
            "lora_amd_linear_bwd_factors_mfma_ragged")
 
 

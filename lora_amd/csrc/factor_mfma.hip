@@ -34,6 +34,12 @@
 //       T / Gt   per row block: every wave leaves the largest |partial| of its share in LDS; the sum of the four is an
 //                upper bound of max|T|, 2^e' brings it into [2^14, 2^15), the slab values leave multiplied by 2^-e'.
 //     bf16 has f32's exponent range: its instantiation carries none of this.
+// Ranks 17..64 (WIDE): both gradients are separable in the rank — dUp[:, j] depends on row j of down only, dDown[j, :] on
+// column j of up only — so a rank-r site is ns = ceil(r / 16) independent rank-16 problems on the same G and X.  Each 16-rank
+// slice gets its own workgroup per row block (the site owns nrb * ns consecutive blocks of the grid), pointed at slice sl of
+// packs that are ns rank-16 packs in a row, writing its 16 rows of a [nparts][16 ns][C] slab; fm_block itself, its 16 x 16 x 32
+// tile and its register classes are those of rank 16.  G / X rows are read ns times; where the ns workgroups of a row block
+// sit in the site's block range is the plan's slice order (adjacent or strided by nrb; strided measured faster, see below).
 // Algorithmic bytes per site: M (N + K) e (G and X once) + the partial slabs 2 RT 4 (N + K) M / R (written here, read by
 // lora_amd_reduce_batched).
 // History: round 4's first form kept the row block of the narrower operand resident in LDS (0.22-0.30 of the roof: ten
@@ -97,25 +103,51 @@ __device__ __forceinline__ void fm_pow2_scale(float mx, int top, float &scale, f
 }
 constexpr int kFmFactorTop = 11, kFmTTop = 14;
 __host__ __device__ inline int fm_rank_tile(int r) { return r <= 4 ? 4 : r <= 8 ? 8 : 16; }
+// Ranks 17..64 (the WIDE form): the rank is cut into ns = ceil(r / 16) slices of 16 and every slice is a rank-16 problem of its
+// own on the same G and X — dUp[:, j] depends on row j of down only, dDown[j, :] on column j of up only.  A wide pack is ns
+// consecutive rank-16 packs [slice][split][c/8][16][8], each with its own 16-byte tail: slice s is exactly the pack of
+// down[16 s : 16 s + 16] / up[:, 16 s : 16 s + 16] zero-padded to 16 ranks (up is read in place at row stride r).
+__host__ __device__ inline int fm_slices(int r) { return r <= 16 ? 1 : (r + 15) >> 4; }
+__host__ __device__ inline int64_t fm_slice_elems(int C) { return (int64_t)C * 32 + 8; }   // one rank-16 pack and its tail
+// one workgroup per (site, side); it walks the side's slices, and every slice takes its own power of two
 __global__ __launch_bounds__(256) void factor_absmax_kernel(const lora_amd_pack_site *__restrict__ sites, int n) {
   __shared__ float s_m[4];
   const lora_amd_pack_site q = sites[blockIdx.x >> 1];
   const bool is_up = blockIdx.x & 1;
   const int C = is_up ? q.N : q.K;
   const float *src = is_up ? q.up : q.down;
-  const int64_t cnt = (int64_t)C * q.r;
-  float m = 0.f;
-  for (int64_t i = threadIdx.x; i < cnt; i += 256) m = fmaxf(m, fabsf(gl(src)[i]));
-  m = fm_wave_max(m);
-  if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    m = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
-    float sc, inv;
-    fm_pow2_scale(m, kFmFactorTop, sc, inv);
-    const int RT = fm_rank_tile(q.r);
-    float *tail = reinterpret_cast<float *>(reinterpret_cast<uint16_t *>(is_up ? q.pk_up : q.pk_down) + (int64_t)C * 2 * RT);
-    gl(tail)[0] = sc; gl(tail)[1] = inv; gl(tail)[2] = 0.f; gl(tail)[3] = 0.f;
+  const int ns = fm_slices(q.r);
+  for (int sl = 0; sl < ns; ++sl) {
+    float m = 0.f;
+    if (ns == 1) {
+      const int64_t cnt = (int64_t)C * q.r;
+      for (int64_t i = threadIdx.x; i < cnt; i += 256) m = fmaxf(m, fabsf(gl(src)[i]));
+    } else {
+      const int rs = min(16, q.r - 16 * sl);   // live ranks of the slice
+      const int cnt = C * 16;                  // (c, jj) over the padded slice
+      if (is_up) {
+        for (int i = threadIdx.x; i < cnt; i += 256) {
+          const int c = i >> 4, jj = i & 15;
+          if (jj < rs) m = fmaxf(m, fabsf(gl(src)[(int64_t)c * q.r + 16 * sl + jj]));
+        }
+      } else {
+        const float *rows = src + (int64_t)16 * sl * C;
+        for (int64_t i = threadIdx.x; i < (int64_t)rs * C; i += 256) m = fmaxf(m, fabsf(gl(rows)[i]));
+      }
+    }
+    m = fm_wave_max(m);
+    __syncthreads();   // the previous slice's s_m has been read
+    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      m = fmaxf(fmaxf(s_m[0], s_m[1]), fmaxf(s_m[2], s_m[3]));
+      float sc, inv;
+      fm_pow2_scale(m, kFmFactorTop, sc, inv);
+      const int RT = fm_rank_tile(q.r);
+      float *tail = reinterpret_cast<float *>(reinterpret_cast<uint16_t *>(is_up ? q.pk_up : q.pk_down) + sl * fm_slice_elems(C) +
+                                              (int64_t)C * 2 * RT);
+      gl(tail)[0] = sc; gl(tail)[1] = inv; gl(tail)[2] = 0.f; gl(tail)[3] = 0.f;
+    }
   }
 }
 
@@ -131,26 +163,33 @@ __global__ __launch_bounds__(256) void factor_pack_kernel(const lora_amd_pack_si
     }
     const lora_amd_pack_site q = sites[lo];
     const int RT = fm_rank_tile(q.r), rts = RT == 4 ? 2 : RT == 8 ? 3 : 4;
-    int64_t p = i - q.begin;                 // piece = (side, c8, jj < RT): down side first
-    const int64_t nd = (int64_t)(q.K >> 3) * RT;
+    int64_t p = i - q.begin;                 // piece = (side, slice, c8, jj < RT): down side first
+    const int ns = fm_slices(q.r);
+    const int64_t nd = (int64_t)(q.K >> 3) * RT * ns;
     const bool is_up = p >= nd;
     if (is_up) p -= nd;
-    const int c8 = (int)(p >> rts), jj = (int)(p & (RT - 1));
     const int C = is_up ? q.N : q.K;
+    int sl = 0;
+    if (ns > 1) {                            // ranks 17..64: ns <= 4 rank-16 packs in a row
+      const int64_t per = (int64_t)(C >> 3) * 16;
+      sl = (int)(p >= per) + (int)(p >= 2 * per) + (int)(p >= 3 * per);
+      p -= sl * per;
+    }
+    const int c8 = (int)(p >> rts), jj = (int)(p & (RT - 1)), j = 16 * sl + jj;
     float v[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = 0.f;
-    if (jj < q.r) {
+    if (j < q.r) {
       if (is_up) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = gl(q.up)[(int64_t)(c8 * 8 + e) * q.r + jj];
+        for (int e = 0; e < 8; ++e) v[e] = gl(q.up)[(int64_t)(c8 * 8 + e) * q.r + j];
       } else {
-        const float *src = q.down + (int64_t)jj * C + c8 * 8;
+        const float *src = q.down + (int64_t)j * C + c8 * 8;
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = gl(src)[e];
       }
     }
-    S *dst = reinterpret_cast<S *>(is_up ? q.pk_up : q.pk_down);
+    S *dst = reinterpret_cast<S *>(is_up ? q.pk_up : q.pk_down) + sl * fm_slice_elems(C);
     if constexpr (kScaled) {   // the tail factor_absmax_kernel wrote in the launch before this one
       const float fs = gl(reinterpret_cast<const float *>(dst + (int64_t)C * 2 * RT))[0];
 #pragma unroll
@@ -225,7 +264,7 @@ struct FmSmem {
   float *pmax;            // [4]
 };
 
-template <class E, bool DROP, int kFrPairs, int MINB, int RG, bool RS2>
+template <class E, bool DROP, int kFrPairs, int MINB, int RG, bool RS2, bool WIDE = false>
 __device__ __forceinline__ void fm_block(const lora_amd_fm_site &sd, const FmSmem &sm, int64_t blk, unsigned long long t_entry = 0,
                                          unsigned long long t_prefix = 0) {
   using S = typename E::storage;
@@ -250,11 +289,25 @@ __device__ __forceinline__ void fm_block(const lora_amd_fm_site &sd, const FmSme
   // from the wave's LDS tile, which every piece crosses anyway for the transposed read of phase 2.
   const int lr = lane >> 2, lc = lane & 3;
   constexpr int R = 32 * NRS;          // == sd.rows_per_block
-  const int64_t rb = blk - sd.block_begin;
+  // WIDE (ranks 17..64): the site owns nrb * ns consecutive workgroups, one per (row block, 16-rank slice); everything below
+  // is the rank-16 problem of slice `sl` on row block `rb` (wave-uniform scalar arithmetic: ns <= 4, so no division).
+  // sd.reserved (the plan's slice order): 0 = the ns slices of a row block on ADJACENT workgroups, 1 = strided by nrb
+  const int ns = WIDE ? fm_slices(sd.r) : 1;   // (a site of rank <= 16 in such a launch is its own single slice)
+  int wrb = 0, sl = 0;
+  if constexpr (WIDE) {
+    const int idx = (int)(blk - sd.block_begin);
+    const int nrb = (int)((sd.M + R - 1) / R);
+    const int sl_s = (int)(idx >= nrb) + (int)(idx >= 2 * nrb) + (int)(idx >= 3 * nrb);
+    const int rb_a = ns == 1 ? idx : ns == 2 ? idx >> 1 : ns == 4 ? idx >> 2 : (int)__umulhi((uint32_t)idx, 0x55555556u);   // idx < 2^31
+    const bool strided = sd.reserved != 0;
+    sl = strided ? sl_s : idx - rb_a * ns;
+    wrb = strided ? idx - sl_s * nrb : rb_a;
+  }
+  const int64_t rb = WIDE ? (int64_t)wrb : blk - sd.block_begin;
   const int64_t m0 = rb * R;
   const int nrows = (int)min((int64_t)R, sd.M - m0);
   const bool ax = sd.resident_is_x != 0;
-  const int RT = fm_rank_tile(sd.r);
+  const int RT = fm_rank_tile(sd.r);   // WIDE: 16
   const S *da = reinterpret_cast<const S *>(ax ? sd.x : sd.g), *db = reinterpret_cast<const S *>(ax ? sd.g : sd.x);
   const int64_t lda = ax ? sd.ldx : sd.ldg, ldb = ax ? sd.ldg : sd.ldx;
   const int Ca = ax ? sd.K : sd.N, Cb = ax ? sd.N : sd.K;
@@ -263,6 +316,10 @@ __device__ __forceinline__ void fm_block(const lora_amd_fm_site &sd, const FmSme
   const FmHeads hdb{(uint32_t)(ax ? sd.g_head_magic : sd.x_head_magic), (ax ? sd.g_head_dim : sd.x_head_dim) >> 3,
                     (ax ? sd.g_head_pad : sd.x_head_pad) >> 3};
   const S *pka = reinterpret_cast<const S *>(ax ? sd.pk_down : sd.pk_up), *pkb = reinterpret_cast<const S *>(ax ? sd.pk_up : sd.pk_down);
+  if constexpr (WIDE) {   // slice sl of the wide packs: a self-contained rank-16 pack (its own tail)
+    pka += sl * fm_slice_elems(Ca);
+    pkb += sl * fm_slice_elems(Cb);
+  }
   const int64_t splita = (int64_t)(Ca >> 3) * RT * 8, splitb = (int64_t)(Cb >> 3) * RT * 8;   // elements per split
   float finv_a = 1.f, finv_b = 1.f;   // f16: 1 / (the power of two the pack multiplied the factor by)
   if constexpr (kScaled) {
@@ -314,8 +371,14 @@ __device__ __forceinline__ void fm_block(const lora_amd_fm_site &sd, const FmSme
     return *gl(reinterpret_cast<const mu32x4 *>(pk + ((uint32_t)cg * fragb + lane16)));
   };
   // slabs: [RT][C] floats per block and operand; lane (j = jj, columns 4 q ..) of a group's two 16-column tiles
+  // (WIDE: [16 ns][C] per block, this workgroup's 16 rows at 16 sl)
   float *outa = (ax ? sd.down_part : sd.up_part) + rb * RT * (int64_t)Ca;
   float *outb = (ax ? sd.up_part : sd.down_part) + rb * RT * (int64_t)Cb;
+  if constexpr (WIDE) {
+    const int64_t srow = rb * (RT * ns) + RT * sl;
+    outa = (ax ? sd.down_part : sd.up_part) + srow * (int64_t)Ca;
+    outb = (ax ? sd.up_part : sd.down_part) + srow * (int64_t)Cb;
+  }
   const uint32_t jrow = jj < RT ? (uint32_t)jj : 0u;
   const uint32_t slaba = (jrow * (uint32_t)Ca + 4u * q) * 4u, slabb = (jrow * (uint32_t)Cb + 4u * q) * 4u;
   unsigned char *stage = s_stage + wave * 32 * kFrPitch;
@@ -543,7 +606,9 @@ __device__ __forceinline__ void fm_block(const lora_amd_fm_site &sd, const FmSme
 }
 
 // HEIGHTS: 1 = every site of the table has 64-row blocks, 0 = 32-row blocks, 2 = both (dispatch per workgroup)
-template <class E, bool DROP, int kFrPairs, int MINB, int RG64, int RG32, int HEIGHTS>
+// WIDE: a table of ranks 17..64 — a workgroup is one (row block, 16-rank slice) of its site (fm_block); false compiles to the
+// rank <= 16 kernel unchanged
+template <class E, bool DROP, int kFrPairs, int MINB, int RG64, int RG32, int HEIGHTS, bool WIDE = false>
 __global__ __launch_bounds__(kFmThreads, MINB) void factors_reg_kernel(const lora_amd_fm_site *__restrict__ sites, int n,
                                                                               const int32_t *__restrict__ block_map) {
   __shared__ __attribute__((aligned(16))) unsigned char s_stage[4 * 32 * kFrPitch];
@@ -589,11 +654,11 @@ __global__ __launch_bounds__(kFmThreads, MINB) void factors_reg_kernel(const lor
   const lora_amd_fm_site sd = sites[lo];
   const FmSmem sm{s_stage, s_part, s_tf, s_pmax};
   const int64_t blk = blockIdx.x;
-  if constexpr (HEIGHTS == 1) fm_block<E, DROP, kFrPairs, MINB, RG64, true>(sd, sm, blk, t_entry, t_prefix);
-  else if constexpr (HEIGHTS == 0) fm_block<E, DROP, kFrPairs, MINB, RG32, false>(sd, sm, blk, t_entry, t_prefix);
+  if constexpr (HEIGHTS == 1) fm_block<E, DROP, kFrPairs, MINB, RG64, true, WIDE>(sd, sm, blk, t_entry, t_prefix);
+  else if constexpr (HEIGHTS == 0) fm_block<E, DROP, kFrPairs, MINB, RG32, false, WIDE>(sd, sm, blk, t_entry, t_prefix);
   else {
-    if (sd.rows_per_block == 64) fm_block<E, DROP, kFrPairs, MINB, RG64, true>(sd, sm, blk, t_entry, t_prefix);   // block-uniform
-    else fm_block<E, DROP, kFrPairs, MINB, RG32, false>(sd, sm, blk, t_entry, t_prefix);
+    if (sd.rows_per_block == 64) fm_block<E, DROP, kFrPairs, MINB, RG64, true, WIDE>(sd, sm, blk, t_entry, t_prefix);   // block-uniform
+    else fm_block<E, DROP, kFrPairs, MINB, RG32, false, WIDE>(sd, sm, blk, t_entry, t_prefix);
   }
 }
 
@@ -646,6 +711,10 @@ static int fm_blocks_per_wg(int64_t nrb) {
 
 static int g_fm_narrow = 1;   // 0: class-1 tables run the wide kernel too (A/B hook, lora_amd_factors_mfma_set_tuning)
 static int g_fm_wide = 0;     // measurement variants of the 10-pair kernel's ring (same hook, bits 4..7; bf16, maskless, rows = 0)
+// ranks 17..64: where the ns slice workgroups of one row block sit in a site's block range (same hook, bit 8; read by
+// lora_amd_factors_mfma_ragged_plan): 0 = adjacent, 1 = strided by the site's row-block count.  Strided is the default: over the
+// SD1.5 tables it measured 1254 against 1322 us at rank 32 and 2347 against 2521 us at rank 64 (profiles/factors_wide_kbench.txt)
+static int g_fm_slice_order = 1;
 
 }  // namespace lora_amd
 
@@ -665,10 +734,11 @@ extern "C" int lora_amd_fm_trace_set(void *buf, int64_t cap_words) {
 // groups in flight per wave: rounds 4-5's geometry), 1 / 2 = the 6-pair kernel at three workgroups per CU with 1 / 2 groups in
 // flight, 3 / 4 / 5 = the 6-pair kernel at two per CU with 2 / 3 / 4 groups in flight; < 0 only reads.  Returns the previous value.
 extern "C" int lora_amd_factors_mfma_set_tuning(int32_t narrow) {
-  const int prev = g_fm_narrow | (g_fm_wide << 4);
-  if (narrow >= 0 && (narrow & 15) <= 5 && (narrow >> 4) <= 4) {
+  const int prev = g_fm_narrow | (g_fm_wide << 4) | (g_fm_slice_order << 8);
+  if (narrow >= 0 && (narrow & 15) <= 5 && ((narrow >> 4) & 15) <= 4 && (narrow >> 8) <= 1) {
     g_fm_narrow = narrow & 15;
-    g_fm_wide = narrow >> 4;
+    g_fm_wide = (narrow >> 4) & 15;
+    g_fm_slice_order = narrow >> 8;
   }
   return prev;
 }
@@ -679,13 +749,17 @@ extern "C" int lora_amd_factors_mfma_plan(int64_t M, int32_t K, int32_t N, int32
   memset(out, 0, sizeof(*out));
   FmGeom g;
   int cls = 0;
-  (void)flags;  // bit 0 (dropout site) selects the masked kernel at launch time; the geometry is the same
+  // bit 0 (dropout site) selects the masked kernel at launch time; the geometry is the same.  Bit 1 (LORA_AMD_FM_PLAN_WIDE):
+  // ranks up to 64 as ns = ceil(r / 16) rank-16 slices — the geometry of the same shape at rank 16, slabs and packs ns times
+  const bool wide = (flags & LORA_AMD_FM_PLAN_WIDE) != 0;
+  if (r > (wide ? 64 : 16)) return LORA_AMD_OK;
+  const int ns = fm_slices(r);
   // the register-resident kernel holds 20 pieces per lane: 64 rows up to 640 columns of the narrower operand, 32 beyond
   if (rows == 0) rows = 64;
-  if (!fm_choose(M, K, N, r, act_dtype, rows, &g, &cls)) return LORA_AMD_OK;
+  if (!fm_choose(M, K, N, std::min(r, 16), act_dtype, rows, &g, &cls)) return LORA_AMD_OK;
   out->supported = 1;
   out->lds_class = cls;
-  out->rank_tile = r <= 4 ? 4 : r <= 8 ? 8 : 16;
+  out->rank_tile = r <= 4 ? 4 : r <= 8 ? 8 : 16 * ns;
   out->rows_per_block = g.R;
   const int64_t nrb = (M + g.R - 1) / g.R;
   out->blocks_per_wg = fm_blocks_per_wg(nrb);
@@ -693,8 +767,9 @@ extern "C" int lora_amd_factors_mfma_plan(int64_t M, int32_t K, int32_t N, int32
   out->lds_bytes = g.lds;
   out->up_part_floats = (int64_t)out->nparts * out->rank_tile * N;
   out->down_part_floats = (int64_t)out->nparts * out->rank_tile * K;
-  out->pack_up_elems = (int64_t)N * 2 * out->rank_tile + 8;    // [2][N/8][RT][8] + the 16-byte tail (f16: the pack's power-of-two scale)
-  out->pack_down_elems = (int64_t)K * 2 * out->rank_tile + 8;
+  // [2][N/8][RT][8] + the 16-byte tail (f16: the pack's power-of-two scale); ranks above 16: ns rank-16 packs, each with its tail
+  out->pack_up_elems = ns > 1 ? ns * fm_slice_elems(N) : (int64_t)N * 2 * out->rank_tile + 8;
+  out->pack_down_elems = ns > 1 ? ns * fm_slice_elems(K) : (int64_t)K * 2 * out->rank_tile + 8;
   return LORA_AMD_OK;
 }
 
@@ -704,12 +779,12 @@ extern "C" int lora_amd_factor_pack_plan(lora_amd_pack_site *sites, int32_t n, i
   for (int i = 0; i < n; ++i) {
     lora_amd_pack_site &q = sites[i];
     LORA_AMD_CHECK(q.down && q.up && q.pk_down && q.pk_up, LORA_AMD_EINVAL, "factor_pack_plan: site %d: null pointer", i);
-    LORA_AMD_CHECK(q.r >= 1 && q.r <= 16, LORA_AMD_ERANK, "factor_pack_plan: site %d: rank %d outside [1,16]", i, q.r);
+    LORA_AMD_CHECK(q.r >= 1 && q.r <= 64, LORA_AMD_ERANK, "factor_pack_plan: site %d: rank %d outside [1,64]", i, q.r);
     LORA_AMD_CHECK(q.N >= 32 && q.K >= 32 && q.N % 32 == 0 && q.K % 32 == 0 && ((uintptr_t)q.pk_down % 16) == 0 &&
                        ((uintptr_t)q.pk_up % 16) == 0,
                    LORA_AMD_EINVAL, "factor_pack_plan: site %d: N, K must be multiples of 32, packs 16-byte aligned", i);
     q.begin = begin;
-    begin += (int64_t)((q.N + q.K) >> 3) * fm_rank_tile(q.r);
+    begin += (int64_t)((q.N + q.K) >> 3) * fm_rank_tile(q.r) * fm_slices(q.r);
   }
   *total = begin;
   return LORA_AMD_OK;
@@ -742,17 +817,23 @@ extern "C" int lora_amd_factors_mfma_ragged_plan(lora_amd_fm_site *sites, int32_
   };
   int64_t begin = 0;
   const int rt0 = sites[0].r <= 4 ? 4 : sites[0].r <= 8 ? 8 : 16;
+  // a table is WIDE (every site of rank 17..64, any mix of slice counts; launched with LORA_AMD_FM_TABLE_WIDE) or not
+  const bool wide = sites[0].r > 16;
   for (int i = 0; i < n; ++i) {
     lora_amd_fm_site &q = sites[i];
     FmGeom g;
     LORA_AMD_CHECK(lds_class == 2 || q.rows_per_block == sites[0].rows_per_block, LORA_AMD_EINVAL,
                    "factors_mfma_ragged_plan: site %d: %d rows per block, site 0: %d (a class-1 table has one block height)", i,
                    q.rows_per_block, sites[0].rows_per_block);
-    LORA_AMD_CHECK(q.r >= 1 && q.r <= 16 && (q.r <= 4 ? 4 : q.r <= 8 ? 8 : 16) == rt0, LORA_AMD_ERANK,
-                   "factors_mfma_ragged_plan: site %d: rank %d (one rank tile per table)", i, q.r);
+    LORA_AMD_CHECK(q.r >= 1 && q.r <= (wide ? 64 : 16) && (q.r > 16) == wide && (q.r <= 4 ? 4 : q.r <= 8 ? 8 : 16) == rt0,
+                   LORA_AMD_ERANK, "factors_mfma_ragged_plan: site %d: rank %d (one rank tile per table; ranks 17..64 in a table of "
+                   "their own)", i, q.r);
+    LORA_AMD_CHECK(!wide || !(q.dropout_p > 0.f), LORA_AMD_EUNSUPPORTED,
+                   "factors_mfma_ragged_plan: site %d: rank %d with dropout (the masked kernel takes ranks <= 16)", i, q.r);
     LORA_AMD_CHECK(q.g && q.x && q.pk_up && q.pk_down && q.up_part && q.down_part, LORA_AMD_EINVAL,
                    "factors_mfma_ragged_plan: site %d: null pointer", i);
-    const bool ok = fm_fit(q.M, q.K, q.N, q.r, act_dtype, q.rows_per_block, lds_class == 1 ? kFmLdsSmall : kFmLdsLarge, &g);
+    const bool ok = fm_fit(q.M, q.K, q.N, std::min(q.r, 16), act_dtype, q.rows_per_block,
+                           lds_class == 1 ? kFmLdsSmall : kFmLdsLarge, &g);
     LORA_AMD_CHECK(ok && ((uintptr_t)q.g % 16) == 0 && ((uintptr_t)q.x % 16) == 0 && q.ldg % 8 == 0 && q.ldx % 8 == 0 &&
                        ((uintptr_t)q.pk_up % 16) == 0 && ((uintptr_t)q.pk_down % 16) == 0 &&
                        heads_ok(q.g_head_dim, q.g_head_pad, q.N, q.ldg) && heads_ok(q.x_head_dim, q.x_head_pad, q.K, q.ldx),
@@ -768,7 +849,14 @@ extern "C" int lora_amd_factors_mfma_ragged_plan(lora_amd_fm_site *sites, int32_
     LORA_AMD_CHECK(q.blocks_per_wg >= 1 && q.blocks_per_wg <= kFmMaxNB, LORA_AMD_EINVAL,
                    "factors_mfma_ragged_plan: site %d: blocks_per_wg %d outside [1, %d]", i, q.blocks_per_wg, kFmMaxNB);
     q.block_begin = begin;
-    begin += (nrb + q.blocks_per_wg - 1) / q.blocks_per_wg;
+    if (wide) {   // one workgroup per (row block, 16-rank slice); the slice order of the kernel rides in `reserved`
+      LORA_AMD_CHECK(q.blocks_per_wg == 1, LORA_AMD_EINVAL, "factors_mfma_ragged_plan: site %d: blocks_per_wg %d at rank %d", i,
+                     q.blocks_per_wg, q.r);
+      q.reserved = g_fm_slice_order;
+      begin += nrb * fm_slices(q.r);
+    } else {
+      begin += (nrb + q.blocks_per_wg - 1) / q.blocks_per_wg;
+    }
   }
   LORA_AMD_CHECK(begin < (1ll << 31), LORA_AMD_EINVAL, "factors_mfma_ragged_plan: too many blocks");
   *grid = begin;
@@ -811,8 +899,13 @@ extern "C" int lora_amd_linear_bwd_factors_mfma_ragged_mapped(const lora_amd_fm_
                  "linear_bwd_factors_mfma_ragged: a class-1 table has one block height");
   LORA_AMD_CHECK(act_dtype == LORA_AMD_F16 || act_dtype == LORA_AMD_BF16, LORA_AMD_EINVAL,
                  "linear_bwd_factors_mfma_ragged: f16 / bf16 activations only");
+  LORA_AMD_CHECK((masked & ~(LORA_AMD_FM_TABLE_MASKED | LORA_AMD_FM_TABLE_WIDE)) == 0, LORA_AMD_EINVAL,
+                 "linear_bwd_factors_mfma_ragged: unknown flag bits %d", masked);
+  LORA_AMD_CHECK(masked != (LORA_AMD_FM_TABLE_MASKED | LORA_AMD_FM_TABLE_WIDE), LORA_AMD_EUNSUPPORTED,
+                 "linear_bwd_factors_mfma_ragged: no masked kernel for a table of ranks 17..64");
   hipStream_t st = (hipStream_t)stream;
-  const bool drop = masked != 0;  // a table of dropout sites: the kernel with the Philox mask on G (straight-line, no per-site branch)
+  const bool drop = (masked & LORA_AMD_FM_TABLE_MASKED) != 0;  // a table of dropout sites: the kernel with the Philox mask on G (straight-line, no per-site branch)
+  const bool wide = (masked & LORA_AMD_FM_TABLE_WIDE) != 0;    // a table of ranks 17..64: a workgroup per (row block, rank slice)
   // register class 1 with 64-row blocks (<= 3 resident column groups per wave): the 6-pair kernels, chosen by
   // lora_amd_factors_mfma_set_tuning; everything else: the 10-pair kernel of its block height
   const int narrow = (lds_class == 1 && rows_per_block == 64) ? g_fm_narrow : 0;
@@ -823,9 +916,22 @@ extern "C" int lora_amd_linear_bwd_factors_mfma_ragged_mapped(const lora_amd_fm_
                                            decltype(rg64)::value, decltype(rg32)::value, decltype(heights)::value>),
                        dim3((unsigned)grid), dim3(kFmThreads), 0, st, sites_dev, n, block_map_dev);
   };
+  auto launch_wide = [&](auto e, auto pairs, auto minb, auto rg64, auto rg32, auto heights) {
+    hipLaunchKernelGGL((factors_reg_kernel<decltype(e), false, decltype(pairs)::value, decltype(minb)::value,
+                                           decltype(rg64)::value, decltype(rg32)::value, decltype(heights)::value, true>),
+                       dim3((unsigned)grid), dim3(kFmThreads), 0, st, sites_dev, n, block_map_dev);
+  };
   constexpr auto narrow_p = int_c<kFrPairsNarrow>;
   constexpr auto wide_p = int_c<kFrPairsWide>;
-  if (g_fm_wide != 0 && narrow == 0 && rows_per_block == 0 && !drop && act_dtype == LORA_AMD_BF16) {
+  if (wide) {
+    // the default tunings only: the three-per-CU 6-pair kernel for class 1 at 64 rows, the 10-pair kernel of the table's height(s)
+    by_dtype<f16_t, bf16_t>(act_dtype, [&](auto e) {
+      if (lds_class == 1 && rows_per_block == 64) launch_wide(e, narrow_p, int_c<3>, int_c<1>, int_c<1>, int_c<1>);
+      else if (rows_per_block == 64) launch_wide(e, wide_p, int_c<2>, int_c<2>, int_c<4>, int_c<1>);
+      else if (rows_per_block == 32) launch_wide(e, wide_p, int_c<2>, int_c<2>, int_c<4>, int_c<0>);
+      else launch_wide(e, wide_p, int_c<2>, int_c<2>, int_c<4>, int_c<2>);
+    });
+  } else if (g_fm_wide != 0 && narrow == 0 && rows_per_block == 0 && !drop && act_dtype == LORA_AMD_BF16) {
     // ring depths of the 10-pair kernel (64-row sites, 32-row sites): 1 = (3, 4), 2 = (4, 4), 3 = (2, 6), 4 = (3, 6); default (2, 4)
     constexpr std::false_type d{};
     if (g_fm_wide == 1) launch(bf16_t{}, d, wide_p, int_c<2>, int_c<3>, int_c<4>, int_c<2>);

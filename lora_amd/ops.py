@@ -304,14 +304,18 @@ class OwedSite(NamedTuple):
     drop: Optional[tuple]
 
 
-def _deferred_plan(sink, g2, x2, down, up, sel=None):
+def _deferred_plan(sink, g2, x2, down, up, sel=None, wide=False):
     """The matrix-core plan of a site whose two factor gradients may go to the step's deferred pass — a trainer state that
-    runs one, no selector, f32 factors, 16-bit rows, a shape the pass takes — else None."""
+    runs one, no selector, f32 factors, 16-bit rows, a shape the pass takes — else None.  ``wide``: the caller's site may
+    enter at rank 17..64 (``WIDE_FACTORS``: the maskless merged-weight sites); every other caller keeps rank <= 16."""
     mw = getattr(getattr(sink, "owner", None), "merged", None)
     if (mw is None or not mw.defer_factors or not _C.FACTORS_MFMA or sel is not None or down.dtype != torch.float32
             or up.dtype != torch.float32 or g2.dtype not in (torch.bfloat16, torch.float16) or x2.dtype != g2.dtype):
         return None
-    plan = _C.factors_mfma_plan(x2.shape[0], down.shape[1], up.shape[0], down.shape[0], g2.dtype)
+    r = down.shape[0]
+    if r > 16 and not (wide and WIDE_FACTORS):
+        return None
+    plan = _C.factors_mfma_plan(x2.shape[0], down.shape[1], up.shape[0], r, g2.dtype, wide=r > 16)
     return plan if plan.supported else None
 
 
@@ -587,10 +591,15 @@ TEMB_ONE_LAUNCH = True
 # (tests/test_gn_resident_route.py and tests/test_gpu_gn_resident.py run both)
 GN_RESIDENT = True
 # maskless Linear adapters of rank 17..64 on the step's merged weights (csrc/merge_step.hip merge_step_wide_kernel: the
-# in-step merge walks the rank in chunks; factor gradients on the rowdot / colreduce primitives in the site's backward);
+# in-step merge walks the rank in chunks; factor gradients: WIDE_FACTORS below);
 # False = the frozen GEMM + primitives route of LoraLinearFunction, forward and backward
 # (tests/test_gpu_merged_wide.py runs both)
 MERGED_WIDE = True
+# factor gradients of those sites in the step's deferred matrix-core pass, as ceil(r / 16) rank-16 slices of the rank <= 16
+# kernel (csrc/factor_mfma.hip, WIDE): a trainer state, 16-bit rows, N and K multiples of 32; False (and every other site
+# of these ranks) = the four primitive launches in the site's backward
+# (tests/test_gpu_factors_wide.py runs both)
+WIDE_FACTORS = True
 
 
 def apply_ab_overrides(spec: str, namespace: dict) -> dict:
@@ -598,7 +607,7 @@ def apply_ab_overrides(spec: str, namespace: dict) -> dict:
     listed in ``allowed`` (and only those) without a code edit; every A/B log under profiles/ names the spec it ran with
     (a constant retired since then is an unknown name here)."""
     allowed = ("ATTN_SHORT_BWD", "CONCAT_GROUPS", "CONV3_FUSED", "GN_RESIDENT", "MASTER_MERGE", "MERGED_WIDE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
-               "WS_DROPOUT_WIDE_BWD")
+               "WS_DROPOUT_WIDE_BWD", "WIDE_FACTORS")
     done = {}
     for item in filter(None, (s.strip() for s in spec.split(","))):
         name, _, val = item.partition("=")
@@ -644,8 +653,9 @@ class MergedWeights:
     ``linear_bwd_factors_self_ragged`` launch after the backward (``flush_factors``; without a trainer state: one
     ``linear_bwd_factors_self`` launch per site, in its backward).
     Eligible: device tensors, dropout not in effect, no selector, frozen weight, f32 factors, rank <= 16 — or rank 17..64
-    on 16-bit weights in the compute dtype (``MERGED_WIDE``: same merge launch form, chunked kernel; factor gradients on the
-    primitives in the site's backward, not deferred).
+    on 16-bit weights in the compute dtype (``MERGED_WIDE``: same merge launch form, chunked kernel; factor gradients in the
+    deferred matrix-core pass as rank-16 slices where it takes the site — ``WIDE_FACTORS`` — else on the primitives in the
+    site's backward).
 
     f32-resident frozen weights under 16-bit autocast (``master_site``): ``lookup`` / ``lookup_group`` are handed the f32
     Parameter itself; the scratch weights take the compute dtype and the in-step merge reads the master (``src_f32``) — no
@@ -950,7 +960,9 @@ class MergedWeights:
                 c = int(st.plan.lds_class)
                 masked = st.drop is not None and st.drop[0] > 0.0
                 cls = (c, masked, int(st.plan.rows_per_block) if c == 1 else 0)
-            groups.setdefault((st.kind, st.g.dtype, 4 if r <= 4 else 8 if r <= 8 else 16, cls), []).append(st)
+            # the third key is the table's rank tile; ranks 17..64 (a WIDE table: any mix of slice counts) go under 64, so a
+            # wide and a narrow site never share a launch
+            groups.setdefault((st.kind, st.g.dtype, 4 if r <= 4 else 8 if r <= 8 else 16 if r <= 16 else 64, cls), []).append(st)
         return groups
 
     def _pack_groups(self, groups) -> None:
@@ -967,7 +979,7 @@ class MergedWeights:
 
     def _table_launch(self, gkey, sites, capturing: bool):
         """Builds and uploads the site table of one group -> (workgroups, the launch on that table)."""
-        kind, dt, _, cls = gkey
+        kind, dt, rank_key, cls = gkey
         dev0 = sites[0].g.device
         if kind != "mfma":
             arr, grid = _C.factors_self_ragged_table([st[:9] for st in sites], dt)   # g .. x_heads
@@ -992,7 +1004,8 @@ class MergedWeights:
         raw, moff = _C.factors_mfma_table_bytes(arr, grid)
         dev = self._upload(gkey, raw, dev0, capturing)
         n = len(sites)
-        return grid, lambda: _C.linear_bwd_factors_mfma_ragged(dev, n, grid, lds_class, dt, masked, height, moff)
+        return grid, lambda: _C.linear_bwd_factors_mfma_ragged(dev, n, grid, lds_class, dt, masked, height, moff,
+                                                               wide=rank_key > 16)
 
     def invalidate(self) -> None:
         """Factor tensors were re-bound (new storage) or a scale changed: rebuild the entries on their next use."""
@@ -1012,7 +1025,15 @@ def _merged_factor_grads(g2, x2, down, up, scale, sink, out_heads, in_heads, K, 
     M, r = x2.shape[0], down.shape[0]
     down_c, up_c = down.contiguous(), up.contiguous()
     if r > 16:
-        return _wide_factor_grads(g2, x2, down_c, up_c, scale, sink, out_heads, in_heads, K, N, tag)
+        # ranks 17..64: the deferred matrix-core pass as rank-16 slices where it takes the site (_deferred_plan: a trainer
+        # state, the pass switched on, 16-bit rows, a supported shape; G / X are read in place, head-padded or not), else
+        # the primitives, here
+        plan = _deferred_plan(sink, g2, x2, down_c, up_c, wide=True)
+        if plan is None:
+            return _wide_factor_grads(g2, x2, down_c, up_c, scale, sink, out_heads, in_heads, K, N, tag)
+        _defer(sink, "mfma", plan, g2, x2, down_c, up_c, scale, out_heads, in_heads)
+        _log("bwd", f"{tag}_dx+factors_deferred_mfma", M, K, N, r)
+        return None, None
     mw = getattr(getattr(sink, "owner", None), "merged", None)
     if mw is not None and mw.defer_factors:
         plan = _deferred_plan(sink, g2, x2, down_c, up_c) if _C.FACTORS_MFMA_MODE == "all" else None
@@ -1030,7 +1051,8 @@ def _merged_factor_grads(g2, x2, down, up, scale, sink, out_heads, in_heads, K, 
 
 
 def _wide_factor_grads(g2, x2, down, up, scale, sink, out_heads, in_heads, K, N, tag):
-    """Both factor gradients of a merged-weight site of rank 17..64, at once (no deferred pass takes these ranks): the
+    """Both factor gradients of a merged-weight site of rank 17..64, at once (a site the deferred pass does not take: no
+    trainer state, f32 rows, N or K off the 32-column groups, ``WIDE_FACTORS`` off): the
     ``primitives`` branch of :func:`_linear_backward` — T = X down^T, dUp = scale G^T T, Gt = scale G up, dDown = Gt^T X —
     accumulated into ``sink`` (beta = 1) when there is one.  Head-padded G / X are unpacked first: against zero-padded factor
     views on the padded rows the copies measured 11-28 % faster (the primitives then read 5/8 of the columns;

@@ -29,14 +29,29 @@ def hchunk(c, hc, hp):
     return (c // hc) * hp + (c % hc) if hc else c
 
 
+def slices(r):
+    """Rank-16 slices of a rank (ranks above 16 run as ceil(r / 16) independent rank-16 problems on the same G and X)."""
+    return 1 if r <= 16 else -(-r // 16)
+
+
+def slice_stride(C):
+    """Element slots between two slices of a wide pack in the model: one split [c8][16][8] and the slice's own tail."""
+    return C * 16 + 8
+
+
 def pack(factor_jc, r):
-    """factor(jj, c) [r, C] -> pk[c8][16][8] (hi split only: the model keeps exact values)."""
+    """factor(jj, c) [r, C] -> pk[slice][c8][16][8] + a tail per slice (hi split only: the model keeps exact values).
+    Rank <= 16: one slice and no tail read; slice s holds ranks 16 s .. 16 s + 15, zero beyond r."""
     C = factor_jc.shape[1]
-    pk = np.zeros((C // 8, 16, 8))
-    for c8 in range(C // 8):
-        for jj in range(r):
-            pk[c8, jj] = factor_jc[jj, c8 * 8:c8 * 8 + 8]
-    return pk.reshape(-1)  # element offsets as the kernel computes them
+    ns = slices(r)
+    out = np.full(ns * slice_stride(C), np.nan)   # the tails stay unwritten: a fragment read that strays into one is caught
+    for sl in range(ns):
+        pk = np.zeros((C // 8, 16, 8))
+        for c8 in range(C // 8):
+            for jj in range(min(16, r - 16 * sl)):
+                pk[c8, jj] = factor_jc[16 * sl + jj, c8 * 8:c8 * 8 + 8]
+        out[sl * slice_stride(C):sl * slice_stride(C) + C * 16] = pk.reshape(-1)  # element offsets as the kernel computes them
+    return out
 
 
 class Lds:
@@ -78,6 +93,7 @@ def phase1(lds, base, pitch, nrt, nks, pk, pk_off, acc):
             for lane in range(64):
                 off = pk_off + ks * 512 + lane * 8
                 b[lane] = pk[off:off + 8]
+            assert not np.isnan(b).any(), "fragment read outside its slice's pack"
             for t in range(nrt):
                 a = np.zeros((64, 8))
                 for lane in range(64):
@@ -140,13 +156,15 @@ def phase2(lds, base, pitch, nk2, ncols, tf, out, col_off, RT):
                 out[jj, col_off + ct * 16 + 4 * q:col_off + ct * 16 + 4 * q + 4] = d[lane]
 
 
-def run_block(g, x, down, up, scale, rb, geom, g_heads=None, x_heads=None):
+def run_block(g, x, down, up, scale, rb, geom, g_heads=None, x_heads=None, sl=0):
     """One workgroup of factors_mfma_kernel.  g [M, N'], x [M, K'] (possibly head-padded physical rows), returns
-    (up_part [RT, N], down_part [RT, K]) of row block rb."""
+    (up_part [RT, N], down_part [RT, K]) of row block rb — at ranks above 16 the 16 slab rows of rank slice ``sl``: the
+    workgroup points both packs at the slice and runs the rank-16 problem."""
     R, cw_full, nch, pa, pb, ax = geom["R"], geom["cw"], geom["nchunk"], geom["pitch_a"], geom["pitch_b"], geom["ax"]
     r = down.shape[0]
     K, N = down.shape[1], up.shape[0]
     RT = 4 if r <= 4 else 8 if r <= 16 and r <= 8 else 16
+    assert 0 <= sl < slices(r)
     M = g.shape[0]
     m0 = rb * R
     nrows = min(R, M - m0)
@@ -159,6 +177,7 @@ def run_block(g, x, down, up, scale, rb, geom, g_heads=None, x_heads=None):
     hca, hpa = (ha[1] // 8, ha[2] // 8) if ha else (0, 0)
     hcb, hpb = (hb[1] // 8, hb[2] // 8) if hb else (0, 0)
     pka, pkb = (pk_down, pk_up) if ax else (pk_up, pk_down)
+    offa, offb = sl * slice_stride(Ca), sl * slice_stride(Cb)   # the slice's own rank-16 pack
     outa, outb = np.zeros((RT, Ca)), np.zeros((RT, Cb))
     bufA, bufB = 0, R * pa
     ttA = bufB + R * pb
@@ -167,7 +186,7 @@ def run_block(g, x, down, up, scale, rb, geom, g_heads=None, x_heads=None):
     assert geom["lds"] == ttB + 32 * fm_tpitch(R)
     stage(lds, bufA, pa, da, None, m0, nrows, R, Ca // 8, 0, hca, hpa)
     acc = [[np.zeros((64, 4)) for _ in range(nrt)] for _ in range(4)]
-    phase1(lds, bufA, pa, nrt, Ca // 32, pka, 0, acc)
+    phase1(lds, bufA, pa, nrt, Ca // 32, pka, offa, acc)
     combine(lds, acc, ttA, nrt, R, scale)
     tf = load_tfrags(lds, ttA, R, nk2)
     acc = [[np.zeros((64, 4)) for _ in range(nrt)] for _ in range(4)]
@@ -175,7 +194,7 @@ def run_block(g, x, down, up, scale, rb, geom, g_heads=None, x_heads=None):
         col0 = c * cw_full
         cw = min(cw_full, Cb - col0)
         stage(lds, bufB, pb, db, None, m0, nrows, R, cw // 8, col0 // 8, hcb, hpb)
-        phase1(lds, bufB, pb, nrt, cw // 32, pkb, (col0 // 8) * 128, acc)
+        phase1(lds, bufB, pb, nrt, cw // 32, pkb, offb + (col0 // 8) * 128, acc)
         phase2(lds, bufB, pb, nk2, cw, tf, outb, col0, RT)
     combine(lds, acc, ttB, nrt, R, scale)
     tf = load_tfrags(lds, ttB, R, nk2)
@@ -216,9 +235,16 @@ def check(M, K, N, r, R, gh=None, xh=None, cap=81920, seed=0):
     gp = heads_pack(g, gh, 7.0) if gh else g
     xp = heads_pack(x, xh, -3.0) if xh else x
     nparts = -(-M // R)
+    ns = slices(r)
     d_up, d_down = np.zeros((N, r)), np.zeros((r, K))
     for rb in range(nparts):
-        up_part, down_part = run_block(gp, xp, down, up, s, rb, geom, gh, xh)
+        if ns == 1:
+            up_part, down_part = run_block(gp, xp, down, up, s, rb, geom, gh, xh)
+        else:   # the block's [16 ns][C] slabs, 16 rows from each slice's workgroup
+            up_part, down_part = np.full((16 * ns, N), np.nan), np.full((16 * ns, K), np.nan)
+            for sl in range(ns):
+                up_part[16 * sl:16 * sl + 16], down_part[16 * sl:16 * sl + 16] = run_block(gp, xp, down, up, s, rb, geom, gh, xh, sl)
+            assert not up_part[r:].any() and not down_part[r:].any(), "slab rows beyond the rank are zero"
         d_up += up_part[:r].T
         d_down += down_part[:r]
     t, gt = s * x @ down.T, s * g @ up
@@ -231,6 +257,8 @@ if __name__ == "__main__":
     for args in [dict(M=70, K=64, N=64, r=4, R=64), dict(M=100, K=64, N=320, r=4, R=32),
                  dict(M=40, K=320, N=96, r=8, R=32), dict(M=64, K=320, N=320, r=16, R=64),
                  dict(M=33, K=320, N=640, r=4, R=64, gh=None, xh=(8, 40, 64)),
-                 dict(M=50, K=320, N=320, r=4, R=32, gh=(8, 40, 64))]:
+                 dict(M=50, K=320, N=320, r=4, R=32, gh=(8, 40, 64)),
+                 dict(M=70, K=64, N=96, r=33, R=64), dict(M=40, K=320, N=96, r=17, R=32),
+                 dict(M=50, K=320, N=320, r=64, R=32, gh=(8, 40, 64))]:
         geom = check(**args)
         print("ok", args, geom)

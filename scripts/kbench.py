@@ -545,6 +545,80 @@ def bench_fm(args):
     print(json.dumps(rec), flush=True)
 
 
+def bench_fm_ranks(args):
+    """The deferred matrix-core factor pass and its fold over the SD1.5 site tables (144 sites, batch 4, 512^2, bf16) at every
+    rank of ``--ranks`` in ONE call: ranks above 16 run as ns = ceil(r / 16) rank-16 slices, one workgroup per (row block,
+    slice), in both slice orders (lora_amd_factors_mfma_set_tuning bit 8, read when the table is planned: 0 = the slices of a
+    row block on adjacent workgroups, 1 = strided by the site's row-block count).  Bytes: G + X once (algorithmic) and the
+    slabs the pass writes and the fold reads; ``frac8`` = algorithmic bytes over 8 TB/s over the time.  ``ns_x_rank16_us`` = ns
+    times the first rank <= 16 of the list, the figure a wide pass is read against; every timing is taken ``--repeats`` times
+    (median of each; the spread of the repeats is printed)."""
+    dt = torch.bfloat16
+    sites = sd15_site_list()
+    byts = sum((M * K + M * N) * 2 for M, K, N in sites)
+    gs, xs = [], []
+    for i, (M, K, N) in enumerate(sites):   # as in the model: q / k / v share one x, cross-attention k / v the text states
+        j = i % 9
+        gs.append(torch.randn(M, N, device=DEV).to(dt))
+        xs.append(xs[i - (j if j < 3 else 1)] if j in (1, 2, 6) else torch.randn(M, K, device=DEV).to(dt))
+    print(json.dumps({"op": "fm_ranks", "sites": len(sites), "GX_GB": round(byts / 1e9, 4), "floor_us_8TBs": round(byts / 8e12 * 1e6, 1),
+                      "repeats": args.repeats}), flush=True)
+    prev = _C.factors_mfma_set_tuning(-1)
+    base16 = None
+    try:
+        for r in [int(v) for v in args.ranks.split(",")]:
+            ns = 1 if r <= 16 else -(-r // 16)
+            downs = [torch.randn(r, K, device=DEV) * 0.25 for _, K, _ in sites]
+            ups = [torch.randn(N, r, device=DEV) * 0.05 for _, _, N in sites]
+            by_cls, packs, rows_m, slab_bytes = {}, [], [], 0
+            for (M, K, N), g, x, down, up in zip(sites, gs, xs, downs, ups):
+                pl = _C.factors_mfma_plan(M, K, N, r, dt, wide=r > 16)
+                assert pl.supported, (M, K, N, r)
+                up_part, down_part = torch.empty(int(pl.up_part_floats), device=DEV), torch.empty(int(pl.down_part_floats), device=DEV)
+                slab_bytes += (int(pl.up_part_floats) + int(pl.down_part_floats)) * 4
+                pk_down = torch.empty(int(pl.pack_down_elems), dtype=dt, device=DEV)
+                pk_up = torch.empty(int(pl.pack_up_elems), dtype=dt, device=DEV)
+                packs.append((down, up, pk_down, pk_up))
+                by_cls.setdefault((int(pl.lds_class), int(pl.rows_per_block) if pl.lds_class == 1 else 0), []).append(
+                    (g, x, pk_down, pk_up, up_part, down_part, 1.0, None, None, r, pl))
+                rows_m += [(up_part, torch.empty(N, r, device=DEV), pl.nparts, pl.rank_tile, N, r, _C.FACTOR_KR, 1.0, 0.0),
+                           (down_part, torch.empty(r, K, device=DEV), pl.nparts, pl.rank_tile, K, r, _C.FACTOR_RK, 1.0, 0.0)]
+            arr, total = _C.factor_pack_table(packs)
+            tab_p = _C.table_to_device(arr, DEV)
+            red = _C.make_reduce_table(rows_m, DEV)
+            rec = {"op": "fm_ranks", "rank": r, "ns": ns, "slab_GB": round(slab_bytes / 1e9, 3),
+                   "pack_us": round(timeit(lambda: _C.factor_pack(tab_p, len(packs), total, dt), inner=5)[0] * 1e6, 1)}
+            folds = [timeit(lambda: _C.reduce_batched(*red), inner=5)[0] * 1e6 for _ in range(args.repeats)]
+            rec["fold_us"] = [round(v, 1) for v in folds]
+            for order in ((0, 1) if r > 16 else (0,)):
+                _C.factors_mfma_set_tuning((prev & 255) | (order << 8))
+                tabs = []
+                for (cls, rpb), ss in sorted(by_cls.items()):   # the trainer's launches: class 1 per height, class 2 both heights
+                    arr, grid = _C.factors_mfma_table(ss, dt, cls)
+                    raw, moff = _C.factors_mfma_table_bytes(arr, grid)
+                    tabs.append((torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(DEV), len(ss), grid, cls, rpb, moff))
+
+                def run():
+                    for tab, cnt, grid, cls, rpb, moff in tabs:
+                        _C.linear_bwd_factors_mfma_ragged(tab, cnt, grid, cls, dt, False, rpb, moff, wide=r > 16)
+
+                ts = [timeit(run, inner=3)[0] * 1e6 for _ in range(args.repeats)]
+                med = sorted(ts)[len(ts) // 2]
+                name = "pass" if r <= 16 else ("pass_adjacent" if order == 0 else "pass_strided")
+                rec[name + "_us"] = [round(v, 1) for v in ts]
+                rec[name + "_frac8"] = round(byts / 8e12 / (med * 1e-6), 3)
+                rec[name + "_blocks"] = sum(t_[2] for t_ in tabs)
+                if r <= 16 and base16 is None:
+                    base16 = med
+            if base16 is not None and r > 16:
+                rec["ns_x_rank16_us"] = round(ns * base16, 1)
+            print(json.dumps(rec), flush=True)
+            del downs, ups, packs, rows_m, by_cls, red, tabs
+            torch.cuda.empty_cache()
+    finally:
+        _C.factors_mfma_set_tuning(prev)
+
+
 def bench_fmtrace(args):
     """Where a block of the factor pass spends its life: the pass from scripts/fm_trace/liblora_amd_trace.so (the same source
     under -DFM_TRACE), every wave's 100 MHz wall-clock stamps averaged per stage, per site type.  LORA_AMD_LIB must point at
@@ -891,6 +965,8 @@ if __name__ == "__main__":
     ap.add_argument("--what", default="merge,linear,ws,conv,hostops")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rank", type=int, default=4)
+    ap.add_argument("--ranks", default="16,32,64", help="fmranks: the ranks of the factor pass, one call")
+    ap.add_argument("--repeats", type=int, default=3, help="fmranks: repeats of every timing (their spread is the call's)")
     a = ap.parse_args()
     print(torch.cuda.get_device_name(0), flush=True)
     if "merge" in a.what:
@@ -915,6 +991,8 @@ if __name__ == "__main__":
         bench_self(a)
     if "fm" in a.what.split(","):
         bench_fm(a)
+    if "fmranks" in a.what.split(","):
+        bench_fm_ranks(a)
     if "fmtrace" in a.what.split(","):
         bench_fmtrace(a)
     if "gemmlayout" in a.what:
