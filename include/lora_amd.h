@@ -154,10 +154,17 @@ int lora_amd_merge_step(const lora_amd_mstep_site *sites_dev, int32_t n, int64_t
 /* Tuning hook (scripts/kbench.py): tile geometry 0..3 = 128x64 | 64x128 | 128x128 | 256x64 (rows x columns; applies to
  * tables planned after the call), dither form 1 = one hash per element, 2 = one hash chain per 16-byte chunk.  < 0 keeps. */
 int lora_amd_merge_step_set_tuning(int32_t tile, int32_t dither);
-/* Ranks 9..16 on 16-bit activations with f32 factors: rowdot / rowdot_masked / rank_update / linear_fwd / linear_bwd_g run
- * their matrix-core forms (csrc/rank16_mfma.hip; same arguments, outputs and partial-buffer geometry).  enable = 0 routes
- * them back to the VALU kernels (parity tests compare the two), 1 = default, < 0 only reads.  Returns the previous value. */
+/* Ranks 9..16 on bf16 activations with f32 factors: rowdot / rowdot_masked / rank_update / linear_fwd / linear_bwd_g run
+ * their matrix-core forms (csrc/rank16_mfma.hip; same arguments, outputs and partial-buffer geometry); ranks 17..64:
+ * rowdot / rowdot_masked / rank_update run the wide forms of the same kernels (ceil(r / 16) rank-16 slices in one launch).
+ * enable = 0 routes all of them back to the VALU kernels (parity tests compare the two), 1 = default, < 0 only reads.
+ * Returns the previous value. */
 int lora_amd_rank16_mfma(int32_t enable);
+/* Pure host arithmetic: 1 exactly when lora_amd_rowdot[_masked] (op 0; cols = K, rows = x, ld = ldx) or lora_amd_rank_update
+ * (op 1; cols = N, rows = y, ld = ldy) would run its matrix-core form on these arguments under the current hook setting —
+ * the predicate the launchers themselves call.  rows is inspected for alignment only; has_selector: sel != NULL. */
+int lora_amd_rank16_mfma_takes(int32_t op, const void *rows, int64_t ld, int64_t M, int32_t cols, int32_t r,
+                               int32_t act_dtype, int32_t factor_dtype, int32_t has_selector);
 
 /* Tuning knobs of the planner/launcher (<= 0 keeps the current value):
  * target elements per tile and resident workgroups per CU (the LDS-slab kernel's grid cap).  blocks_per_cu >= 100
@@ -177,7 +184,10 @@ int lora_amd_merge_set_tuning(int64_t tile_elems, int64_t blocks_per_cu);
 
 /* T[M, r] (f32) = scale * X[M, K] @ F^T, F given as [r,K] or [K,r];
  * optional selector S [r, r] (f32): T <- T @ S^T (sel_transposed=0, forward,
- * lora.py:56,63-70) or T <- T @ S (sel_transposed=1, backward).  sel may be NULL. */
+ * lora.py:56,63-70) or T <- T @ S (sel_transposed=1, backward).  sel may be NULL.
+ * 1 <= r <= LORA_AMD_MAX_RANK.  bf16 rows with f32 factors, 9 <= r <= 64, no selector, K % 32 == 0, 16-byte aligned rows
+ * (x, ldx % 8): the matrix-core form (ranks above 16 as ceil(r / 16) rank-16 slices in the same launch); anything else the
+ * VALU kernel.  lora_amd_rank16_mfma_takes(0, ...) tells which. */
 int lora_amd_rowdot(const void *x, int64_t ldx, const void *factor, void *t_out,
                     int64_t M, int32_t K, int32_t r, int32_t x_dtype,
                     int32_t factor_dtype, int32_t factor_layout, float scale,
@@ -186,7 +196,10 @@ int lora_amd_rowdot(const void *x, int64_t ldx, const void *factor, void *t_out,
 /* Y[M, N] (y_dtype, in place) += scale * mask * T[M, r] (f32) @ F, F given as
  * [r,N] or [N,r].  Dropout (lora.py:45,56): keep-probability 1-p with inverted
  * scaling, generated in-kernel from Philox(seed, offset, offset_dev, element index); p = 0
- * disables it.  The same (seed, offset, offset_dev) reproduces the same mask in rowdot_masked. */
+ * disables it.  The same (seed, offset, offset_dev) reproduces the same mask in rowdot_masked.
+ * 1 <= r <= LORA_AMD_MAX_RANK.  bf16 rows with f32 factors, 9 <= r <= 64, N % 8 == 0, 16-byte aligned rows (y, ldy % 8): the
+ * matrix-core form (ranks above 16: the rank-16 slices chain into one sum, masked once — Y is read and written once, the mask
+ * is the VALU kernel's); anything else the VALU kernel.  lora_amd_rank16_mfma_takes(1, ...) tells which. */
 int lora_amd_rank_update(void *y, int64_t ldy, const float *t, const void *factor,
                          int64_t M, int32_t N, int32_t r, int32_t y_dtype,
                          int32_t factor_dtype, int32_t factor_layout,

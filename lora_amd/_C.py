@@ -292,6 +292,7 @@ FUNCTIONS = (
     ("lora_amd_merge_step", cint, (vp, i32, i64, i32, i32, f32, i32, vp)),
     ("lora_amd_merge_step_set_tuning", cint, (i32, i32)),
     ("lora_amd_rank16_mfma", cint, (i32,)),
+    ("lora_amd_rank16_mfma_takes", cint, (i32, vp, i64, i64, i32, i32, i32, i32, i32)),
     ("lora_amd_merge_set_tuning", cint, (i64, i64)),
     ("lora_amd_rowdot", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32, vp)),
     ("lora_amd_rank_update", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, f32, u64, u64, vp, vp)),
@@ -620,8 +621,18 @@ def factors_mfma_set_tuning(narrow: int = -1) -> int:
 
 
 def rank16_mfma(enable: int = -1) -> int:
-    """Matrix-core forms of the rank-9..16 kernels on / off (csrc/rank16_mfma.hip); returns the previous setting."""
+    """Matrix-core forms of the rank-9..64 kernels on / off (csrc/rank16_mfma.hip); returns the previous setting."""
     return int(require().lora_amd_rank16_mfma(int(enable)))
+
+
+def rank16_mfma_takes(op: int, tensor: torch.Tensor, r: int, factor_dtype: torch.dtype = torch.float32,
+                      has_selector: bool = False) -> int:
+    """1 when ``rowdot`` (op 0) / ``rank_update_`` (op 1) of the 2-D ``tensor`` (X / Y) at rank ``r`` would run its
+    matrix-core form under the current hook setting: the launchers' own predicate (host arithmetic, any device)."""
+    t = _as2d(tensor)
+    M, cols = t.shape
+    return int(require().lora_amd_rank16_mfma_takes(int(op), t.data_ptr(), t.stride(0), M, cols, int(r), dtype_code(t.dtype),
+                                                    dtype_code(factor_dtype), int(bool(has_selector))))
 
 
 def merge_step_set_tuning(tile: int = -1, dither: int = -1) -> None:

@@ -703,9 +703,9 @@ extern "C" int lora_amd_rowdot_masked(const void *x, int64_t ldx, const void *fa
   LORA_AMD_CHECK(dropout_p >= 0.f && dropout_p < 1.f, LORA_AMD_EINVAL, "rowdot: dropout p=%f", dropout_p);
   hipStream_t st = (hipStream_t)stream;
   const bool masked = dropout_p > 0.f;
-  // ranks 9..16 on 16-bit rows: the matrix-core form (csrc/rank16_mfma.hip)
-  if (sel == nullptr && r16_rowdot(x, ldx, factor, factor_dtype, factor_layout, reinterpret_cast<float *>(t_out), M, K, r,
-                                   x_dtype, scale, dropout_p, seed, offset, offset_dev, st))
+  // ranks 9..64 on bf16 rows without a selector: the matrix-core form (csrc/rank16_mfma.hip; r16_takes decides)
+  if (r16_rowdot(x, ldx, factor, factor_dtype, factor_layout, reinterpret_cast<float *>(t_out), M, K, r, x_dtype, scale,
+                 dropout_p, seed, offset, offset_dev, st, sel != nullptr))
     return check_launch("lora_amd_rowdot(mfma)");
   return by_dtype(x_dtype, [&](auto e) {
     using E = decltype(e);

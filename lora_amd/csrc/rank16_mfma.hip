@@ -1,4 +1,5 @@
-// Rank-tile-16 forms of the adapter's streaming kernels on the matrix cores (ranks 9..16, bf16 activations, f32 factors).
+// Rank-tile-16 forms of the adapter's streaming kernels on the matrix cores (ranks 9..16, bf16 activations, f32 factors), and the
+// wide forms of the row product and the rank update (ranks 17..64: ceil(r / 16) rank-16 slices in one launch, template NS).
 //
 // replaces: csrc/linear.hip's rowdot / rank_update kernels and csrc/linear_fused.hip's linear_bwd_g_kernel<E, 16> for
 //           lora_diffusion/lora.py:53-58 (Linear) and lora.py:130-135 (Conv2d, channels-last rows) at rank 16 — BASELINE
@@ -48,9 +49,10 @@ __device__ __forceinline__ mu32x4 r16_zero() { return mu32x4{0u, 0u, 0u, 0u}; }
 // B-operand fragment pair (hi, lo) of the factor for the 32 columns c0 .. c0 + 31: lane (j = l & 15, kq = l >> 4) holds
 // mult * F[j, c0 + 8 kq + e].  layout RK: F = [r, C] (8 consecutive floats); KR: F = [C, r] (stride r).  Two steps, so that
 // a loop can have the next k-step's values in flight: r16_factor_load (global -> 8 floats), r16_factor_split.
+// j0: first rank of the 16-rank slice the fragment holds (the wide forms, ranks 17..64: lane j <-> rank j0 + j, zero at or past r).
 struct R16Raw { float v[8]; };
-__device__ __forceinline__ R16Raw r16_factor_load(const float *__restrict__ f, int layout, int r, int C, int c0) {
-  const int lane = threadIdx.x & 63, jj = lane & 15, kq = lane >> 4;
+__device__ __forceinline__ R16Raw r16_factor_load(const float *__restrict__ f, int layout, int r, int C, int c0, int j0 = 0) {
+  const int lane = threadIdx.x & 63, jj = j0 + (lane & 15), kq = lane >> 4;
   const int c = c0 + 8 * kq;
   R16Raw w;
 #pragma unroll
@@ -82,12 +84,24 @@ __device__ __forceinline__ void r16_factor_frag(const float *__restrict__ f, int
 // ============================================================================ rowdot16
 // A workgroup = `slabs` 16-row slabs x `wps` waves per slab (slabs * wps = blockDim / 64); the waves of a slab take the
 // k-steps ks = cw, cw + wps, ... and meet once in LDS.  Two data pieces and one factor fragment ahead of the MFMAs.
-template <class E, bool DROP>
+// NS: 16-rank slices (1: ranks 9..16; 2..4: the wide form, ranks 17..64).  Both products are linear in the rank, so a wide
+// problem is NS rank-16 problems on the same rows: a wave reads its data piece and draws the piece's dropout mask ONCE and
+// feeds every slice from it (one accumulator and one fragment pair per slice; lane jj of slice sl holds rank 16 sl + jj and
+// reads zero at or past r).  The cross-wave meeting of the wide form carries NS times the floats in dynamic LDS sized by the
+// launch ((waves - slabs) * NS KB, nothing when wps = 1), so that the 256-thread launches of short rows keep their occupancy.
+template <class E, bool DROP, int NS = 1>
 __global__ __launch_bounds__(1024) void rowdot16_mfma_kernel(
     const typename E::storage *__restrict__ x, int64_t ldx, const float *__restrict__ f, int layout, float *__restrict__ t_out,
     int64_t M, int C, int r, int wps, float scale, float p, uint64_t seed, uint64_t offset, const uint64_t *offset_dev) {
   using S = typename E::storage;
-  __shared__ __attribute__((aligned(16))) float s_red[16 * 4 * 64];
+  float *s_red;
+  if constexpr (NS == 1) {
+    __shared__ __attribute__((aligned(16))) float s_red1[16 * 4 * 64];
+    s_red = s_red1;
+  } else {
+    extern __shared__ __attribute__((aligned(16))) float s_red_wide[];
+    s_red = s_red_wide;
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, jj = lane & 15, q = lane >> 4;
   const int nwaves = blockDim.x >> 6, slabs = nwaves / wps;
   const int sl = wave / wps, cw = wave - sl * wps;
@@ -104,45 +118,70 @@ __global__ __launch_bounds__(1024) void rowdot16_mfma_kernel(
   const bool rok = row < M;
   const S *xr = x + (rok ? row : 0) * ldx + 8 * q;
   const int nks = C >> 5;  // C % 32 == 0 (host check)
-  mf32x4 d = {0.f, 0.f, 0.f, 0.f};
+  mf32x4 d[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) d[s] = mf32x4{0.f, 0.f, 0.f, 0.f};
   if (m0 < M) {
     auto piece = [&](int ks) -> mu32x4 {
       return ks < nks ? *gl(reinterpret_cast<const mu32x4 *>(xr + (int64_t)ks * 32)) : r16_zero();
     };
-    mu32x4 c0 = piece(cw), c1 = piece(cw + wps);
-    R16Raw fr = r16_factor_load(f, layout, r, C, (cw < nks ? cw : 0) * 32);
+    // data pieces ahead of the MFMAs: two; one at four slices, whose 8 accumulator and 16 factor dwords more would not
+    // fit beside a third piece in the 128 VGPRs of a 1024-thread workgroup (a k-step of four fragment builds is long enough)
+    constexpr int kAhead = NS < 4 ? 2 : 1;
+    mu32x4 c0 = piece(cw), c1 = kAhead == 2 ? piece(cw + wps) : r16_zero();
+    R16Raw fr[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) fr[s] = r16_factor_load(f, layout, r, C, (cw < nks ? cw : 0) * 32, 16 * s);
 #pragma unroll 1
     for (int ks = cw; ks < nks; ks += wps) {
-      const mu32x4 c2 = piece(ks + 2 * wps);
-      mu32x4 fh, fl;
-      r16_factor_split<E>(fr, sc, fh, fl);
-      if (ks + wps < nks) fr = r16_factor_load(f, layout, r, C, (ks + wps) * 32);
+      const mu32x4 c2 = piece(ks + kAhead * wps);
       mu32x4 cur = c0;
-      if constexpr (DROP) cur &= dropout_and8(seed, off, (uint64_t)(row * (int64_t)(C >> 3) + ks * 4 + q), thr);
-      if (!rok) cur = r16_zero();
-      d = FmMfma<E>::mma(fm_frag<E>(cur), fm_frag<E>(fh), d);
-      d = FmMfma<E>::mma(fm_frag<E>(cur), fm_frag<E>(fl), d);
-      c0 = c1;
+      auto mask_piece = [&]() {  // the piece and its mask: once for all slices
+        if constexpr (DROP) cur &= dropout_and8(seed, off, (uint64_t)(row * (int64_t)(C >> 3) + ks * 4 + q), thr);
+        if (!rok) cur = r16_zero();
+      };
+      if constexpr (NS > 1) mask_piece();  // ahead of the fragments: the Philox temporaries are gone before they arrive
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        mu32x4 fh, fl;
+        r16_factor_split<E>(fr[s], sc, fh, fl);
+        if (ks + wps < nks) fr[s] = r16_factor_load(f, layout, r, C, (ks + wps) * 32, 16 * s);
+        if constexpr (NS == 1) mask_piece();
+        d[s] = FmMfma<E>::mma(fm_frag<E>(cur), fm_frag<E>(fh), d[s]);
+        d[s] = FmMfma<E>::mma(fm_frag<E>(cur), fm_frag<E>(fl), d[s]);
+      }
+      c0 = kAhead == 2 ? c1 : c2;
       c1 = c2;
     }
   }
   if (wps > 1) {  // block-uniform
+    // slot of a partial: the wave itself (NS = 1, static 16 KB) | the slab's waves 1 .. wps - 1 packed (wide, dynamic)
+    const int slot = NS == 1 ? wave : sl * (wps - 1) + cw - 1;
     if (cw > 0) {
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) s_red[(wave * 4 + reg) * 64 + lane] = d[reg];
+      for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) s_red[((slot * NS + s) * 4 + reg) * 64 + lane] = d[s][reg];
     }
     __syncthreads();
     if (cw > 0) return;
-    for (int k = 1; k < wps; ++k)
+    for (int k = 1; k < wps; ++k) {
+      const int src = NS == 1 ? wave + k : sl * (wps - 1) + k - 1;
 #pragma unroll
-      for (int reg = 0; reg < 4; ++reg) d[reg] += s_red[((wave + k) * 4 + reg) * 64 + lane];
+      for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) d[s][reg] += s_red[((src * NS + s) * 4 + reg) * 64 + lane];
+    }
   }
-  // D: lane (column j = jj, rows 4 q + reg)
-  if (jj < r && m0 < M) {
+  // D: lane (column j = 16 s + jj, rows 4 q + reg)
 #pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int64_t rw = m0 + 4 * q + reg;
-      if (rw < M) t_out[rw * r + jj] = d[reg];
+  for (int s = 0; s < NS; ++s) {
+    if (16 * s + jj < r && m0 < M) {
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int64_t rw = m0 + 4 * q + reg;
+        if (rw < M) t_out[rw * r + 16 * s + jj] = d[s][reg];
+      }
     }
   }
 }
@@ -151,12 +190,17 @@ __global__ __launch_bounds__(1024) void rowdot16_mfma_kernel(
 // grid (row blocks of `rows_per_block` = 64 | 128 | 256, column splits of 128 columns); a wave owns ONE 32-column group:
 // its two A fragments are built once and meet every 16-row slab of the block, whose T fragments all four waves share
 // through LDS.
-template <class E, bool DROP>
+// NS: 16-rank slices (1: ranks 9..16; 2..4: the wide form, ranks 17..64).  The dropout mask belongs to the SUM over the ranks,
+// so the slices chain into the same two accumulators of a slab (slice 0 first: zero ranks beyond 16 change no bit of the
+// narrow kernel's result): Y is read, masked and written once.  A fragments ua[NS][2]; the T image holds NS fragment pairs
+// per slab, and the rows of a workgroup come down with it (kR16RuSlabs: at most 32 KB of LDS).
+constexpr int kR16RuSlabs[5] = {0, 16, 8, 4, 4};  // 16-row slabs of a workgroup's T image per slice count
+template <class E, bool DROP, int NS = 1>
 __global__ __launch_bounds__(kR16Threads) void rank_update16_mfma_kernel(
     typename E::storage *__restrict__ y, int64_t ldy, const float *__restrict__ t, int nparts, int64_t part_stride,
     const float *__restrict__ f, int layout, int64_t M, int N, int r, int rows_per_block, float scale, float p, uint64_t seed,
     uint64_t offset, const uint64_t *offset_dev) {
-  __shared__ __attribute__((aligned(16))) mu32x4 s_t[16 * 2 * 64];  // [slab][hi, lo][lane]: B operands (32 KB)
+  __shared__ __attribute__((aligned(16))) mu32x4 s_t[kR16RuSlabs[NS] * NS * 2 * 64];  // [slab][slice][hi, lo][lane]: B operands
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, mm = lane & 15, q = lane >> 4;
   const int64_t m0 = (int64_t)blockIdx.x * rows_per_block;
   const int nrows = (int)min((int64_t)rows_per_block, M - m0);
@@ -166,42 +210,48 @@ __global__ __launch_bounds__(kR16Threads) void rank_update16_mfma_kernel(
   // B operands: T of the block's 16-row slabs, (hi | hi) and (lo | lo) along k
   for (int s = wave; s < nslabs; s += 4) {
     const int64_t row = m0 + s * 16 + mm;
-    float v[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = 0.f;
-    if (row < M) {
-      const int j0 = 8 * (q & 1);
-      for (int pi = 0; pi < nparts; ++pi) {
-        const float *tp = t + pi * part_stride + row * r;
+    for (int sl = 0; sl < NS; ++sl) {
+      float v[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (j0 + e < r) v[e] += gl(tp)[j0 + e];
+      for (int e = 0; e < 8; ++e) v[e] = 0.f;
+      if (row < M) {
+        const int j0 = 16 * sl + 8 * (q & 1);
+        for (int pi = 0; pi < nparts; ++pi) {
+          const float *tp = t + pi * part_stride + row * r;
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (j0 + e < r) v[e] += gl(tp)[j0 + e];
+        }
       }
+      mu32x4 hi, lo;
+      split_hi_lo<E>(v, hi, lo);
+      s_t[((s * NS + sl) * 2 + 0) * 64 + lane] = hi;
+      s_t[((s * NS + sl) * 2 + 1) * 64 + lane] = lo;
     }
-    mu32x4 hi, lo;
-    split_hi_lo<E>(v, hi, lo);
-    s_t[(s * 2 + 0) * 64 + lane] = hi;
-    s_t[(s * 2 + 1) * 64 + lane] = lo;
   }
   const int n0 = (blockIdx.y * 4 + wave) * 32;
   // A operands of the two interleaved tiles: lane (i = mm, kq = q) holds (hi for kq < 2, lo for kq >= 2) of
-  // U[n(i, tile), 8 (kq & 1) + e], n(i, tile) = n0 + 8 (i / 4) + 4 tile + i % 4
-  mu32x4 ua[2];
+  // U[n(i, tile), 16 slice + 8 (kq & 1) + e], n(i, tile) = n0 + 8 (i / 4) + 4 tile + i % 4
+  mu32x4 ua[NS][2];
 #pragma unroll
-  for (int tile = 0; tile < 2; ++tile) {
-    const int n = n0 + 8 * (mm >> 2) + 4 * tile + (mm & 3);
-    const int j0 = 8 * (q & 1);
-    float v[8];
+  for (int sl = 0; sl < NS; ++sl) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = 0.f;
-    if (n < N) {
+    for (int tile = 0; tile < 2; ++tile) {
+      const int n = n0 + 8 * (mm >> 2) + 4 * tile + (mm & 3);
+      const int j0 = 16 * sl + 8 * (q & 1);
+      float v[8];
 #pragma unroll
-      for (int e = 0; e < 8; ++e)
-        if (j0 + e < r) v[e] = layout == LORA_AMD_FACTOR_KR ? gl(f)[(int64_t)n * r + j0 + e] : gl(f)[(int64_t)(j0 + e) * N + n];
+      for (int e = 0; e < 8; ++e) v[e] = 0.f;
+      if (n < N) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (j0 + e < r) v[e] = layout == LORA_AMD_FACTOR_KR ? gl(f)[(int64_t)n * r + j0 + e] : gl(f)[(int64_t)(j0 + e) * N + n];
+      }
+      mu32x4 hi, lo;
+      split_hi_lo<E>(v, hi, lo);
+      ua[sl][tile] = q < 2 ? hi : lo;
     }
-    mu32x4 hi, lo;
-    split_hi_lo<E>(v, hi, lo);
-    ua[tile] = q < 2 ? hi : lo;
   }
   __syncthreads();
   const int col = n0 + 8 * q;  // this lane's 16-byte chunk of each row
@@ -216,13 +266,16 @@ __global__ __launch_bounds__(kR16Threads) void rank_update16_mfma_kernel(
 #pragma unroll 1
   for (int s = 0; s < nslabs; ++s) {
     const mu32x4 y2 = yload(s + 2);
-    const mu32x4 th = s_t[(s * 2 + 0) * 64 + lane], tl = s_t[(s * 2 + 1) * 64 + lane];
     const int64_t row = m0 + s * 16 + mm;
     mf32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
-    d0 = FmMfma<E>::mma(fm_frag<E>(ua[0]), fm_frag<E>(th), d0);
-    d0 = FmMfma<E>::mma(fm_frag<E>(ua[0]), fm_frag<E>(tl), d0);
-    d1 = FmMfma<E>::mma(fm_frag<E>(ua[1]), fm_frag<E>(th), d1);
-    d1 = FmMfma<E>::mma(fm_frag<E>(ua[1]), fm_frag<E>(tl), d1);
+#pragma unroll
+    for (int sl = 0; sl < NS; ++sl) {
+      const mu32x4 th = s_t[((s * NS + sl) * 2 + 0) * 64 + lane], tl = s_t[((s * NS + sl) * 2 + 1) * 64 + lane];
+      d0 = FmMfma<E>::mma(fm_frag<E>(ua[sl][0]), fm_frag<E>(th), d0);
+      d0 = FmMfma<E>::mma(fm_frag<E>(ua[sl][0]), fm_frag<E>(tl), d0);
+      d1 = FmMfma<E>::mma(fm_frag<E>(ua[sl][1]), fm_frag<E>(th), d1);
+      d1 = FmMfma<E>::mma(fm_frag<E>(ua[sl][1]), fm_frag<E>(tl), d1);
+    }
     // lane (row m = mm, q): d0[reg] -> column col + reg, d1[reg] -> column col + 4 + reg
     float pr[8] = {d0[0], d0[1], d0[2], d0[3], d1[0], d1[1], d1[2], d1[3]};
     if constexpr (DROP) {
@@ -696,26 +749,54 @@ __global__ __launch_bounds__(256) void split16_transpose_kernel(const lora_amd_s
 // bf16 activations only (round 6): the (hi, lo) split of `up` ~ 1e-4 (lora.py:50-51 starts it at 0) and of Gt = s G up
 // ~ 1e-8 .. 1e-3 needs f32's exponent range, which bf16 has and f16 has not — f16 activations at ranks 9..16 take the VALU
 // kernels (exact f32 arithmetic on the converted data); the one-launch factor pass (factor_mfma.hip) pre-scales instead.
-static bool r16_common_ok(int act_dtype, int fdt, int r) {
-  return g_r16_mfma && act_dtype == LORA_AMD_BF16 && fdt == LORA_AMD_F32 && r > 8 && r <= 16;
+// rmax: 16 for bwd_g16 (one rank tile), 64 for the row product and the rank update (the wide forms: 17..64 as 2..4 slices).
+static bool r16_common_ok(int act_dtype, int fdt, int r, int rmax) {
+  return g_r16_mfma && act_dtype == LORA_AMD_BF16 && fdt == LORA_AMD_F32 && r > 8 && r <= rmax;
+}
+
+// rows of a rank_update16 workgroup: as many as keep >= 768 workgroups (the A fragments are rebuilt per workgroup), at most
+// what the T image of `ns` slices holds (256 | 128 | 64 | 64)
+static int r16_ru_rows(int64_t M, int64_t ny, int ns) {
+  int rows = 16 * kR16RuSlabs[ns];
+  while (rows > 64 && ((M + rows - 1) / rows) * ny < 768) rows >>= 1;
+  return rows;
+}
+
+// THE predicate of the two launchers below (and of lora_amd_rank16_mfma_takes, which only exposes it): does this call run its
+// matrix-core form?  op 0 = rowdot (cols = C), 1 = rank_update (cols = N); `rows` is inspected for alignment only.
+// No shape class of ranks 17..64 is held back: profiles/r16_wide_kbench.txt has the wide forms ahead of the VALU kernels on
+// every shape of the leg.
+bool r16_takes(int op, const void *rows, int64_t ld, int64_t M, int cols, int r, int act_dtype, int fdt, bool has_sel) {
+  if (!r16_common_ok(act_dtype, fdt, r, 64) || has_sel || ld % 8 || ((uintptr_t)rows & 15u) || M <= 0 || cols <= 0) return false;
+  if (op == 0) return cols % 32 == 0 && (M + 15) / 16 <= 0x7fffffff;
+  if (op != 1 || cols % 8) return false;
+  const int64_t ny = ((int64_t)cols + 127) / 128;  // a wave = one 32-column group
+  const int rpb = r16_ru_rows(M, ny, (r + 15) / 16);
+  return (M + rpb - 1) / rpb <= 0x7fffffff && ny <= 65535;
 }
 
 bool r16_rowdot(const void *x, int64_t ldx, const void *f, int fdt, int layout, float *t_out, int64_t M, int C, int r,
-                int act_dtype, float scale, float p, uint64_t seed, uint64_t offset, const uint64_t *offset_dev, hipStream_t st) {
-  if (!r16_common_ok(act_dtype, fdt, r) || C % 32 || ldx % 8 || ((uintptr_t)x & 15u) || M <= 0) return false;
+                int act_dtype, float scale, float p, uint64_t seed, uint64_t offset, const uint64_t *offset_dev, hipStream_t st,
+                bool has_sel) {
+  if (!r16_takes(0, x, ldx, M, C, r, act_dtype, fdt, has_sel)) return false;
   // waves per 16-row slab: >= 4 k-steps per wave, ~4096 waves in flight at most (a wave's chain of dependent loads is what
-  // bounds a long row: 576 rows x 10240 columns on one wave per slab took 110-154 us, profiles/r04_kbench_r16_first.log)
-  const int nks = C >> 5;
+  // bounds a long row: 576 rows x 10240 columns on one wave per slab took 110-154 us, profiles/r04_kbench_r16_first.log).
+  // The wide forms keep the rule: a k-step of theirs is longer (ns fragment pairs), the chain of data loads is the same.
+  const int nks = C >> 5, ns = (r + 15) / 16;
   const int64_t nslabs = (M + 15) / 16;
   int wps = 1;
   while (wps < 16 && nks / (2 * wps) >= 4 && nslabs * wps < 4096) wps *= 2;
   const int slabs = wps <= 4 ? 4 / wps : 1;
   const unsigned block = (unsigned)(64 * wps * slabs);
   const unsigned grid = (unsigned)((nslabs + slabs - 1) / slabs);
+  // the wide forms' meeting place: 1 KB per slice and wave that hands its partial over (60 KB at 16 waves x 4 slices)
+  const size_t lds = ns > 1 && wps > 1 ? (size_t)(wps - 1) * slabs * ns * 4 * 64 * sizeof(float) : 0;
   const float *ff = reinterpret_cast<const float *>(f);
   by_bool(p > 0.f, [&](auto d) {
-    hipLaunchKernelGGL((rowdot16_mfma_kernel<bf16_t, decltype(d)::value>), dim3(grid), dim3(block), 0, st,
-                       reinterpret_cast<const bf16_t::storage *>(x), ldx, ff, layout, t_out, M, C, r, wps, scale, p, seed, offset, offset_dev);
+    by_int<1, 2, 3, 4>(ns, [&](auto n) {
+      hipLaunchKernelGGL((rowdot16_mfma_kernel<bf16_t, decltype(d)::value, decltype(n)::value>), dim3(grid), dim3(block), lds, st,
+                         reinterpret_cast<const bf16_t::storage *>(x), ldx, ff, layout, t_out, M, C, r, wps, scale, p, seed, offset, offset_dev);
+    });
   });
   return true;
 }
@@ -723,18 +804,17 @@ bool r16_rowdot(const void *x, int64_t ldx, const void *f, int fdt, int layout, 
 bool r16_rank_update(void *y, int64_t ldy, const float *t, int nparts, int64_t part_stride, const void *f, int fdt, int layout,
                      int64_t M, int N, int r, int act_dtype, float scale, float p, uint64_t seed, uint64_t offset,
                      const uint64_t *offset_dev, hipStream_t st) {
-  if (!r16_common_ok(act_dtype, fdt, r) || N % 8 || ldy % 8 || ((uintptr_t)y & 15u) || M <= 0 || nparts < 1) return false;
-  const int64_t ny = (N + 127) / 128;  // a wave = one 32-column group
-  // rows per workgroup: as many as keep >= 768 workgroups (the A fragments are rebuilt per workgroup)
-  int rows = 256;
-  while (rows > 64 && ((M + rows - 1) / rows) * ny < 768) rows >>= 1;
+  if (!r16_takes(1, y, ldy, M, N, r, act_dtype, fdt, false) || nparts < 1) return false;
+  const int64_t ny = (N + 127) / 128;
+  const int ns = (r + 15) / 16, rows = r16_ru_rows(M, ny, ns);
   const int64_t gx = (M + rows - 1) / rows;
-  if (gx > 0x7fffffff || ny > 65535) return false;
   const float *ff = reinterpret_cast<const float *>(f);
   by_bool(p > 0.f, [&](auto d) {
-    hipLaunchKernelGGL((rank_update16_mfma_kernel<bf16_t, decltype(d)::value>), dim3((unsigned)gx, (unsigned)ny), dim3(kR16Threads), 0, st,
-                       reinterpret_cast<bf16_t::storage *>(y), ldy, t, nparts, part_stride, ff, layout, M, N, r,
-                       rows, scale, p, seed, offset, offset_dev);
+    by_int<1, 2, 3, 4>(ns, [&](auto n) {
+      hipLaunchKernelGGL((rank_update16_mfma_kernel<bf16_t, decltype(d)::value, decltype(n)::value>), dim3((unsigned)gx, (unsigned)ny),
+                         dim3(kR16Threads), 0, st, reinterpret_cast<bf16_t::storage *>(y), ldy, t, nparts, part_stride, ff, layout,
+                         M, N, r, rows, scale, p, seed, offset, offset_dev);
+    });
   });
   return true;
 }
@@ -743,7 +823,7 @@ bool r16_bwd_g(const void *g, int64_t ldg, const float *t, const void *up, int f
                int N, int r, int log_ct8, int nct, int rows_per_block, int64_t nrb, int act_dtype, float scale, float p,
                uint64_t seed, uint64_t offset, const uint64_t *offset_dev, hipStream_t st, float *gt_out, unsigned *counters) {
   const int cw = 8 << log_ct8;
-  if (!r16_common_ok(act_dtype, fdt, r) || cw < 32 || cw > 512 || rows_per_block > 128 || N % 8 || ldg % 8 ||
+  if (!r16_common_ok(act_dtype, fdt, r, 16) || cw < 32 || cw > 512 || rows_per_block > 128 || N % 8 || ldg % 8 ||
       ((uintptr_t)g & 15u) || M <= 0 || !up_part || ((uintptr_t)up_part & 15u) || nrb * nct > 0x7fffffff)
     return false;
   const unsigned grid = (unsigned)(nrb * nct);
@@ -758,12 +838,19 @@ bool r16_bwd_g(const void *g, int64_t ldg, const float *t, const void *up, int f
 
 }  // namespace lora_amd
 
-// Tuning / test hook: 0 routes ranks 9..16 back to the VALU kernels (parity tests compare both), 1 (default) the
+// Tuning / test hook: 0 routes ranks 9..64 back to the VALU kernels (parity tests compare both), 1 (default) the
 // matrix-core forms.  Returns the previous value.
 extern "C" int lora_amd_rank16_mfma(int32_t enable) {
   const int prev = lora_amd::g_r16_mfma;
   if (enable >= 0) lora_amd::g_r16_mfma = enable ? 1 : 0;
   return prev;
+}
+
+// Pure host: 1 when lora_amd_rowdot[_masked] (op 0) / lora_amd_rank_update (op 1) would run the matrix-core form on these
+// arguments under the current hook setting — the launchers' own predicate, not a restatement of it.
+extern "C" int lora_amd_rank16_mfma_takes(int32_t op, const void *rows, int64_t ld, int64_t M, int32_t cols, int32_t r,
+                                          int32_t act_dtype, int32_t factor_dtype, int32_t has_selector) {
+  return lora_amd::r16_takes(op, rows, ld, M, cols, r, act_dtype, factor_dtype, has_selector != 0) ? 1 : 0;
 }
 
 using namespace lora_amd;

@@ -144,27 +144,40 @@ def bench_mstep(args):
 
 def bench_r16(args):
     """Rank-16 kernels of BASELINE configs[3] (768^2, batch 1, dropout 0.1): matrix-core form (csrc/rank16_mfma.hip) against
-    the VALU kernel it replaces, same call, hook on / off.  Bytes: the activation once (rowdot, bwd_g) or twice (rank_update)."""
-    r, p, dt = 16, 0.1, torch.bfloat16
+    the VALU kernel it replaces, same call, hook on / off.  Bytes: the activation once (rowdot, bwd_g) or twice (rank_update).
+    Ranks 32 and 64 (the wide forms of rowdot / rank_update: 2 and 4 rank-16 slices in one launch) on the same shapes; the
+    rank-16 lines are what they are read against (``mfma_over_r16`` / ``valu_over_r16``: the time ratios per kernel, next to
+    the factor re-read ratio of the row product, 2 : 1 at rank 16, 8 : 1 at rank 64).  bwd_g exists at rank 16 only."""
+    p, dt = 0.1, torch.bfloat16
+    ranks = (16, 32, 64)
     for (M, C) in ((9216, 320), (9216, 2560), (2304, 640), (2304, 5120), (576, 1280), (576, 10240), (144, 1280), (77, 1280)):
         a = torch.randn(M, C, device=DEV).to(dt)
-        t = torch.randn(M, r, device=DEV)
-        fkr, frk = torch.randn(C, r, device=DEV) * 0.2, torch.randn(r, C, device=DEV) * 0.2
-        plan = _C.linear_plan(M, 320, C, r)
-        gt_part = torch.empty(plan.gt_part_floats, device=DEV)
-        up_part = torch.empty(plan.up_part_floats, device=DEV)
-        calls = {"rowdot_masked": (lambda: _C.rowdot(a, fkr, _C.FACTOR_KR, 0.7, None, False, p, 5, 9), M * C * 2),
-                 "rowdot": (lambda: _C.rowdot(a, frk, _C.FACTOR_RK, 1.0), M * C * 2),
-                 "rank_update": (lambda: _C.rank_update_(a, t, fkr, _C.FACTOR_KR, 1e-3, p, 5, 9), 2 * M * C * 2),
-                 "bwd_g": (lambda: _C.linear_bwd_g(a, t, fkr, gt_part, up_part, 0.7, p, 5, 9), M * C * 2)}
-        for name, (fn, byts) in calls.items():
-            res = dict(kernel=name, M=M, C=C, r=r)
-            for tag, on in (("mfma", 1), ("valu", 0)):
-                prev = _C.rank16_mfma(on)
-                med, _ = timeit(fn, args.iters)
-                _C.rank16_mfma(prev)
-                res[tag + "_us"], res[tag + "_GBs"] = round(med * 1e6, 2), round(byts / med / 1e9, 1)
-            print(json.dumps(res), flush=True)
+        base = {}
+        for r in ranks:
+            t = torch.randn(M, r, device=DEV)
+            fkr, frk = torch.randn(C, r, device=DEV) * 0.2, torch.randn(r, C, device=DEV) * 0.2
+            calls = {"rowdot_masked": (lambda: _C.rowdot(a, fkr, _C.FACTOR_KR, 0.7, None, False, p, 5, 9), M * C * 2),
+                     "rowdot": (lambda: _C.rowdot(a, frk, _C.FACTOR_RK, 1.0), M * C * 2),
+                     "rank_update": (lambda: _C.rank_update_(a, t, fkr, _C.FACTOR_KR, 1e-3, p, 5, 9), 2 * M * C * 2)}
+            if r == 16:
+                plan = _C.linear_plan(M, 320, C, r)
+                gt_part = torch.empty(plan.gt_part_floats, device=DEV)
+                up_part = torch.empty(plan.up_part_floats, device=DEV)
+                calls["bwd_g"] = (lambda: _C.linear_bwd_g(a, t, fkr, gt_part, up_part, 0.7, p, 5, 9), M * C * 2)
+            for name, (fn, byts) in calls.items():
+                res = dict(kernel=name, M=M, C=C, r=r)
+                for tag, on in (("mfma", 1), ("valu", 0)):
+                    prev = _C.rank16_mfma(on)
+                    med, best = timeit(fn, args.iters)
+                    _C.rank16_mfma(prev)
+                    res[tag + "_us"], res[tag + "_best_us"] = round(med * 1e6, 2), round(best * 1e6, 2)
+                    res[tag + "_GBs"] = round(byts / med / 1e9, 1)
+                if r == 16:
+                    base[name] = res
+                elif name in base:
+                    res["mfma_over_r16"] = round(res["mfma_us"] / base[name]["mfma_us"], 2)
+                    res["valu_over_r16"] = round(res["valu_us"] / base[name]["valu_us"], 2)
+                print(json.dumps(res), flush=True)
 
 
 def bench_linear(args):
