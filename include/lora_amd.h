@@ -677,15 +677,24 @@ typedef struct lora_amd_fm_site {
   const uint64_t *offset_dev;
 } lora_amd_fm_site;
 /* A table is narrow (every rank <= 16, one rank tile) or WIDE (every rank in 17..64, any mix of slice counts): a mixed one is
- * LORA_AMD_ERANK, a wide site with dropout_p > 0 LORA_AMD_EUNSUPPORTED.  A wide site owns nrb * ns consecutive blocks of the
+ * LORA_AMD_ERANK.  This entry answers LORA_AMD_EUNSUPPORTED for a wide site with dropout_p > 0: such a table is planned by
+ * lora_amd_factors_mfma_ragged_plan_masked below.  A wide site owns nrb * ns consecutive blocks of the
  * grid (nrb = ceil(M / rows_per_block)) and its slabs are [nparts][16 ns][C] (lora_amd_factors_mfma_plan, LORA_AMD_FM_PLAN_WIDE). */
 int lora_amd_factors_mfma_ragged_plan(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype, int32_t lds_class,
                                       int64_t *grid);
+/* The same plan (arguments, results, checks: one implementation) that also takes dropout_p > 0 at ranks 17..64 (ABI 7, additive).
+ * The mask of a site is indexed by G's own row and 8-column chunk, so the ns slice workgroups of a row block regenerate the same
+ * mask and the masked wide pass is ns masked rank-16 passes; `scale` arrives with 1 / (1 - p) folded in, as at rank <= 16.  A wide
+ * table may mix masked and maskless sites and any slice counts; wide and narrow sites stay apart (LORA_AMD_ERANK), and so does a
+ * rank above 64.  A table with a masked site of rank 17..64 is launched by lora_amd_linear_bwd_factors_mfma_wide_masked. */
+int lora_amd_factors_mfma_ragged_plan_masked(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype, int32_t lds_class,
+                                             int64_t *grid);
 /* masked: a flags word.  Bit 0 (LORA_AMD_FM_TABLE_MASKED): 0 = no site of the table has dropout_p > 0; 1 = the kernel that
  * regenerates the dropout mask on G (sites with dropout_p = 0 in such a table run unmasked).  Bit 1 (LORA_AMD_FM_TABLE_WIDE):
  * the table was planned from sites of rank 17..64 (a workgroup is one (row block, 16-rank slice) of its site) — the caller's
  * promise: the launcher cannot see the device table, and a wide table launched without the bit reads past its rows.  Both
- * bits: LORA_AMD_EUNSUPPORTED. */
+ * bits: LORA_AMD_EUNSUPPORTED from the two entries that take this word — a masked wide table has its own entry,
+ * lora_amd_linear_bwd_factors_mfma_wide_masked. */
 #define LORA_AMD_FM_TABLE_MASKED 1
 #define LORA_AMD_FM_TABLE_WIDE 2
 /* rows_per_block (ABI 6): the block height (32 / 64) every site of the table was planned with — a compile-time constant of
@@ -701,6 +710,13 @@ int lora_amd_factors_mfma_block_map(const lora_amd_fm_site *sites /* host, plann
 int lora_amd_linear_bwd_factors_mfma_ragged_mapped(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid,
                                                    const int32_t *block_map_dev, int32_t lds_class, int32_t rows_per_block,
                                                    int32_t act_dtype, int32_t masked, void *stream);
+/* A WIDE table (ranks 17..64) in which sites carry dropout_p > 0, planned by lora_amd_factors_mfma_ragged_plan_masked (ABI 7,
+ * additive): the arguments of the _mapped entry without the flag word (block_map_dev may be NULL), the same argument checks
+ * before any launch, the masked instantiation of the wide kernel of (lds_class, rows_per_block).  Sites with dropout_p = 0 in
+ * such a table run unmasked. */
+int lora_amd_linear_bwd_factors_mfma_wide_masked(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid,
+                                                 const int32_t *block_map_dev, int32_t lds_class, int32_t rows_per_block,
+                                                 int32_t act_dtype, void *stream);
 /* Tuning / test hook: which kernel a table of class 1 (64-row blocks) runs — 0 = the 10-pair kernel every class can take (two
  * workgroups per CU, two column groups in flight per wave), 1 / 2 = the 6-pair kernel at three workgroups per CU with 1 / 2
  * groups in flight, 3 / 4 / 5 = the 6-pair kernel at two per CU with 2 / 3 / 4 groups in flight; < 0 only reads.  Returns the

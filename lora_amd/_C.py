@@ -358,9 +358,11 @@ FUNCTIONS = (
     ("lora_amd_factor_pack_plan", cint, (P(PackSite), i32, P(i64))),
     ("lora_amd_factor_pack", cint, (vp, i32, i64, i32, vp)),
     ("lora_amd_factors_mfma_ragged_plan", cint, (P(FmSite), i32, i32, i32, P(i64))),
+    ("lora_amd_factors_mfma_ragged_plan_masked", cint, (P(FmSite), i32, i32, i32, P(i64))),
     ("lora_amd_linear_bwd_factors_mfma_ragged", cint, (vp, i32, i64, i32, i32, i32, i32, vp)),
     ("lora_amd_factors_mfma_block_map", cint, (P(FmSite), i32, i64, P(i32))),
     ("lora_amd_linear_bwd_factors_mfma_ragged_mapped", cint, (vp, i32, i64, vp, i32, i32, i32, i32, vp)),
+    ("lora_amd_linear_bwd_factors_mfma_wide_masked", cint, (vp, i32, i64, vp, i32, i32, i32, vp)),
     ("lora_amd_factors_mfma_set_tuning", cint, (i32,)),
     ("lora_amd_conv_plan", cint, (i32, i32, i32, i32, i32, i32, i32, P(ConvPlan))),
     ("lora_amd_conv_down_fwd", cint, (vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp)),
@@ -1341,8 +1343,11 @@ def factors_mfma_table(sites, act_dtype: torch.dtype, lds_class: int):
     x_heads, r, plan[, (p, seed, offset)])] of one LDS class and rank tile (``plan`` = the site's ``factors_mfma_plan``;
     the optional last item = nn.Dropout on the branch: ``scale`` is then multiplied by 1 / (1 - p) here) -> (planned ctypes
     table, grid).  Sites of rank 17..64 (``plan`` taken with ``wide=True``) make a WIDE table: any mix of slice counts, no
-    site of rank <= 16 beside them; it is launched with ``wide=True``."""
+    site of rank <= 16 beside them; it is launched with ``wide=True``.  A wide site with a dropout triple sends the table
+    through ``lora_amd_factors_mfma_ragged_plan_masked`` (the older entry keeps refusing it); such a table may hold maskless
+    sites too and is launched with ``masked=True, wide=True``."""
     arr = (FmSite * len(sites))()
+    wide_masked = False
     for q, site in zip(arr, sites):
         g, x, pk_down, pk_up, up_part, down_part, scale, g_heads, x_heads, r, plan = site[:11]
         drop = site[11] if len(site) > 11 else None
@@ -1350,6 +1355,7 @@ def factors_mfma_table(sites, act_dtype: torch.dtype, lds_class: int):
             p, seed, off = drop
             q.dropout_p, q.seed = float(p), int(seed)
             scale = float(scale) / (1.0 - float(p))
+            wide_masked = wide_masked or int(r) > 16
             if torch.is_tensor(off):
                 q.offset, q.offset_dev = 0, off.data_ptr()
             else:
@@ -1364,8 +1370,8 @@ def factors_mfma_table(sites, act_dtype: torch.dtype, lds_class: int):
         q.g_head_dim, q.g_head_pad = (g_heads[1], g_heads[2]) if g_heads else (0, 0)
         q.x_head_dim, q.x_head_pad = (x_heads[1], x_heads[2]) if x_heads else (0, 0)
     grid = C.c_int64(0)
-    _check(require().lora_amd_factors_mfma_ragged_plan(arr, len(sites), dtype_code(act_dtype), lds_class, C.byref(grid)),
-           "lora_amd_factors_mfma_ragged_plan")
+    name = "lora_amd_factors_mfma_ragged_plan" + ("_masked" if wide_masked else "")
+    _check(getattr(require(), name)(arr, len(sites), dtype_code(act_dtype), lds_class, C.byref(grid)), name)
     return arr, grid.value
 
 
@@ -1389,7 +1395,14 @@ def linear_bwd_factors_mfma_ragged(table_dev: torch.Tensor, n: int, grid: int, l
                                    wide: bool = False) -> None:
     """``rows``: the block height (``plan.rows_per_block``) of EVERY site of the table (one per table, ABI 6).
     ``map_offset`` > 0: the table buffer holds the block -> site map at that byte offset (``factors_mfma_table_bytes``).
-    ``wide``: the table was planned from sites of rank 17..64 (``FM_TABLE_WIDE``; not with ``masked``)."""
+    ``wide``: the table was planned from sites of rank 17..64 (``FM_TABLE_WIDE``).  ``masked`` and ``wide`` together: the
+    table's own entry, ``lora_amd_linear_bwd_factors_mfma_wide_masked`` (the flag word of the other two refuses the pair)."""
+    if masked and wide:
+        bmap = table_dev.data_ptr() + int(map_offset) if map_offset else None
+        _check(require().lora_amd_linear_bwd_factors_mfma_wide_masked(table_dev.data_ptr(), n, grid, bmap, lds_class, int(rows),
+                                                                      dtype_code(act_dtype), _stream()),
+               "lora_amd_linear_bwd_factors_mfma_wide_masked")
+        return
     flags = (FM_TABLE_MASKED if masked else 0) | (FM_TABLE_WIDE if wide else 0)
     if map_offset:
         _check(require().lora_amd_linear_bwd_factors_mfma_ragged_mapped(table_dev.data_ptr(), n, grid,

@@ -40,6 +40,8 @@
 // packs that are ns rank-16 packs in a row, writing its 16 rows of a [nparts][16 ns][C] slab; fm_block itself, its 16 x 16 x 32
 // tile and its register classes are those of rank 16.  G / X rows are read ns times; where the ns workgroups of a row block
 // sit in the site's block range is the plan's slice order (adjacent or strided by nrb; strided measured faster, see below).
+// nn.Dropout on such a site (DROP and WIDE): the mask is indexed by G's own row and 8-column chunk, so every slice of a row block
+// regenerates the same one — the masked wide pass is ns masked rank-16 passes, with no code of its own.
 // Algorithmic bytes per site: M (N + K) e (G and X once) + the partial slabs 2 RT 4 (N + K) M / R (written here, read by
 // lora_amd_reduce_batched).
 // History: round 4's first form kept the row block of the narrower operand resident in LDS (0.22-0.30 of the roof: ten
@@ -806,8 +808,10 @@ extern "C" int lora_amd_factor_pack(const lora_amd_pack_site *sites_dev, int32_t
   return check_launch("lora_amd_factor_pack");
 }
 
-extern "C" int lora_amd_factors_mfma_ragged_plan(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype, int32_t lds_class,
-                                                 int64_t *grid) {
+// both ragged-plan entries; wide_dropout: a site of rank 17..64 may carry dropout_p > 0 (the table is then launched with
+// lora_amd_linear_bwd_factors_mfma_wide_masked)
+static int fm_ragged_plan(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype, int32_t lds_class, int64_t *grid,
+                          bool wide_dropout) {
   LORA_AMD_CHECK(sites && n >= 1 && grid && (lds_class == 1 || lds_class == 2), LORA_AMD_EINVAL,
                  "factors_mfma_ragged_plan: bad argument");
   LORA_AMD_CHECK(act_dtype == LORA_AMD_F16 || act_dtype == LORA_AMD_BF16, LORA_AMD_EINVAL,
@@ -828,8 +832,9 @@ extern "C" int lora_amd_factors_mfma_ragged_plan(lora_amd_fm_site *sites, int32_
     LORA_AMD_CHECK(q.r >= 1 && q.r <= (wide ? 64 : 16) && (q.r > 16) == wide && (q.r <= 4 ? 4 : q.r <= 8 ? 8 : 16) == rt0,
                    LORA_AMD_ERANK, "factors_mfma_ragged_plan: site %d: rank %d (one rank tile per table; ranks 17..64 in a table of "
                    "their own)", i, q.r);
-    LORA_AMD_CHECK(!wide || !(q.dropout_p > 0.f), LORA_AMD_EUNSUPPORTED,
-                   "factors_mfma_ragged_plan: site %d: rank %d with dropout (the masked kernel takes ranks <= 16)", i, q.r);
+    LORA_AMD_CHECK(!wide || wide_dropout || !(q.dropout_p > 0.f), LORA_AMD_EUNSUPPORTED,
+                   "factors_mfma_ragged_plan: site %d: rank %d with dropout (lora_amd_factors_mfma_ragged_plan_masked plans it)", i,
+                   q.r);
     LORA_AMD_CHECK(q.g && q.x && q.pk_up && q.pk_down && q.up_part && q.down_part, LORA_AMD_EINVAL,
                    "factors_mfma_ragged_plan: site %d: null pointer", i);
     const bool ok = fm_fit(q.M, q.K, q.N, std::min(q.r, 16), act_dtype, q.rows_per_block,
@@ -863,6 +868,16 @@ extern "C" int lora_amd_factors_mfma_ragged_plan(lora_amd_fm_site *sites, int32_
   return LORA_AMD_OK;
 }
 
+extern "C" int lora_amd_factors_mfma_ragged_plan(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype, int32_t lds_class,
+                                                 int64_t *grid) {
+  return fm_ragged_plan(sites, n, act_dtype, lds_class, grid, false);
+}
+
+extern "C" int lora_amd_factors_mfma_ragged_plan_masked(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype, int32_t lds_class,
+                                                        int64_t *grid) {
+  return fm_ragged_plan(sites, n, act_dtype, lds_class, grid, true);
+}
+
 extern "C" int lora_amd_factors_mfma_block_map(const lora_amd_fm_site *sites, int32_t n, int64_t grid, int32_t *map) {
   LORA_AMD_CHECK(sites && map && n >= 1 && grid >= 1, LORA_AMD_EINVAL, "factors_mfma_block_map: bad argument");
   int64_t b = 0;
@@ -885,10 +900,11 @@ extern "C" int lora_amd_linear_bwd_factors_mfma_ragged(const lora_amd_fm_site *s
                                                         stream);
 }
 
-extern "C" int lora_amd_linear_bwd_factors_mfma_ragged_mapped(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid,
-                                                              const int32_t *block_map_dev, int32_t lds_class,
-                                                              int32_t rows_per_block, int32_t act_dtype, int32_t masked,
-                                                              void *stream) {
+// every launch entry of the pass: the argument checks, then the kernel of (dtype, masked, wide, class, height).  Masked AND wide
+// is lora_amd_linear_bwd_factors_mfma_wide_masked's alone (wide_masked); the flag word of the older entries keeps refusing it
+static int fm_launch_table(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid, const int32_t *block_map_dev,
+                           int32_t lds_class, int32_t rows_per_block, int32_t act_dtype, int32_t masked, void *stream,
+                           bool wide_masked) {
   LORA_AMD_CHECK(((uintptr_t)block_map_dev % 4) == 0, LORA_AMD_EINVAL, "linear_bwd_factors_mfma_ragged: block map not aligned");
   LORA_AMD_CHECK(sites_dev && n >= 1 && grid >= 1 && grid < (1ll << 31) && (lds_class == 1 || lds_class == 2),
                  LORA_AMD_EINVAL, "linear_bwd_factors_mfma_ragged: bad argument");
@@ -901,8 +917,9 @@ extern "C" int lora_amd_linear_bwd_factors_mfma_ragged_mapped(const lora_amd_fm_
                  "linear_bwd_factors_mfma_ragged: f16 / bf16 activations only");
   LORA_AMD_CHECK((masked & ~(LORA_AMD_FM_TABLE_MASKED | LORA_AMD_FM_TABLE_WIDE)) == 0, LORA_AMD_EINVAL,
                  "linear_bwd_factors_mfma_ragged: unknown flag bits %d", masked);
-  LORA_AMD_CHECK(masked != (LORA_AMD_FM_TABLE_MASKED | LORA_AMD_FM_TABLE_WIDE), LORA_AMD_EUNSUPPORTED,
-                 "linear_bwd_factors_mfma_ragged: no masked kernel for a table of ranks 17..64");
+  LORA_AMD_CHECK(wide_masked || masked != (LORA_AMD_FM_TABLE_MASKED | LORA_AMD_FM_TABLE_WIDE), LORA_AMD_EUNSUPPORTED,
+                 "linear_bwd_factors_mfma_ragged: a masked table of ranks 17..64 is launched by "
+                 "lora_amd_linear_bwd_factors_mfma_wide_masked");
   hipStream_t st = (hipStream_t)stream;
   const bool drop = (masked & LORA_AMD_FM_TABLE_MASKED) != 0;  // a table of dropout sites: the kernel with the Philox mask on G (straight-line, no per-site branch)
   const bool wide = (masked & LORA_AMD_FM_TABLE_WIDE) != 0;    // a table of ranks 17..64: a workgroup per (row block, rank slice)
@@ -916,20 +933,24 @@ extern "C" int lora_amd_linear_bwd_factors_mfma_ragged_mapped(const lora_amd_fm_
                                            decltype(rg64)::value, decltype(rg32)::value, decltype(heights)::value>),
                        dim3((unsigned)grid), dim3(kFmThreads), 0, st, sites_dev, n, block_map_dev);
   };
-  auto launch_wide = [&](auto e, auto pairs, auto minb, auto rg64, auto rg32, auto heights) {
-    hipLaunchKernelGGL((factors_reg_kernel<decltype(e), false, decltype(pairs)::value, decltype(minb)::value,
+  auto launch_wide = [&](auto e, auto d, auto pairs, auto minb, auto rg64, auto rg32, auto heights) {
+    hipLaunchKernelGGL((factors_reg_kernel<decltype(e), decltype(d)::value, decltype(pairs)::value, decltype(minb)::value,
                                            decltype(rg64)::value, decltype(rg32)::value, decltype(heights)::value, true>),
                        dim3((unsigned)grid), dim3(kFmThreads), 0, st, sites_dev, n, block_map_dev);
   };
   constexpr auto narrow_p = int_c<kFrPairsNarrow>;
   constexpr auto wide_p = int_c<kFrPairsWide>;
   if (wide) {
-    // the default tunings only: the three-per-CU 6-pair kernel for class 1 at 64 rows, the 10-pair kernel of the table's height(s)
+    // the default tunings only: the three-per-CU 6-pair kernel for class 1 at 64 rows, the 10-pair kernel of the table's height(s);
+    // masked: the same four with the Philox mask on G — it is indexed by G's own row and column chunk, so every slice of a row
+    // block regenerates the same mask
     by_dtype<f16_t, bf16_t>(act_dtype, [&](auto e) {
-      if (lds_class == 1 && rows_per_block == 64) launch_wide(e, narrow_p, int_c<3>, int_c<1>, int_c<1>, int_c<1>);
-      else if (rows_per_block == 64) launch_wide(e, wide_p, int_c<2>, int_c<2>, int_c<4>, int_c<1>);
-      else if (rows_per_block == 32) launch_wide(e, wide_p, int_c<2>, int_c<2>, int_c<4>, int_c<0>);
-      else launch_wide(e, wide_p, int_c<2>, int_c<2>, int_c<4>, int_c<2>);
+      by_bool(drop, [&](auto d) {
+        if (lds_class == 1 && rows_per_block == 64) launch_wide(e, d, narrow_p, int_c<3>, int_c<1>, int_c<1>, int_c<1>);
+        else if (rows_per_block == 64) launch_wide(e, d, wide_p, int_c<2>, int_c<2>, int_c<4>, int_c<1>);
+        else if (rows_per_block == 32) launch_wide(e, d, wide_p, int_c<2>, int_c<2>, int_c<4>, int_c<0>);
+        else launch_wide(e, d, wide_p, int_c<2>, int_c<2>, int_c<4>, int_c<2>);
+      });
     });
   } else if (g_fm_wide != 0 && narrow == 0 && rows_per_block == 0 && !drop && act_dtype == LORA_AMD_BF16) {
     // ring depths of the 10-pair kernel (64-row sites, 32-row sites): 1 = (3, 4), 2 = (4, 4), 3 = (2, 6), 4 = (3, 6); default (2, 4)
@@ -953,4 +974,18 @@ extern "C" int lora_amd_linear_bwd_factors_mfma_ragged_mapped(const lora_amd_fm_
     });
   }
   return check_launch("lora_amd_linear_bwd_factors_mfma_ragged");
+}
+
+extern "C" int lora_amd_linear_bwd_factors_mfma_ragged_mapped(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid,
+                                                              const int32_t *block_map_dev, int32_t lds_class,
+                                                              int32_t rows_per_block, int32_t act_dtype, int32_t masked,
+                                                              void *stream) {
+  return fm_launch_table(sites_dev, n, grid, block_map_dev, lds_class, rows_per_block, act_dtype, masked, stream, false);
+}
+
+extern "C" int lora_amd_linear_bwd_factors_mfma_wide_masked(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid,
+                                                            const int32_t *block_map_dev, int32_t lds_class,
+                                                            int32_t rows_per_block, int32_t act_dtype, void *stream) {
+  return fm_launch_table(sites_dev, n, grid, block_map_dev, lds_class, rows_per_block, act_dtype,
+                         LORA_AMD_FM_TABLE_MASKED | LORA_AMD_FM_TABLE_WIDE, stream, true);
 }

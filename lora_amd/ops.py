@@ -304,19 +304,32 @@ class OwedSite(NamedTuple):
     drop: Optional[tuple]
 
 
-def _deferred_plan(sink, g2, x2, down, up, sel=None, wide=False):
+def _deferred_plan(sink, g2, x2, down, up, sel=None, wide=False, merged=True):
     """The matrix-core plan of a site whose two factor gradients may go to the step's deferred pass — a trainer state that
     runs one, no selector, f32 factors, 16-bit rows, a shape the pass takes — else None.  ``wide``: the caller's site may
-    enter at rank 17..64 (``WIDE_FACTORS``: the maskless merged-weight sites); every other caller keeps rank <= 16."""
+    enter at rank 17..64 — under ``WIDE_FACTORS`` from the merged-weight route (``merged``: the maskless sites), under
+    ``WIDE_DROPOUT`` from :class:`LoraLinearFunction` (the sites nn.Dropout keeps off the merged weights); every other
+    caller keeps rank <= 16."""
     mw = getattr(getattr(sink, "owner", None), "merged", None)
     if (mw is None or not mw.defer_factors or not _C.FACTORS_MFMA or sel is not None or down.dtype != torch.float32
             or up.dtype != torch.float32 or g2.dtype not in (torch.bfloat16, torch.float16) or x2.dtype != g2.dtype):
         return None
     r = down.shape[0]
-    if r > 16 and not (wide and WIDE_FACTORS):
+    if r > 16 and not (wide and (WIDE_FACTORS if merged else WIDE_DROPOUT)):
         return None
     plan = _C.factors_mfma_plan(x2.shape[0], down.shape[1], up.shape[0], r, g2.dtype, wide=r > 16)
     return plan if plan.supported else None
+
+
+def _wide_site_plan(sink, g2, x2, down, up, sel, needs):
+    """The deferred-pass plan of a :class:`LoraLinearFunction` site of rank 17..64 whose backward leaves both factor
+    gradients to it (``WIDE_DROPOUT``), else None: no selector, no gradient of the frozen weight, both factor gradients
+    wanted, G and X rows the kernels read in place, and :func:`_deferred_plan`'s conditions."""
+    _, need_w, _, need_down, need_up = needs
+    if (not 17 <= down.shape[0] <= 64 or sel is not None or need_w or not (need_down and need_up)
+            or not _C._rows_ok(g2) or not _C._rows_ok(x2)):
+        return None
+    return _deferred_plan(sink, g2, x2, down, up, wide=True, merged=False)
 
 
 def _defer(sink, kind, plan, g2, x2, down, up, scale, g_heads=None, x_heads=None, drop=None) -> None:
@@ -522,6 +535,19 @@ def _linear_backward(saved, needs, g, s, drop, sink, fused, has_bias, x_shape):
             dx = dx2.view(x_shape)
         if not deferred:
             d_down, d_up = _finish(sink, site, bufs(), down, up)
+    elif (plan_w := _wide_site_plan(sink, g2, x2, down_c, up_c, sel, needs)) is not None:
+        # ranks 17..64 of a trainer's step (WIDE_DROPOUT; nn.Dropout keeps these sites off the merged weights): both factor
+        # gradients are the deferred matrix-core pass's, which recomputes T and regenerates the forward's mask on G in every
+        # rank-16 slice; what is launched here is only what dX needs — Gt and the low-rank term on the matrix-core primitives
+        # around the frozen GEMM — and nothing at all where the input takes no gradient (cross-attention k / v on the text
+        # states, the time-embedding projections)
+        if need_x:
+            gt = rowdot_any(g2, up_c, _C.FACTOR_KR, s, None, True, p, seed, off)
+            dx2 = g2 @ weight  # frozen dense GEMM
+            rank_update_any_(dx2, gt, down_c, _C.FACTOR_RK, 1.0)
+            dx = dx2.view(x_shape)
+        _defer(sink, "mfma", plan_w, g2, x2, down_c, up_c, s, drop=drop)
+        _log("bwd", ("rowdot+lib+rank_update+" if need_x else "") + "factors_deferred_mfma", M, K, N, r)
     else:
         gt = None
         _log("bwd", "primitives", M, K, N, r)
@@ -600,6 +626,12 @@ MERGED_WIDE = True
 # of these ranks) = the four primitive launches in the site's backward
 # (tests/test_gpu_factors_wide.py runs both)
 WIDE_FACTORS = True
+# factor gradients of the rank 17..64 Linear sites that run LoraLinearFunction in a trainer's step (nn.Dropout on the branch —
+# inject_trainable_lora_extended puts it on every site — keeps them off the merged weights) in the same deferred pass, the
+# forward's mask regenerated on G in every rank-16 slice (csrc/factor_mfma.hip, DROP and WIDE); the site's backward launches
+# only what dX needs, nothing where the input takes no gradient; False = the primitives in the site's backward
+# (tests/test_gpu_factors_wide_masked.py runs both)
+WIDE_DROPOUT = True
 
 
 def apply_ab_overrides(spec: str, namespace: dict) -> dict:
@@ -607,7 +639,7 @@ def apply_ab_overrides(spec: str, namespace: dict) -> dict:
     listed in ``allowed`` (and only those) without a code edit; every A/B log under profiles/ names the spec it ran with
     (a constant retired since then is an unknown name here)."""
     allowed = ("ATTN_SHORT_BWD", "CONCAT_GROUPS", "CONV3_FUSED", "GN_RESIDENT", "MASTER_MERGE", "MERGED_WIDE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
-               "WS_DROPOUT_WIDE_BWD", "WIDE_FACTORS")
+               "WS_DROPOUT_WIDE_BWD", "WIDE_FACTORS", "WIDE_DROPOUT")
     done = {}
     for item in filter(None, (s.strip() for s in spec.split(","))):
         name, _, val = item.partition("=")

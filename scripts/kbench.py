@@ -623,6 +623,21 @@ def bench_fm_ranks(args):
                 rec[name + "_blocks"] = sum(t_[2] for t_ in tabs)
                 if r <= 16 and base16 is None:
                     base16 = med
+            if args.fm_dropout > 0.0:
+                # the same tables with nn.Dropout(p) on every site (the forward's Philox mask regenerated on G), default slice
+                # order: what the mask costs the pass, against the maskless timing of the same call
+                tabs = []
+                for (cls, rpb), ss in sorted(by_cls.items()):
+                    arr, grid = _C.factors_mfma_table([s + ((args.fm_dropout, 1234 + i, 8 * i),) for i, s in enumerate(ss)], dt, cls)
+                    raw, moff = _C.factors_mfma_table_bytes(arr, grid)
+                    tabs.append((torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(DEV), len(ss), grid, cls, rpb, moff))
+
+                def run_masked():
+                    for tab, cnt, grid, cls, rpb, moff in tabs:
+                        _C.linear_bwd_factors_mfma_ragged(tab, cnt, grid, cls, dt, True, rpb, moff, wide=r > 16)
+
+                rec["pass_masked_us"] = [round(timeit(run_masked, inner=3)[0] * 1e6, 1) for _ in range(args.repeats)]
+                rec["pass_masked_p"] = args.fm_dropout
             if base16 is not None and r > 16:
                 rec["ns_x_rank16_us"] = round(ns * base16, 1)
             print(json.dumps(rec), flush=True)
@@ -980,6 +995,7 @@ if __name__ == "__main__":
     ap.add_argument("--rank", type=int, default=4)
     ap.add_argument("--ranks", default="16,32,64", help="fmranks: the ranks of the factor pass, one call")
     ap.add_argument("--repeats", type=int, default=3, help="fmranks: repeats of every timing (their spread is the call's)")
+    ap.add_argument("--fm-dropout", type=float, default=0.0, help="fmranks: also time the masked pass (nn.Dropout(p) on every site)")
     a = ap.parse_args()
     print(torch.cuda.get_device_name(0), flush=True)
     if "merge" in a.what:
