@@ -836,6 +836,28 @@ int lora_amd_conv3_nhwc_bwd_dx(void *dx, const float *gt, const void *pd, int32_
 /* down_part [nsplit][rank_pad][C_in * 9] f32: per-workgroup partial sums of dDown (rows >= r are not written). */
 int lora_amd_conv3_nhwc_bwd_down(const void *x, const float *gt, float *down_part, int32_t B, int32_t C_in,
                                  int32_t H, int32_t W, int32_t r, int32_t act_dtype, void *stream);
+/* Ranks 20, 24, .., 64: ns = ceil(r / 16) rank-16 slices inside ONE launch per contraction (slice s = ranks 16 s .. 16 s + 15,
+ * the last one with 4, 8, 12 or 16 live ranks).  T and Gt stay dense [B*H*W, r] f32.  Same geometry conditions as above.
+ * lora_amd_conv3_nhwc_wide_plan fills the same struct: rank_pad = 16 ns, ks = 5, pf_elems = ns * 9 * C_in * 16,
+ * pd_elems = ns * C_in * 160, t_part_floats = ksplit * B*H*W * r (ksplit > 1), down_part_floats = nsplit * 16 ns * C_in * 9;
+ * native = 0 for every other rank <= LORA_AMD_MAX_RANK (ranks <= 16 belong to lora_amd_conv3_nhwc_plan), LORA_AMD_ERANK above.
+ *   pf: ns consecutive rank-16 forward packs, pd: ns consecutive rank-16 input-gradient packs (ks = 5 each); slice s is bit
+ *       for bit what lora_amd_conv3_nhwc_pack writes for down[16 s : 16 s + 16] zero-padded to 16 ranks (no low-part rows:
+ *       the factor is rounded to the activation dtype, as at rank 12 / 16).  One launch packs both.
+ *   t_part: [ksplit][B*H*W][r] partials (plan.ksplit > 1), folded into t_out by the entry.
+ *   dx: read and written once; the slices of a pixel tile run in sequence into the same accumulators.
+ *   down_part: [nsplit][16 ns][C_in * 9]; rows >= r are neither written nor to be read (lora_amd_reduce_batched with
+ *       rank_pad = 16 ns folds rows < r). */
+int lora_amd_conv3_nhwc_wide_plan(int32_t B, int32_t C_in, int32_t H, int32_t W, int32_t r,
+                                  lora_amd_conv3_nhwc_plan_t *out);
+int lora_amd_conv3_nhwc_wide_pack(const float *down, int32_t r, int32_t C_in, int32_t act_dtype, void *pf, void *pd,
+                                  void *stream);
+int lora_amd_conv3_nhwc_wide_down_fwd(const void *x, const void *pf, float *t_part, float *t_out, int32_t B, int32_t C_in,
+                                      int32_t H, int32_t W, int32_t r, int32_t act_dtype, void *stream);
+int lora_amd_conv3_nhwc_wide_bwd_dx(void *dx, const float *gt, const void *pd, int32_t B, int32_t C_in, int32_t H,
+                                    int32_t W, int32_t r, int32_t act_dtype, void *stream);
+int lora_amd_conv3_nhwc_wide_bwd_down(const void *x, const float *gt, float *down_part, int32_t B, int32_t C_in,
+                                      int32_t H, int32_t W, int32_t r, int32_t act_dtype, void *stream);
 /* Round 6 — launch fusion of the 3x3 site.
  * (1) The fragment packs of EVERY conv site in ONE launch per optimiser step (the factors change once per step, not per
  *     forward): pf / pd as lora_amd_conv3_nhwc_pack writes them plus pu, `up` [C_out, r] as the matrix-core operand of the

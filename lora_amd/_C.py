@@ -377,6 +377,11 @@ FUNCTIONS = (
     ("lora_amd_conv3_nhwc_down_fwd", cint, (vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp)),
     ("lora_amd_conv3_nhwc_bwd_dx", cint, (vp, vp, vp, i32, i32, i32, i32, i32, i32, vp)),
     ("lora_amd_conv3_nhwc_bwd_down", cint, (vp, vp, vp, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_conv3_nhwc_wide_plan", cint, (i32, i32, i32, i32, i32, P(Conv3NhwcPlan))),
+    ("lora_amd_conv3_nhwc_wide_pack", cint, (vp, i32, i32, i32, vp, vp, vp)),
+    ("lora_amd_conv3_nhwc_wide_down_fwd", cint, (vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_conv3_nhwc_wide_bwd_dx", cint, (vp, vp, vp, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_conv3_nhwc_wide_bwd_down", cint, (vp, vp, vp, i32, i32, i32, i32, i32, i32, vp)),
     ("lora_amd_conv3_nhwc_pack_plan", cint, (P(Conv3PackSite), i32, P(i64))),
     ("lora_amd_conv3_nhwc_pack_batched", cint, (vp, i32, i64, i32, vp)),
     ("lora_amd_conv3_nhwc_fwd_fused", cint, (vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32,
@@ -1500,6 +1505,25 @@ def conv3_nhwc_plan(B: int, C_in: int, H: int, W: int, r: int) -> Conv3NhwcPlan:
     return pl
 
 
+_conv3_nhwc_wide_plan_cache = {}
+
+
+def conv3_nhwc_wide_plan(B: int, C_in: int, H: int, W: int, r: int) -> Conv3NhwcPlan:
+    """The plan of the rank 20, 24, .., 64 entries (ns = ceil(r / 16) rank-16 slices per launch): ``native`` = 0 elsewhere."""
+    key = (B, C_in, H, W, r)
+    pl = _conv3_nhwc_wide_plan_cache.get(key)
+    if pl is None:
+        pl = Conv3NhwcPlan()
+        _check(require().lora_amd_conv3_nhwc_wide_plan(B, C_in, H, W, r, C.byref(pl)), "lora_amd_conv3_nhwc_wide_plan")
+        _conv3_nhwc_wide_plan_cache[key] = pl
+    return pl
+
+
+def conv3_nhwc_wide_ok(B: int, C_in: int, H: int, W: int, r: int) -> bool:
+    """Does the wide plan take this site?  (False, not an error, for ranks above MAX_RANK.)"""
+    return 16 < r <= MAX_RANK and bool(conv3_nhwc_wide_plan(B, C_in, H, W, r).native)
+
+
 def _nhwc_dims(x: torch.Tensor):
     """(B, C, H, W) of a logically-NCHW tensor whose memory is [B, H, W, C] contiguous."""
     B, Ci, H, W = x.shape
@@ -1529,6 +1553,30 @@ def conv3_nhwc_down_fwd(x: torch.Tensor, pf: torch.Tensor, r: int, t_part: Optio
     _check(require().lora_amd_conv3_nhwc_down_fwd(x.data_ptr(), pf.data_ptr(), _ptr(t_part) if need else None,
                                                   t.data_ptr(), B, Ci, H, W, r, dtype_code(x.dtype), _stream()),
            "lora_amd_conv3_nhwc_down_fwd")
+    return t
+
+
+def conv3_nhwc_wide_pack(down: torch.Tensor, act_dtype: torch.dtype, plan: Conv3NhwcPlan) -> Tuple[torch.Tensor, torch.Tensor]:
+    """down [r, C_in, 3, 3] f32, r in {20, .., 64} -> (pf, pd): ns consecutive rank-16 packs each, one launch."""
+    r, Ci = down.shape[0], down.shape[1]
+    pf = torch.empty(int(plan.pf_elems), dtype=act_dtype, device=down.device)
+    pd = torch.empty(int(plan.pd_elems), dtype=act_dtype, device=down.device)
+    _check(require().lora_amd_conv3_nhwc_wide_pack(down.data_ptr(), r, Ci, dtype_code(act_dtype), pf.data_ptr(),
+                                                   pd.data_ptr(), _stream()), "lora_amd_conv3_nhwc_wide_pack")
+    return pf, pd
+
+
+def conv3_nhwc_wide_down_fwd(x: torch.Tensor, pf: torch.Tensor, r: int, t_part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """T [B*H*W, r] f32 = conv3x3(x; down) at a wide rank, all slices in one launch (``t_part`` as in
+    :func:`conv3_nhwc_down_fwd`)."""
+    B, Ci, H, W = _nhwc_dims(x)
+    t = torch.empty((B * H * W, r), dtype=torch.float32, device=x.device)
+    need = int(conv3_nhwc_wide_plan(B, Ci, H, W, r).t_part_floats)
+    if need and (t_part is None or t_part.numel() < need):
+        t_part = torch.empty(need, dtype=torch.float32, device=x.device)
+    _check(require().lora_amd_conv3_nhwc_wide_down_fwd(x.data_ptr(), pf.data_ptr(), _ptr(t_part) if need else None,
+                                                       t.data_ptr(), B, Ci, H, W, r, dtype_code(x.dtype), _stream()),
+           "lora_amd_conv3_nhwc_wide_down_fwd")
     return t
 
 
@@ -1607,6 +1655,22 @@ def conv3_nhwc_bwd_down(x: torch.Tensor, gt: torch.Tensor, down_part: torch.Tens
     _check(require().lora_amd_conv3_nhwc_bwd_down(x.data_ptr(), gt.data_ptr(), down_part.data_ptr(), B, Ci, H, W,
                                                   gt.shape[1], dtype_code(x.dtype), _stream()),
            "lora_amd_conv3_nhwc_bwd_down")
+
+
+def conv3_nhwc_wide_bwd_dx_(dx: torch.Tensor, gt: torch.Tensor, pd: torch.Tensor) -> torch.Tensor:
+    """dx (channels_last, in place) += conv_transpose3x3(gt; down), gt [B*H*W, r] at a wide rank: one read-modify-write."""
+    B, Ci, H, W = _nhwc_dims(dx)
+    _check(require().lora_amd_conv3_nhwc_wide_bwd_dx(dx.data_ptr(), gt.data_ptr(), pd.data_ptr(), B, Ci, H, W, gt.shape[1],
+                                                     dtype_code(dx.dtype), _stream()), "lora_amd_conv3_nhwc_wide_bwd_dx")
+    return dx
+
+
+def conv3_nhwc_wide_bwd_down(x: torch.Tensor, gt: torch.Tensor, down_part: torch.Tensor) -> None:
+    """down_part [nsplit][16 ns][C_in * 9] (wide plan) <- the dDown partials of every slice, one launch."""
+    B, Ci, H, W = _nhwc_dims(x)
+    _check(require().lora_amd_conv3_nhwc_wide_bwd_down(x.data_ptr(), gt.data_ptr(), down_part.data_ptr(), B, Ci, H, W,
+                                                       gt.shape[1], dtype_code(x.dtype), _stream()),
+           "lora_amd_conv3_nhwc_wide_bwd_down")
 
 
 def sum_parts(part: torch.Tensor, nparts: int, n: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -25,6 +25,8 @@
 //     is a pure shift) and the transposed Gt are staged in LDS, the X^T fragments are gathered from there with 2-byte
 //     reads; the strips are dealt to `nsplit` workgroups per 64-channel chunk, whose partials are folded by the
 //     trainer's batched reduce (same [parts][rank_pad][C*9] layout as conv.hip's).
+// Ranks 20, 24, .., 64 run as ceil(r / 16) rank-16 slices INSIDE one launch of each contraction (the wide kernels below:
+// X, dX and the staged X strips are still touched once; T and Gt stay dense [B*H*W, r] f32).
 // Algorithmic bytes per site: forward B*H*W*C*e (X once); backward 2*B*H*W*C*e (dX read + write) + B*H*W*C*e (X once);
 // the [B*H*W, r] f32 tensors are 2r/C of that.  All three are HBM/L2-stream bound (9*r*2 flop per 2-byte element is
 // 144 flop/B at r = 16, under the 312 flop/B MFMA balance).
@@ -827,6 +829,457 @@ __global__ __launch_bounds__(256) void nh_sum_parts_kernel(const float *__restri
   reinterpret_cast<nf32x4 *>(out)[i] = a;
 }
 
+// ============================================================================ ranks 20, 24, .., 64: rank-16 slices in one launch
+// The adapter is linear in the rank dimension (T[:, j] needs down[j] only, dDown[j] needs Gt[:, j] only, dX is a sum over
+// ranks), so a wide rank is NS = ceil(r / 16) rank-16 slices of the three contractions above — run INSIDE one launch each,
+// because the activations are the traffic (the [M, r] tensors are 2r/C of it): NS launches would read X, read and write dX
+// and stage the X strips NS times.  T and Gt stay dense [B*H*W, r] f32 (what the wide rank_update / rowdot entries use);
+// slice s covers columns 16 s .. 16 s + 15, the last one holds 4, 8, 12 or 16 live ranks.
+//   * pack: pf = NS consecutive rank-16 forward packs, pd = NS consecutive rank-16 input-gradient packs (KS = 5 each),
+//     slice s bit for bit conv3_pack_kernel's output for down[16 s : 16 s + 16] zero-padded to 16 ranks; no low-part rows.
+//   * T: a wave fetches each X fragment (k-step, column shift, input row) once and feeds all NS slices' MFMAs from it; only
+//     the weight fragments and the accumulators are per slice; the four channel shares meet in LDS slice after slice.
+//   * dX: the Gt fragments of all slices stay in registers (NS * PT * 5); per 64-channel block the slices run in sequence
+//     into the SAME accumulator, so a dX element is read once and written once.
+//   * dDown: the X strip is staged once; gT holds all 16 NS rank rows (58 KB at NS = 4, beside the 64 KB strip: one
+//     workgroup per CU, as before).  Eight waves = 4 channel tiles x 2 slice groups (slices sg, sg + 2): a wave keeps
+//     9 accumulators per owned slice (72 VGPRs at most — 9 x 4 slices would be 144 of the 256 a wave of a 512-thread
+//     workgroup has) and walks EVERY k-step, so nothing meets in LDS at the end; the X^T gather is done by both groups
+//     (LDS reads, hidden under 18 MFMAs per k-step).  The first 8 rank quads of the next strip's Gt are prefetched in
+//     registers across the multiply; quads beyond are loaded at staging time, their latency behind the X writes.
+constexpr int kNhWideKS = 5;  // a rank-16 slice has 144 (tap, rank) slots
+
+template <class E>
+__global__ __launch_bounds__(256) void conv3_wide_pack_kernel(const float *__restrict__ down, int r, int C, int ns,
+                                                              typename E::storage *__restrict__ pf,
+                                                              typename E::storage *__restrict__ pd) {
+  const int KC = C >> 5;
+  const int64_t npf1 = (int64_t)9 * KC * 64, npd1 = (int64_t)(C >> 4) * kNhWideKS * 64;  // pieces of one slice
+  const int64_t npf = npf1 * ns, total = (npf1 + npd1) * ns;
+  for (int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x; id < total; id += (int64_t)gridDim.x * 256) {
+    Chunk8<E> c;
+    if (id < npf) {
+      const int s = (int)(id / npf1);
+      const int64_t q = id - s * npf1;
+      const int lane = (int)(q & 63), f = (int)(q >> 6);
+      const int kc = f % KC, tap = f / KC;
+      const int j = 16 * s + (lane & 15), c0 = kc * 32 + (lane >> 4) * 8;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) c.v[e] = E::from_f(j < r ? down[((int64_t)j * C + c0 + e) * 9 + tap] : 0.f);
+      *reinterpret_cast<Chunk8<E> *>(pf + id * 8) = c;
+    } else {
+      const int64_t id2 = id - npf;
+      const int s = (int)(id2 / npd1);
+      const int64_t q = id2 - s * npd1;
+      const int lane = (int)(q & 63), f = (int)(q >> 6);
+      const int ks = f % kNhWideKS, ct = f / kNhWideKS;
+      const int ch = ct * 16 + (lane & 15), s0 = ks * 32 + (lane >> 4) * 8;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int sl = s0 + e;
+        const int tap = sl >> 4, j = 16 * s + (sl & 15);
+        c.v[e] = E::from_f((sl < 144 && j < r) ? down[((int64_t)j * C + ch) * 9 + tap] : 0.f);
+      }
+      *reinterpret_cast<Chunk8<E> *>(pd + id2 * 8) = c;
+    }
+  }
+}
+
+// T: conv3_down_nhwc_kernel's tile, k loop and masks; acc[s][t] and the weight fragments per slice, the X fragments shared.
+template <class E, int PT, int NS>
+__global__ __launch_bounds__(kNhThreads) void conv3_down_wide_kernel(const typename E::storage *__restrict__ x,
+                                                                     const typename E::storage *__restrict__ pf,
+                                                                     float *__restrict__ t_out, const NhGeom g) {
+  using S = typename E::storage;
+  __shared__ __attribute__((aligned(16))) float red[4 * PT * 64 * 4];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int l15 = lane & 15, lg = lane >> 4;
+  int bid = (int)xcd_remap(blockIdx.x, gridDim.x);
+  const int tc = bid % g.ntc;
+  bid /= g.ntc;
+  const int rgi = bid % g.nrg, b = bid / g.nrg;
+  const int H = g.H, W = g.W, C = g.C, KC = C >> 5;
+  const int y0 = rgi * PT, xx = tc * 16 + l15;
+
+  int rowoff[PT + 2], coloff[3];
+  unsigned rowmask[PT + 2], colmask[3];
+#pragma unroll
+  for (int q = 0; q < PT + 2; ++q) {
+    const int yy = y0 + q - 1;
+    rowoff[q] = ((b * H + nh_clamp(yy, H - 1)) * W) * C;
+    rowmask[q] = (yy >= 0 && yy < H) ? 0xFFFFFFFFu : 0u;
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const int xs = xx + d - 1;
+    coloff[d] = nh_clamp(xs, W - 1) * C + lg * 8;
+    colmask[d] = (xs >= 0 && xs < W) ? 0xFFFFFFFFu : 0u;
+  }
+
+  nf32x4 acc[NS][PT];
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int t = 0; t < PT; ++t) acc[s][t] = (nf32x4){0.f, 0.f, 0.f, 0.f};
+
+  const int ksplit = gridDim.y;
+  const int64_t slice_elems = (int64_t)9 * KC * 512;  // one rank-16 forward pack
+  t_out += (int64_t)blockIdx.y * ((int64_t)g.B * H * W * g.r);  // this share's partial (the output itself at ksplit 1)
+  for (int kc = blockIdx.y * 4 + wave; kc < KC; kc += 4 * ksplit) {
+    const S *xk = x + kc * 32;
+    const S *pk = pf + ((int64_t)kc * 64 + lane) * 8;
+    // all loads of the k-step first, in the order of their use: X (shared by the slices), then slice after slice
+    nu32x4 xr[3][PT + 2];
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+      for (int q = 0; q < PT + 2; ++q) xr[d][q] = *reinterpret_cast<const nu32x4 *>(xk + rowoff[q] + coloff[d]);
+    nu32x4 praw[NS][9];
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap)
+        praw[s][tap] = *reinterpret_cast<const nu32x4 *>(pk + s * slice_elems + (int64_t)(tap * KC) * 512);
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+      for (int q = 0; q < PT + 2; ++q) asm volatile("" : "+v"(xr[d][q]));
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) asm volatile("" : "+v"(praw[s][tap]));
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+#pragma unroll
+      for (int q = 0; q < PT + 2; ++q) {
+        const unsigned m = rowmask[q] & colmask[d];
+        xr[d][q] = xr[d][q] & (nu32x4){m, m, m, m};
+      }
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+      for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int t = 0; t < PT; ++t)
+#pragma unroll
+          for (int dy = 0; dy < 3; ++dy)
+            acc[s][t] = NhMfma<E>::mma(nh_frag_bits<E>(praw[s][dy * 3 + d]), nh_frag_bits<E>(xr[d][t + dy]), acc[s][t]);
+  }
+
+  // the four channel shares meet in LDS, one slice at a time; acc[s][t][e] = T[pixel l15 of row t][rank 16 s + 4 lg + e]
+  const int r = g.r;
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    if (s) __syncthreads();  // the previous slice has been read
+#pragma unroll
+    for (int t = 0; t < PT; ++t) *reinterpret_cast<nf32x4 *>(red + ((wave * PT + t) * 64 + lane) * 4) = acc[s][t];
+    __syncthreads();
+    for (int t = wave; t < PT; t += 4) {
+      nf32x4 v = (nf32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int w = 0; w < 4; ++w) v += *reinterpret_cast<const nf32x4 *>(red + ((w * PT + t) * 64 + lane) * 4);
+      const int yy = y0 + t, j = 16 * s + lg * 4;
+      if (yy < H && xx < W && j < r)  // live ranks only (r % 4 == 0: a quad is live or dead as a whole)
+        *reinterpret_cast<nf32x4 *>(t_out + (((int64_t)b * H + yy) * W + xx) * r + j) = v;
+    }
+  }
+}
+
+// dX: conv3_dx_nhwc_kernel with the Gt fragments of every slice resident and the slices chained into one accumulator.
+template <class E, int PT, int NS>
+__global__ __launch_bounds__(kNhThreads) void conv3_dx_wide_kernel(typename E::storage *__restrict__ dx,
+                                                                   const float *__restrict__ gt,
+                                                                   const typename E::storage *__restrict__ pd,
+                                                                   const NhGeom g) {
+  using S = typename E::storage;
+  using F = typename NhMfma<E>::frag;
+  constexpr int KS = kNhWideKS;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int l15 = lane & 15, lg = lane >> 4;
+  int bid = (int)xcd_remap(blockIdx.x, gridDim.x);
+  const int tc = bid % g.ntc;
+  bid /= g.ntc;
+  const int rgi = bid % g.nrg, b = bid / g.nrg;
+  const int H = g.H, W = g.W, C = g.C, r = g.r;
+  const int y0 = rgi * PT, xx = tc * 16 + l15;
+
+  F bg[NS][PT][KS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    // the slice's PT*KS*2 loads in flight together (clamped addresses), masks afterwards
+    nu32x4 graw[PT][KS][2];
+    unsigned gmask[PT][KS][2];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int sl = ks * 32 + lg * 8 + 4 * h;
+        const int tap0 = sl >> 4, j0 = 16 * s + (sl & 15);
+        const bool live = sl < 144 && j0 < r;
+        const int tap = live ? tap0 : 0, j = live ? j0 : 0;
+        const int dy = tap / 3 - 1, dxx = tap % 3 - 1;
+        const int xs = xx - dxx;
+        const bool xok = live && xs >= 0 && xs < W;
+        const int xc = nh_clamp(xs, W - 1);
+#pragma unroll
+        for (int t = 0; t < PT; ++t) {
+          const int ys = y0 + t - dy;
+          const float *src = gt + (((int64_t)b * H + nh_clamp(ys, H - 1)) * W + xc) * r + j;
+          graw[t][ks][h] = *reinterpret_cast<const nu32x4 *>(src);
+          gmask[t][ks][h] = (xok && ys >= 0 && ys < H) ? 0xFFFFFFFFu : 0u;
+        }
+      }
+#pragma unroll
+    for (int t = 0; t < PT; ++t)
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) asm volatile("" : "+v"(graw[t][ks][h]));
+#pragma unroll
+    for (int t = 0; t < PT; ++t)
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        float v[8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const unsigned m = gmask[t][ks][h];
+          const nu32x4 q = graw[t][ks][h] & (nu32x4){m, m, m, m};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const unsigned qe = q[e];
+            v[h * 4 + e] = __builtin_bit_cast(float, qe);
+          }
+        }
+        bg[s][t][ks] = nh_frag<E>(v);
+      }
+  }
+
+  bool pok[PT];
+  int poff[PT];
+#pragma unroll
+  for (int t = 0; t < PT; ++t) {
+    const int yy = y0 + t;
+    pok[t] = yy < H && xx < W;
+    poff[t] = ((b * H + nh_clamp(yy, H - 1)) * W + nh_clamp(xx, W - 1)) * C + lg * 4;
+  }
+  const int NCB = C >> 6;
+  const int64_t slice_elems = (int64_t)(C >> 4) * KS * 512;  // one rank-16 input-gradient pack
+  // the next block's dX lines are requested before this block is multiplied; the weight fragments of a block (NS * KS
+  // coalesced 1 KB loads, L2 hits after the first tile) are fetched slice by slice ahead of their MFMAs
+  nu32x2 prev[PT];
+  auto fetch_dx = [&](int cb) {
+    const int ct = cb * 4 + wave;
+#pragma unroll
+    for (int t = 0; t < PT; ++t) prev[t] = *reinterpret_cast<const nu32x2 *>(dx + poff[t] + ct * 16);
+  };
+  int cb = blockIdx.y;
+  if (cb < NCB) fetch_dx(cb);
+  for (; cb < NCB; cb += gridDim.y) {
+    const int ct = cb * 4 + wave;
+    F pa[NS][KS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks)
+        pa[s][ks] = *reinterpret_cast<const F *>(pd + s * slice_elems + (((int64_t)ct * KS + ks) * 64 + lane) * 8);
+    nu32x2 pv[PT];
+#pragma unroll
+    for (int t = 0; t < PT; ++t) pv[t] = prev[t];
+    if (cb + (int)gridDim.y < NCB) fetch_dx(cb + gridDim.y);
+#pragma unroll
+    for (int t = 0; t < PT; ++t) {
+      nf32x4 a = (nf32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) a = NhMfma<E>::mma(pa[s][ks], bg[s][t][ks], a);
+      union { nu32x2 v; S s[4]; } o;
+      o.v = pv[t];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o.s[e] = E::from_f(E::to_f(o.s[e]) + a[e]);
+      if (pok[t]) *reinterpret_cast<nu32x2 *>(dx + poff[t] + ct * 16) = o.v;
+    }
+  }
+}
+
+// dDown: conv3_ddown_nhwc_kernel's staging (same constants, same strips); rq = r / 4 live rank quads.
+template <class E, int NS>
+__global__ __launch_bounds__(kDdThreads) void conv3_ddown_wide_kernel(const typename E::storage *__restrict__ x,
+                                                                      const float *__restrict__ gt,
+                                                                      float *__restrict__ part, const NhGeom g, int PR,
+                                                                      int nsplit, int xcd_aware) {
+  using S = typename E::storage;
+  using F = typename NhMfma<E>::frag;
+  constexpr int NI = (NS + 1) / 2;         // slices a wave owns at most: sg, sg + 2
+  constexpr int GPF = 8;                   // rank quads prefetched in registers across the multiply
+  constexpr int NQ = 4 * NS, NLATE = NQ - GPF;
+  __shared__ __attribute__((aligned(16))) unsigned char xs[(kDdMaxPix + kDdTail) * kDdRowB];
+  __shared__ __attribute__((aligned(16))) unsigned short gT[16 * NS * kDdGRow];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, lg = lane >> 4;
+  const int ctw = wave & 3, sg = wave >> 2;
+  const int nch = g.C >> 6;
+  const int logical = xcd_aware ? (int)xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+  const int cc = logical % nch, sid = logical / nch;
+  const int H = g.H, W = g.W, C = g.C, r = g.r, WP = W + 2, rq = r >> 2;
+  const int spi = (H + PR - 1) / PR, nstrips = g.B * spi;
+  const int SPP = PR * WP, KSP = (SPP + 31) >> 5;
+  const int nchunks = (PR + 2) * W * 8;
+
+  // everything that is never written below stays zero: the pixel margins of every staged row, the tail, ranks >= r
+  for (int i = tid; i < (int)(sizeof(xs) / 16); i += kDdThreads) reinterpret_cast<nu32x4 *>(xs)[i] = (nu32x4){0u, 0u, 0u, 0u};
+  for (int i = tid; i < (int)(sizeof(gT) / 16); i += kDdThreads) reinterpret_cast<nu32x4 *>(gT)[i] = (nu32x4){0u, 0u, 0u, 0u};
+
+  int xrel[kDdNld], xlds[kDdNld], xry[kDdNld];
+#pragma unroll
+  for (int u = 0; u < kDdNld; ++u) {
+    const int q = tid + kDdThreads * u;
+    const bool live = q < nchunks;
+    const int f = live ? q >> 3 : 0, c16 = q & 7;
+    const int ryp = f / W, xq = f - ryp * W;
+    xry[u] = live ? ryp - 1 : (1 << 20);
+    xrel[u] = ((ryp - 1) * W + xq) * C + cc * 64 + c16 * 8;
+    xlds[u] = (ryp * WP + xq + 2) * kDdRowB + c16 * 16;
+  }
+  const int gsp = tid;
+  const bool gin = gsp < KSP * 32;
+  const int gry = gsp / WP, gxx = gsp - gry * WP;
+  const bool gst = gsp < SPP && gxx >= 1 && gxx <= W;
+  const int grel = (gry * W + gxx - 1) * r;
+
+  nu32x4 xr[kDdNld];
+  nf32x4 gr[GPF];
+  auto prefetch = [&](int s) {
+    const int b = s / spi, y0 = (s - b * spi) * PR;
+    const int rows_valid = min(PR, H - y0);
+    const S *xb = x + ((int64_t)(b * H + y0) * W) * C;
+    const float *gb = gt + ((int64_t)(b * H + y0) * W) * r;
+#pragma unroll
+    for (int u = 0; u < kDdNld; ++u) {
+      const int y = y0 + xry[u];
+      const bool ok = y >= 0 && y < H;
+      xr[u] = *reinterpret_cast<const nu32x4 *>(xb + (ok ? xrel[u] : cc * 64 + (tid & 7) * 8));
+    }
+    const bool ok = gst && gry < rows_valid;
+#pragma unroll
+    for (int qd = 0; qd < GPF; ++qd)  // r >= 20: quads 0..4 always exist; a dead one re-reads quad 0 (never stored)
+      gr[qd] = *reinterpret_cast<const nf32x4 *>(gb + (ok ? grel : 0) + (qd < rq ? 4 * qd : 0));
+  };
+
+  nf32x4 acc[NI][9];
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+#pragma unroll
+    for (int t = 0; t < 9; ++t) acc[i][t] = (nf32x4){0.f, 0.f, 0.f, 0.f};
+  const unsigned short *xs16 = reinterpret_cast<const unsigned short *>(xs);
+  const int col = ctw * 16 + l15;
+
+  const int per = nstrips / nsplit, extra = nstrips - per * nsplit;
+  const int s_begin = sid * per + min(sid, extra), s_end = s_begin + per + (sid < extra ? 1 : 0);
+  if (s_begin < s_end) prefetch(s_begin);
+  for (int s = s_begin; s < s_end; ++s) {
+    const int b = s / spi, y0 = (s - b * spi) * PR;
+    const int rows_valid = min(PR, H - y0);
+    const bool gok = gst && gry < rows_valid;
+    __syncthreads();  // the previous strip has been multiplied (first trip: the zero fill is complete)
+    nf32x4 glate[NLATE > 0 ? NLATE : 1];
+    if constexpr (NLATE > 0) {
+      const float *gb = gt + ((int64_t)(b * H + y0) * W) * r + (gok ? grel : 0);
+#pragma unroll
+      for (int qd = 0; qd < NLATE; ++qd) glate[qd] = *reinterpret_cast<const nf32x4 *>(gb + (GPF + qd < rq ? 4 * (GPF + qd) : 0));
+    }
+#pragma unroll
+    for (int u = 0; u < kDdNld; ++u) {
+      const int y = y0 + xry[u];
+      const unsigned m = (y >= 0 && y < H) ? 0xFFFFFFFFu : 0u;
+      const nu32x4 v = xr[u] & (nu32x4){m, m, m, m};
+      if (tid + kDdThreads * u < nchunks) {
+        *reinterpret_cast<nu32x2 *>(xs + xlds[u]) = (nu32x2){v[0], v[1]};
+        *reinterpret_cast<nu32x2 *>(xs + xlds[u] + 8) = (nu32x2){v[2], v[3]};
+      }
+    }
+    if (gin) {
+#pragma unroll
+      for (int qd = 0; qd < NQ; ++qd) {
+        if (qd < rq) {
+          nf32x4 q4;
+          if constexpr (NLATE > 0) q4 = qd < GPF ? gr[qd < GPF ? qd : 0] : glate[qd >= GPF ? qd - GPF : 0];
+          else q4 = gr[qd < GPF ? qd : 0];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            union { S s; unsigned short u; } cv;
+            cv.s = E::from_f(gok ? q4[e] : 0.f);
+            gT[(qd * 4 + e) * kDdGRow + gsp] = cv.u;
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (s + 1 < s_end) prefetch(s + 1);  // in flight while this strip is multiplied
+
+    unsigned v[3][10];
+    nu32x4 gaw[NI];
+    auto fetch = [&](int ks) {
+      const int sp0 = ks * 32 + lg * 8;
+#pragma unroll
+      for (int i = 0; i < NI; ++i)
+        if (sg + 2 * i < NS) gaw[i] = *reinterpret_cast<const nu32x4 *>(gT + ((sg + 2 * i) * 16 + l15) * kDdGRow + sp0);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const unsigned short *src = xs16 + (sp0 + WP * d) * (kDdRowB / 2) + col;
+#pragma unroll
+        for (int i = 0; i < 10; ++i) v[d][i] = src[i * (kDdRowB / 2)];
+      }
+    };
+    fetch(0);
+    for (int ks = 0; ks < KSP; ++ks) {
+      unsigned P[3][5];
+#pragma unroll
+      for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) P[d][k] = v[d][2 * k] | (v[d][2 * k + 1] << 16);
+      F ga[NI];
+#pragma unroll
+      for (int i = 0; i < NI; ++i) ga[i] = nh_frag_bits<E>(gaw[i]);
+      if (ks + 1 < KSP) fetch(ks + 1);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const nu32x4 fm = (nu32x4){P[d][0], P[d][1], P[d][2], P[d][3]};
+        const nu32x4 fp = (nu32x4){P[d][1], P[d][2], P[d][3], P[d][4]};
+        const nu32x4 f0 = (nu32x4){(P[d][0] >> 16) | (P[d][1] << 16), (P[d][1] >> 16) | (P[d][2] << 16),
+                                   (P[d][2] >> 16) | (P[d][3] << 16), (P[d][3] >> 16) | (P[d][4] << 16)};
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+          if (sg + 2 * i < NS) {  // wave-uniform
+            acc[i][d * 3 + 0] = NhMfma<E>::mma(ga[i], nh_frag_bits<E>(fm), acc[i][d * 3 + 0]);
+            acc[i][d * 3 + 1] = NhMfma<E>::mma(ga[i], nh_frag_bits<E>(f0), acc[i][d * 3 + 1]);
+            acc[i][d * 3 + 2] = NhMfma<E>::mma(ga[i], nh_frag_bits<E>(fp), acc[i][d * 3 + 2]);
+          }
+        }
+      }
+    }
+  }
+
+  // acc[i][tap][e] = dDown[rank 16 (sg + 2 i) + 4 lg + e][channel cc*64 + ctw*16 + l15][tap]; rows >= r are not written
+  const int64_t row_len = (int64_t)C * 9;
+  const int c = cc * 64 + ctw * 16 + l15;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    if (sg + 2 * i < NS) {
+#pragma unroll
+      for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int j = (sg + 2 * i) * 16 + lg * 4 + e;
+          if (j < r) part[((int64_t)sid * (16 * NS) + j) * row_len + (int64_t)c * 9 + t] = acc[i][t][e];
+        }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------- host
 static inline int nh_rank_pad(int r) { return r <= 4 ? 4 : r <= 8 ? 8 : 16; }
 static inline int64_t nh_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -1090,6 +1543,158 @@ extern "C" int lora_amd_conv3_nhwc_bwd_down(const void *x, const float *gt, floa
     });
   });
   return check_launch("lora_amd_conv3_nhwc_bwd_down");
+}
+
+// ---------------------------------------------------------------------------- ranks 20, 24, .., 64 (rank-16 slices)
+static inline bool nh_wide_native(int B, int C, int H, int W, int r) {
+  return B >= 1 && H >= 1 && W >= 1 && C >= 64 && C % 64 == 0 && r >= 20 && r <= 64 && r % 4 == 0 &&
+         (int64_t)B * H * W * C < ((int64_t)1 << 31) && nh_pick_pr(H, W) >= 1;
+}
+// The cuts of the wide kernels.  Tiles and strips are nh_cuts' (the X / dX streams and the staging budget do not depend on
+// the rank); what the rank changes:
+//   * dX keeps NS * pt_dx * 5 Gt fragments in registers: 2 tile rows up to 2 slices (80 fragment registers), 1 above;
+//   * dDown's partial slab has 16 NS rows per split: the byte cap counts them, the stream-share cap the real r.  The byte
+//     cap is 16 MiB here, not nh_cuts' 4: at 9 r 2 = 360 .. 1152 flop per activation byte the wide kernel is bound by the
+//     matrix cores, not by the stream (balance 312 flop/B), so its time falls with the number of workgroups until every
+//     CU has one, while 16 MiB of partials written and read back is ~8 us of HBM time at worst (they sit in the 256 MB
+//     last-level cache).  At the 96 x 96 x 320 site of rank 64 the cap is then 22 splits instead of 5; the equal-share rule
+//     makes that ceil(48 / ceil(48 / 22)) = 16 splits = 80 workgroups (the rank-16 plan's split) instead of 5 = 25.
+static NhCuts nh_wide_cuts(int B, int C, int H, int W, int r) {
+  NhCuts q = nh_cuts(B, C, H, W, 16);
+  const int ns = (r + 15) / 16;
+  const int64_t ntc = (W + 15) / 16, M = (int64_t)B * H * W;
+  if (ns > 2) q.pt_dx = 1;
+  const int64_t tiles_dx = (int64_t)B * nh_cdiv(H, q.pt_dx) * ntc;
+  const int cs = tiles_dx >= 192 ? 1 : (int)nh_cdiv(256, tiles_dx);
+  q.csplit = (int)std::max<int64_t>(1, std::min<int64_t>(cs, C / 64));
+  const int64_t nstrips = (int64_t)B * nh_cdiv(H, std::max(q.pr, 1));
+  const int64_t cap = std::max<int64_t>((int64_t)(0.30 * (double)M / (18.0 * r)),
+                                        std::max<int64_t>(1, ((int64_t)16 << 20) / ((int64_t)16 * ns * C * 36)));
+  const int64_t bound = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(256 / (C / 64), cap), nstrips));
+  q.nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(nh_cdiv(nstrips, nh_cdiv(nstrips, bound)), nstrips));
+  return q;
+}
+
+extern "C" int lora_amd_conv3_nhwc_wide_plan(int32_t B, int32_t C_in, int32_t H, int32_t W, int32_t r,
+                                             lora_amd_conv3_nhwc_plan_t *out) {
+  LORA_AMD_CHECK(out != nullptr, LORA_AMD_EINVAL, "conv3_nhwc_wide_plan: null output");
+  LORA_AMD_CHECK(B >= 0 && C_in > 0 && H > 0 && W > 0, LORA_AMD_EINVAL, "conv3_nhwc_wide_plan: bad shape");
+  LORA_AMD_CHECK(r >= 1 && r <= LORA_AMD_MAX_RANK, LORA_AMD_ERANK, "conv3_nhwc_wide_plan: rank %d outside [1,%d]", r,
+                 LORA_AMD_MAX_RANK);
+  memset(out, 0, sizeof(*out));
+  if (!nh_wide_native(B, C_in, H, W, r)) return LORA_AMD_OK;
+  const NhCuts q = nh_wide_cuts(B, C_in, H, W, r);
+  const int ns = (r + 15) / 16;
+  const int64_t M = (int64_t)B * H * W;
+  out->native = 1;
+  out->pt = q.pt;
+  out->ksplit = q.ksplit;
+  out->csplit = q.csplit;
+  out->ks = kNhWideKS;
+  out->pr = q.pr;
+  out->nsplit = q.nsplit;
+  out->rank_pad = 16 * ns;
+  out->pf_elems = (int64_t)ns * 9 * C_in * 16;
+  out->pd_elems = (int64_t)ns * C_in * kNhWideKS * 32;
+  out->t_part_floats = q.ksplit > 1 ? q.ksplit * M * r : 0;
+  out->fwd_tiles = (int32_t)((int64_t)B * nh_cdiv(H, q.pt) * ((W + 15) / 16));
+  out->down_part_floats = (int64_t)q.nsplit * out->rank_pad * C_in * 9;
+  return LORA_AMD_OK;
+}
+
+#define NH_WIDE_COMMON(name)                                                                                     \
+  LORA_AMD_CHECK(act_dtype == LORA_AMD_BF16 || act_dtype == LORA_AMD_F16, LORA_AMD_EINVAL,                       \
+                 name ": activations must be bf16 or f16");                                                       \
+  LORA_AMD_CHECK(r >= 1 && r <= LORA_AMD_MAX_RANK, LORA_AMD_ERANK, name ": rank %d outside [1,%d]", r,            \
+                 LORA_AMD_MAX_RANK);                                                                              \
+  LORA_AMD_CHECK(nh_wide_native(B, C_in, H, W, r), LORA_AMD_EINVAL,                                               \
+                 name ": needs C_in %% 64 == 0, rank in {20, 24, .., 64}, W <= 128, B*H*W*C_in < 2^31 "          \
+                      "(lora_amd_conv3_nhwc_wide_plan)")
+
+extern "C" int lora_amd_conv3_nhwc_wide_pack(const float *down, int32_t r, int32_t C_in, int32_t act_dtype, void *pf,
+                                             void *pd, void *stream) {
+  const int B = 1, H = 1, W = 1;
+  NH_WIDE_COMMON("conv3_nhwc_wide_pack");
+  LORA_AMD_CHECK(down && pf && pd, LORA_AMD_EINVAL, "conv3_nhwc_wide_pack: null pointer");
+  LORA_AMD_CHECK((((uintptr_t)pf | (uintptr_t)pd) & 15u) == 0, LORA_AMD_EINVAL, "conv3_nhwc_wide_pack: 16-byte aligned packs");
+  const int ns = (r + 15) / 16;
+  const int64_t pieces = ((int64_t)9 * (C_in / 32) * 64 + (int64_t)(C_in / 16) * kNhWideKS * 64) * ns;
+  const unsigned grid = (unsigned)std::min<int64_t>((pieces + 255) / 256, 2048);
+  by_dtype<bf16_t, f16_t>(act_dtype, [&](auto e) {
+    using S = typename decltype(e)::storage;
+    hipLaunchKernelGGL(conv3_wide_pack_kernel<decltype(e)>, dim3(grid), dim3(256), 0, (hipStream_t)stream, down, r, C_in, ns,
+                       (S *)pf, (S *)pd);
+  });
+  return check_launch("lora_amd_conv3_nhwc_wide_pack");
+}
+
+extern "C" int lora_amd_conv3_nhwc_wide_down_fwd(const void *x, const void *pf, float *t_part, float *t_out, int32_t B,
+                                                 int32_t C_in, int32_t H, int32_t W, int32_t r, int32_t act_dtype,
+                                                 void *stream) {
+  NH_WIDE_COMMON("conv3_nhwc_wide_down_fwd");
+  LORA_AMD_CHECK(x && pf && t_out, LORA_AMD_EINVAL, "conv3_nhwc_wide_down_fwd: null pointer");
+  LORA_AMD_CHECK((((uintptr_t)x | (uintptr_t)pf | (uintptr_t)t_out | (uintptr_t)t_part) & 15u) == 0, LORA_AMD_EINVAL,
+                 "conv3_nhwc_wide_down_fwd: 16-byte aligned buffers");
+  const NhCuts q = nh_wide_cuts(B, C_in, H, W, r);
+  LORA_AMD_CHECK(q.ksplit == 1 || t_part != nullptr, LORA_AMD_EWORKSPACE,
+                 "conv3_nhwc_wide_down_fwd: this geometry splits the channels over %d workgroups and needs t_part "
+                 "(plan.t_part_floats)", q.ksplit);
+  const NhGeom g = nh_geom(B, C_in, H, W, r, q.pt);
+  const dim3 grid((unsigned)((int64_t)B * g.nrg * g.ntc), (unsigned)q.ksplit);
+  float *dst = q.ksplit > 1 ? t_part : t_out;
+  by_dtype<bf16_t, f16_t>(act_dtype, [&](auto e) {
+    by_int<4, 2, 1>(q.pt, [&](auto ptv) {
+      by_int<2, 3, 4>((r + 15) / 16, [&](auto nsv) {
+        using S = typename decltype(e)::storage;
+        hipLaunchKernelGGL((conv3_down_wide_kernel<decltype(e), decltype(ptv)::value, decltype(nsv)::value>), grid,
+                           dim3(kNhThreads), 0, (hipStream_t)stream, (const S *)x, (const S *)pf, dst, g);
+      });
+    });
+  });
+  const int rc = check_launch("lora_amd_conv3_nhwc_wide_down_fwd");
+  if (rc != LORA_AMD_OK || q.ksplit == 1) return rc;
+  return nh_launch_sum(t_part, q.ksplit, (int64_t)B * H * W * r, t_out, stream);
+}
+
+extern "C" int lora_amd_conv3_nhwc_wide_bwd_dx(void *dx, const float *gt, const void *pd, int32_t B, int32_t C_in,
+                                               int32_t H, int32_t W, int32_t r, int32_t act_dtype, void *stream) {
+  NH_WIDE_COMMON("conv3_nhwc_wide_bwd_dx");
+  LORA_AMD_CHECK(dx && gt && pd, LORA_AMD_EINVAL, "conv3_nhwc_wide_bwd_dx: null pointer");
+  LORA_AMD_CHECK((((uintptr_t)dx | (uintptr_t)pd | (uintptr_t)gt) & 15u) == 0, LORA_AMD_EINVAL,
+                 "conv3_nhwc_wide_bwd_dx: 16-byte aligned buffers");
+  const NhCuts q = nh_wide_cuts(B, C_in, H, W, r);
+  const NhGeom g = nh_geom(B, C_in, H, W, r, q.pt_dx);
+  const dim3 grid((unsigned)((int64_t)B * g.nrg * g.ntc), (unsigned)q.csplit);
+  by_dtype<bf16_t, f16_t>(act_dtype, [&](auto e) {
+    using S = typename decltype(e)::storage;
+    auto launch = [&](auto ptv, auto nsv) {
+      hipLaunchKernelGGL((conv3_dx_wide_kernel<decltype(e), decltype(ptv)::value, decltype(nsv)::value>), grid,
+                         dim3(kNhThreads), 0, (hipStream_t)stream, (S *)dx, gt, (const S *)pd, g);
+    };
+    // two tile rows exist for two slices only (nh_wide_cuts): 3 x 2 x 5 Gt fragments and up leave no room for the weights
+    if (q.pt_dx == 2) launch(int_c<2>, int_c<2>);
+    else by_int<2, 3, 4>((r + 15) / 16, [&](auto nsv) { launch(int_c<1>, nsv); });
+  });
+  return check_launch("lora_amd_conv3_nhwc_wide_bwd_dx");
+}
+
+extern "C" int lora_amd_conv3_nhwc_wide_bwd_down(const void *x, const float *gt, float *down_part, int32_t B,
+                                                 int32_t C_in, int32_t H, int32_t W, int32_t r, int32_t act_dtype,
+                                                 void *stream) {
+  NH_WIDE_COMMON("conv3_nhwc_wide_bwd_down");
+  LORA_AMD_CHECK(x && gt && down_part, LORA_AMD_EINVAL, "conv3_nhwc_wide_bwd_down: null pointer");
+  LORA_AMD_CHECK((((uintptr_t)x | (uintptr_t)gt) & 15u) == 0, LORA_AMD_EINVAL,
+                 "conv3_nhwc_wide_bwd_down: 16-byte aligned buffers");
+  const NhCuts q = nh_wide_cuts(B, C_in, H, W, r);
+  const NhGeom g = nh_geom(B, C_in, H, W, r, 1);
+  const dim3 grid((unsigned)((C_in / 64) * q.nsplit));
+  by_dtype<bf16_t, f16_t>(act_dtype, [&](auto e) {
+    by_int<2, 3, 4>((r + 15) / 16, [&](auto nsv) {
+      hipLaunchKernelGGL((conv3_ddown_wide_kernel<decltype(e), decltype(nsv)::value>), grid, dim3(kDdThreads), 0,
+                         (hipStream_t)stream, (const typename decltype(e)::storage *)x, gt, down_part, g, q.pr, q.nsplit, 1);
+    });
+  });
+  return check_launch("lora_amd_conv3_nhwc_wide_bwd_down");
 }
 
 extern "C" int lora_amd_sum_parts(const float *part, int32_t nparts, int64_t stride, float *out, int64_t n,

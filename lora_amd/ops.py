@@ -209,17 +209,17 @@ def _begin(sink, site):
 
 def _finish(sink, site, w, down, up):
     """Last step: the slabs ``w`` stay pending on the sink (the trainer's batched reduce folds them into the flat gradient
-    buffer) and (None, None) is returned, or they are folded here into fresh (d_down, d_up) in the factors' dtypes."""
+    buffer) and (None, None) is returned, or they are folded here into fresh (d_down, d_up) in the factors' dtypes.
+    ``up`` None: the slabs hold dDown partials only (dUp came whole from a primitive) and d_up is None."""
     key, _, rows = site
     if sink is not None:
         sink.pending = key
         return None, None
-    d_up = torch.empty(up.shape, dtype=torch.float32, device=up.device)
+    d_up = torch.empty(up.shape, dtype=torch.float32, device=up.device) if up is not None else None
     d_down = torch.empty(down.shape, dtype=torch.float32, device=down.device)
-    table, n, total = _C.make_reduce_table(rows(w, d_up, d_down, 0.0), up.device)
+    table, n, total = _C.make_reduce_table(rows(w, d_up, d_down, 0.0), down.device)
     _C.reduce_batched(table, n, total)
-    d_up = d_up.to(up.dtype)
-    return d_down.to(down.dtype), d_up
+    return d_down.to(down.dtype), d_up.to(up.dtype) if up is not None else None
 
 
 def _rows2d(t: torch.Tensor, cols: int) -> torch.Tensor:
@@ -632,13 +632,18 @@ WIDE_FACTORS = True
 # only what dX needs, nothing where the input takes no gradient; False = the primitives in the site's backward
 # (tests/test_gpu_factors_wide_masked.py runs both)
 WIDE_DROPOUT = True
+# channels-last 3x3 Conv2d adapters of rank 20, 24, .., 64 on the matrix-core kernels of csrc/conv_nhwc.hip, ceil(r / 16)
+# rank-16 slices inside one launch per contraction (LoraConv3NhwcWideFunction); False = the frozen conv +
+# ``lora_conv_branch`` (library convolutions in NCHW for the down-projection and its gradients)
+# (tests/test_gpu_conv_nhwc_wide.py runs both)
+CONV3_WIDE = True
 
 
 def apply_ab_overrides(spec: str, namespace: dict) -> dict:
     """``LORA_AMD_AB="NAME=0,OTHER=1"``: the ONE measurement switch for same-box A/B runs — flips the module constants
     listed in ``allowed`` (and only those) without a code edit; every A/B log under profiles/ names the spec it ran with
     (a constant retired since then is an unknown name here)."""
-    allowed = ("ATTN_SHORT_BWD", "CONCAT_GROUPS", "CONV3_FUSED", "GN_RESIDENT", "MASTER_MERGE", "MERGED_WIDE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
+    allowed = ("ATTN_SHORT_BWD", "CONCAT_GROUPS", "CONV3_FUSED", "CONV3_WIDE", "GN_RESIDENT", "MASTER_MERGE", "MERGED_WIDE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
                "WS_DROPOUT_WIDE_BWD", "WIDE_FACTORS", "WIDE_DROPOUT")
     done = {}
     for item in filter(None, (s.strip() for s in spec.split(","))):
@@ -1789,6 +1794,88 @@ class LoraConv3NhwcFunction(torch.autograd.Function):
         return dx, dw, db, d_down, d_up, None, None, None, None
 
 
+class LoraConv3NhwcWideFunction(torch.autograd.Function):
+    """:class:`LoraConv3NhwcFunction`'s site at rank 20, 24, .., 64: the wide entries of csrc/conv_nhwc.hip run the
+    ceil(r / 16) rank-16 slices of T, dX and dDown inside one launch each; T and Gt are dense [B*H*W, r] f32, which is what
+    the rank <= 64 forms of ``rank_update`` / ``rowdot`` / ``colreduce`` take on the pixel rows.  No fused forward and no
+    per-step pack table at these ranks (one pack launch per forward); dUp comes whole from ``colreduce``, the dDown
+    partials stay pending on the sink for the trainer's batched reduce (or are folded here without one)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, down, up, sel, scale, dropout_p, sink):
+        _C.require()
+        B, Ci, H, W = x.shape
+        Co, r = weight.shape[0], down.shape[0]
+        M = B * H * W
+        y = F.conv2d(x, weight, bias, 1, 1)  # frozen dense conv (MIOpen, MFMA)
+        if not y.is_contiguous(memory_format=torch.channels_last):
+            y = y.contiguous(memory_format=torch.channels_last)
+        plan = _C.conv3_nhwc_wide_plan(B, Ci, H, W, r)
+        down_c = down.float().contiguous()  # f32 masters: no-ops in training
+        up2 = up.reshape(Co, r).float().contiguous()
+        sel_c = sel.to(torch.float32).contiguous() if sel is not None else None
+        seed = off = 0
+        if dropout_p > 0.0:
+            seed, off = next_dropout_stream(x.device)
+        pf, pd = _C.conv3_nhwc_wide_pack(down_c, x.dtype, plan)
+        t = _C.conv3_nhwc_wide_down_fwd(x, pf, r)
+        if sel_c is not None:  # rare (set_lora_diag): T' = T S^T on the [M, r] rows
+            t = (t @ sel_c.t()).contiguous()
+        _C.rank_update_(y.permute(0, 2, 3, 1).view(M, Co), t, up2, _C.FACTOR_KR, scale, dropout_p, seed, off)
+        _log("fwd", "conv3_nhwc_wide", M, Ci * 9, Co, r)
+        ctx.save_for_backward(x, weight, down, up, t, sel_c, pd)
+        ctx.scale, ctx.p, ctx.seed, ctx.off, ctx.sink = float(scale), float(dropout_p), seed, off, sink
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, weight, down, up, t, sel, pd = ctx.saved_tensors
+        B, Ci, H, W = x.shape
+        Co, r = weight.shape[0], down.shape[0]
+        M = B * H * W
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        if not g.is_contiguous(memory_format=torch.channels_last):
+            g = g.contiguous(memory_format=torch.channels_last)
+        g2 = g.permute(0, 2, 3, 1).view(M, Co)
+        cplan = _C.conv3_nhwc_wide_plan(B, Ci, H, W, r)
+        sink = ctx.sink
+        fold = lambda w, ug, dg, beta: [(w[0], dg, cplan.nsplit, cplan.rank_pad, Ci * 9, r, _C.FACTOR_RK, 1.0, beta)]  # noqa: E731
+        site = (("conv3w", B, Ci, Co, H, W, r), lambda: _slabs((cplan.down_part_floats,), g.device, least=4), fold)
+        bufs = _begin(sink, site)
+        down_part = bufs[0]
+        up2 = up.reshape(Co, r).float().contiguous()
+        s, p, seed, off = ctx.scale, ctx.p, ctx.seed, ctx.off
+        gt = rowdot_any(g2, up2, _C.FACTOR_KR, s, None, False, p, seed, off)
+        # dUp whole from the primitive: straight into the sink's gradient (beta 1), or a fresh tensor
+        to_sink = sink is not None
+        d_up = colreduce_any(g2, t, _C.FACTOR_KR, s, out=sink.up_grad.view(Co, r) if to_sink else None,
+                             beta=1.0 if to_sink else 0.0, p=p, seed=seed, off=off)
+        if sel is not None:
+            gt = (gt @ sel).contiguous()
+        dx = None
+        if need_x:  # frozen dense conv's input gradient (MIOpen), then the low-rank term is added in place
+            dx = torch.ops.aten.convolution_backward(g, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
+                                                     [True, False, False])[0]
+            if not dx.is_contiguous(memory_format=torch.channels_last):
+                dx = dx.contiguous(memory_format=torch.channels_last)
+            _C.conv3_nhwc_wide_bwd_dx_(dx, gt, pd)
+        _C.conv3_nhwc_wide_bwd_down(x, gt, down_part)
+        # the dDown partials stay pending on the sink (the trainer's batched reduce folds them from its resident table:
+        # nothing is built or copied here, so the backward can sit in a captured graph), or are folded now
+        d_down, _ = _finish(sink, site, bufs, down, None)
+        _log("bwd", "conv3_nhwc_wide", M, Ci * 9, Co, r)
+        d_up = None if to_sink else d_up.view(up.shape).to(up.dtype)
+        dw = db = None
+        if need_w:
+            dw = torch.ops.aten.convolution_backward(g, x, weight, None, [1, 1], [1, 1], [1, 1], False, [0, 0], 1,
+                                                     [False, True, False])[1]
+        if ctx.has_bias and need_b:
+            db = g.sum((0, 2, 3))
+        return dx, dw, db, d_down, d_up, None, None, None, None
+
+
 def _channels_last_only(x: torch.Tensor) -> bool:
     """Memory is [B, H, W, C] and NOT also plain NCHW-contiguous (C == 1 or H == W == 1 are both)."""
     return x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
@@ -1796,7 +1883,8 @@ def _channels_last_only(x: torch.Tensor) -> bool:
 
 def conv_nhwc_ok(x: torch.Tensor, weight: torch.Tensor, r: int, stride, padding, dilation, groups) -> bool:
     """Channels-last activations at a site the NHWC forms cover: 1x1 (= the Linear adapter on the pixel rows) or
-    3x3 / padding 1 with a geometry ``_C.conv3_nhwc_plan`` accepts; stride 1, 16-bit activations."""
+    3x3 / padding 1 with a geometry ``_C.conv3_nhwc_plan`` accepts (rank <= 16) or, with ``CONV3_WIDE``,
+    ``_C.conv3_nhwc_wide_plan`` (rank 20, 24, .., 64); stride 1, 16-bit activations."""
     if not _channels_last_only(x) or groups != 1 or tuple(stride) != (1, 1) or tuple(dilation) != (1, 1):
         return False
     kh, kw = weight.shape[2], weight.shape[3]
@@ -1807,6 +1895,8 @@ def conv_nhwc_ok(x: torch.Tensor, weight: torch.Tensor, r: int, stride, padding,
     if kh == 1:
         return True
     B, Ci, H, W = x.shape
+    if r > 16:
+        return CONV3_WIDE and _C.conv3_nhwc_wide_ok(B, Ci, H, W, r)
     return bool(_C.conv3_nhwc_plan(B, Ci, H, W, r).native)
 
 
@@ -1831,7 +1921,8 @@ def lora_conv(x, weight, bias, down_w, up_w, sel, stride, padding, dilation, gro
             y = LoraLinearFunction.apply(x.permute(0, 2, 3, 1), weight.reshape(Co, Ci), bias, down_w.reshape(r, Ci),
                                          up_w.reshape(Co, r), sel, float(scale), float(dropout_p), sink)
             return y.permute(0, 3, 1, 2)
-        return LoraConv3NhwcFunction.apply(x, weight, bias, down_w, up_w, sel, float(scale), float(dropout_p), sink)
+        fn = LoraConv3NhwcWideFunction if r > 16 else LoraConv3NhwcFunction
+        return fn.apply(x, weight, bias, down_w, up_w, sel, float(scale), float(dropout_p), sink)
     if down_w.dtype == up_w.dtype and conv_native_ok(x, weight, r, stride, padding, dilation, groups):
         return LoraConvFunction.apply(x, weight, bias, down_w, up_w, sel, int(weight.shape[2]), float(scale),
                                       float(dropout_p), sink)
@@ -1947,7 +2038,8 @@ def _ps_conv3_pack(cache: dict, down: torch.Tensor, dt: torch.dtype, plan) -> to
     hit = cache.get("pf")
     if hit is not None and hit[0] is down and hit[1] == key:
         return hit[2]
-    pf = _C.conv3_nhwc_pack(down.detach().float().contiguous(), dt, plan)[0]
+    pack = _C.conv3_nhwc_wide_pack if down.shape[0] > 16 else _C.conv3_nhwc_pack
+    pf = pack(down.detach().float().contiguous(), dt, plan)[0]
     cache["pf"] = (down, key, pf)
     return pf
 
@@ -1974,8 +2066,12 @@ def lora_conv_per_sample(x, weight, bias, down_w, up_w, sel, stride, padding, di
         y = F.conv2d(x, weight, bias, 1, 1)  # frozen dense conv (MIOpen)
         if not y.is_contiguous(memory_format=torch.channels_last):
             y = y.contiguous(memory_format=torch.channels_last)
-        plan = _C.conv3_nhwc_plan(B, Ci, H, W, r)
-        t = _C.conv3_nhwc_down_fwd(x, _ps_conv3_pack(cache, down_w, x.dtype, plan), r)
+        if r > 16:  # rank 20, 24, .., 64: the slices in one launch (conv_nhwc_ok has asked the wide plan)
+            plan = _C.conv3_nhwc_wide_plan(B, Ci, H, W, r)
+            t = _C.conv3_nhwc_wide_down_fwd(x, _ps_conv3_pack(cache, down_w, x.dtype, plan), r)
+        else:
+            plan = _C.conv3_nhwc_plan(B, Ci, H, W, r)
+            t = _C.conv3_nhwc_down_fwd(x, _ps_conv3_pack(cache, down_w, x.dtype, plan), r)
         if sel is not None:
             t = (t @ sel.float().t()).contiguous()
         rank_update_rowscale_any_(y.permute(0, 2, 3, 1).view(B * H * W, Co), t, up2, _C.FACTOR_KR, scale, rows, H * W,

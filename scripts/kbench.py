@@ -808,6 +808,55 @@ def bench_nhwc(args):
         print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in res.items()}), flush=True)
 
 
+def bench_conv3_wide(args):
+    """The wide (rank 20..64) channels-last 3x3 kernels at the 3x3 sites of SD1.5 at 768^2, batch 1: one launch for all
+    ns = ceil(r / 16) slices against the yardstick, ns launches of the rank-16 kernel on the slices (contiguous Gt slices,
+    the slices' own packs), and against the byte roof of csrc/conv_nhwc.hip's algorithmic bytes (GB/s = those bytes over the
+    kernel time: X once; dX read + write; X once).  ``dup_us`` / ``gt_us``: the two primitive passes over G of the wide
+    route's backward (colreduce for dUp, rowdot for Gt) at C_out = C_in, for the share of dUp in what is left.  The batch-2
+    row is the first geometry whose forward tiles are four rows deep."""
+    for r in (32, 64):
+        for (B, C, Hh) in ((1, 320, 96), (1, 640, 48), (1, 1280, 24), (1, 2560, 24), (1, 1280, 12), (2, 320, 96)):  # last: pt 4
+            ns = -(-r // 16)
+            xl = torch.randn(B, C, Hh, Hh, device=DEV).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+            dxl = torch.randn(B, C, Hh, Hh, device=DEV).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+            down = torch.randn(r, C, 3, 3, device=DEV) * 0.1
+            M = B * Hh * Hh
+            gt = torch.randn(M, r, device=DEV)
+            plan, p16 = _C.conv3_nhwc_wide_plan(B, C, Hh, Hh, r), _C.conv3_nhwc_plan(B, C, Hh, Hh, 16)
+            pf, pd = _C.conv3_nhwc_wide_pack(down, torch.bfloat16, plan)
+            part = torch.empty(int(plan.down_part_floats), device=DEV)
+            d16 = [down[16 * s:16 * s + 16].contiguous() for s in range(ns)]
+            g16 = [gt[:, 16 * s:16 * s + 16].contiguous() for s in range(ns)]
+            packs = [_C.conv3_nhwc_pack(d, torch.bfloat16, p16) for d in d16]
+            part16 = torch.empty(int(p16.down_part_floats), device=DEV)
+            ex = B * C * Hh * Hh * 2
+            res = dict(B=B, C=C, HW=Hh, r=r, pt=plan.pt, ksplit=plan.ksplit, csplit=plan.csplit, nsplit=plan.nsplit,
+                       nsplit16=p16.nsplit)
+
+            def pair(name, wide, narrow, nbytes):
+                med, _ = timeit(wide, args.iters)
+                med16, _ = timeit(narrow, args.iters)
+                res[name + "_us"], res[name + "_x16_us"] = med * 1e6, med16 * 1e6
+                res[name + "_GBs"] = nbytes / med / 1e9
+
+            pair("pack", lambda: _C.conv3_nhwc_wide_pack(down, torch.bfloat16, plan),
+                 lambda: [_C.conv3_nhwc_pack(d, torch.bfloat16, p16) for d in d16], 36 * r * C + 2 * (plan.pf_elems + plan.pd_elems))
+            pair("T", lambda: _C.conv3_nhwc_wide_down_fwd(xl, pf, r),
+                 lambda: [_C.conv3_nhwc_down_fwd(xl, q[0], 16) for q in packs], ex)
+            pair("dx", lambda: _C.conv3_nhwc_wide_bwd_dx_(dxl, gt, pd),
+                 lambda: [_C.conv3_nhwc_bwd_dx_(dxl, g, q[1]) for g, q in zip(g16, packs)], 2 * ex)
+            pair("ddown", lambda: _C.conv3_nhwc_wide_bwd_down(xl, gt, part),
+                 lambda: [_C.conv3_nhwc_bwd_down(xl, g, part16) for g in g16], ex)
+            g2 = dxl.permute(0, 2, 3, 1).view(M, C)
+            up = torch.randn(C, r, device=DEV) * 0.05
+            med, _ = timeit(lambda: _C.colreduce(g2, gt, _C.FACTOR_KR, 1.0), args.iters)
+            res["dup_us"] = med * 1e6
+            med, _ = timeit(lambda: _C.rowdot(g2, up, _C.FACTOR_KR, 1.0), args.iters)
+            res["gt_us"] = med * 1e6
+            print(json.dumps({k: (round(v, 2) if isinstance(v, float) else v) for k, v in res.items()}), flush=True)
+
+
 def bench_hostops(args):
     """GroupNorm(+SiLU), LayerNorm and the GEGLU gate of the frozen UNet: HIP passes vs the ATen sequences (bf16)."""
     import torch.nn as nn
@@ -1014,6 +1063,8 @@ if __name__ == "__main__":
         bench_conv(a)
     if "nhwc" in a.what:
         bench_nhwc(a)
+    if "c3wide" in a.what.split(","):
+        bench_conv3_wide(a)
     if "hostops" in a.what:
         bench_hostops(a)
     if "self" in a.what:
