@@ -160,11 +160,20 @@ int lora_amd_merge_step_set_tuning(int32_t tile, int32_t dither);
  * enable = 0 routes all of them back to the VALU kernels (parity tests compare the two), 1 = default, < 0 only reads.
  * Returns the previous value. */
 int lora_amd_rank16_mfma(int32_t enable);
+/* The same for lora_amd_colreduce alone (ranks 9..64, colreduce16_mfma_kernel): 0 keeps it on the VALU two-stage kernel
+ * whatever lora_amd_rank16_mfma says, 1 = default (the matrix-core form where lora_amd_rank16_mfma is on too), < 0 only
+ * reads.  Returns the previous value. */
+int lora_amd_colreduce_mfma(int32_t enable);
 /* Pure host arithmetic: 1 exactly when lora_amd_rowdot[_masked] (op 0; cols = K, rows = x, ld = ldx) or lora_amd_rank_update
  * (op 1; cols = N, rows = y, ld = ldy) would run its matrix-core form on these arguments under the current hook setting —
- * the predicate the launchers themselves call.  rows is inspected for alignment only; has_selector: sel != NULL. */
+ * the predicate the launchers themselves call.  rows is inspected for alignment only; has_selector: sel != NULL.  Any other
+ * op: 0. */
 int lora_amd_rank16_mfma_takes(int32_t op, const void *rows, int64_t ld, int64_t M, int32_t cols, int32_t r,
                                int32_t act_dtype, int32_t factor_dtype, int32_t has_selector);
+/* The same for lora_amd_colreduce (the launchers' op 2: cols = K, T is f32): 1 exactly when it would run its matrix-core form
+ * on these arguments under the current settings of lora_amd_rank16_mfma AND lora_amd_colreduce_mfma.  x is inspected for
+ * alignment only.  An entry of its own, so that lora_amd_rank16_mfma_takes answers for ops 0 and 1 what it always did. */
+int lora_amd_colreduce_mfma_takes(const void *x, int64_t ldx, int64_t M, int32_t K, int32_t r, int32_t x_dtype);
 
 /* Tuning knobs of the planner/launcher (<= 0 keeps the current value):
  * target elements per tile and resident workgroups per CU (the LDS-slab kernel's grid cap).  blocks_per_cu >= 100
@@ -226,7 +235,12 @@ int lora_amd_rowdot_masked(const void *x, int64_t ldx, const void *factor,
 
 /* D (f32) = beta * D + scale * sum_m T[m, j] * mask * X[m, k]; D is [r,K] or
  * [K,r] per out_layout.  Two-stage reduction through `workspace` (bytes given
- * by lora_amd_colreduce_workspace).  dropout args as above (p = 0: no mask). */
+ * by lora_amd_colreduce_workspace).  dropout args as above (p = 0: no mask).
+ * 1 <= r <= LORA_AMD_MAX_RANK.  bf16 rows, 9 <= r <= 64, K % 32 == 0, 16-byte aligned rows (x, ldx % 8), D and workspace
+ * 16-byte aligned: the matrix-core form (ceil(r / 16) rank-16 slices in one launch over X; row blocks of 128 rows up to
+ * rank 32, 256 above; the first writes D, the others leave partials inside the same workspace bytes that a second launch
+ * adds in block order — no atomics, the same bits on every call); anything else, and the batched and ragged forms, the VALU
+ * kernels.  lora_amd_colreduce_mfma_takes tells which. */
 size_t lora_amd_colreduce_workspace(int64_t M, int32_t K, int32_t r);
 int lora_amd_colreduce(const void *x, int64_t ldx, const float *t, float *d_out,
                        int64_t M, int32_t K, int32_t r, int32_t x_dtype,

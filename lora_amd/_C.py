@@ -292,7 +292,9 @@ FUNCTIONS = (
     ("lora_amd_merge_step", cint, (vp, i32, i64, i32, i32, f32, i32, vp)),
     ("lora_amd_merge_step_set_tuning", cint, (i32, i32)),
     ("lora_amd_rank16_mfma", cint, (i32,)),
+    ("lora_amd_colreduce_mfma", cint, (i32,)),
     ("lora_amd_rank16_mfma_takes", cint, (i32, vp, i64, i64, i32, i32, i32, i32, i32)),
+    ("lora_amd_colreduce_mfma_takes", cint, (vp, i64, i64, i32, i32, i32)),
     ("lora_amd_merge_set_tuning", cint, (i64, i64)),
     ("lora_amd_rowdot", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32, vp)),
     ("lora_amd_rank_update", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, f32, u64, u64, vp, vp)),
@@ -632,12 +634,21 @@ def rank16_mfma(enable: int = -1) -> int:
     return int(require().lora_amd_rank16_mfma(int(enable)))
 
 
+def colreduce_mfma(enable: int = -1) -> int:
+    """Matrix-core form of ``colreduce`` at ranks 9..64 on / off (ANDed with ``rank16_mfma``); returns the previous setting."""
+    return int(require().lora_amd_colreduce_mfma(int(enable)))
+
+
 def rank16_mfma_takes(op: int, tensor: torch.Tensor, r: int, factor_dtype: torch.dtype = torch.float32,
                       has_selector: bool = False) -> int:
-    """1 when ``rowdot`` (op 0) / ``rank_update_`` (op 1) of the 2-D ``tensor`` (X / Y) at rank ``r`` would run its
-    matrix-core form under the current hook setting: the launchers' own predicate (host arithmetic, any device)."""
+    """1 when ``rowdot`` (op 0) / ``rank_update_`` (op 1) / ``colreduce`` (op 2) of the 2-D ``tensor`` (X / Y / X) at rank
+    ``r`` would run its matrix-core form under the current hook settings: the launchers' own predicate (host arithmetic, any
+    device).  Op 2 asks ``lora_amd_colreduce_mfma_takes`` (T is f32 and there is no selector: the last two arguments do not
+    apply); the C entry of ops 0 and 1 answers 0 for any other op."""
     t = _as2d(tensor)
     M, cols = t.shape
+    if int(op) == 2:
+        return int(require().lora_amd_colreduce_mfma_takes(t.data_ptr(), t.stride(0), M, cols, int(r), dtype_code(t.dtype)))
     return int(require().lora_amd_rank16_mfma_takes(int(op), t.data_ptr(), t.stride(0), M, cols, int(r), dtype_code(t.dtype),
                                                     dtype_code(factor_dtype), int(bool(has_selector))))
 

@@ -788,6 +788,17 @@ extern "C" int lora_amd_colreduce(const void *x, int64_t ldx, const float *t, fl
   LORA_AMD_CHECK(dropout_p >= 0.f && dropout_p < 1.f, LORA_AMD_EINVAL, "colreduce: dropout p=%f", dropout_p);
   hipStream_t st = (hipStream_t)stream;
   const bool masked = dropout_p > 0.f;
+  // ranks 9..64 on bf16 rows, K % 32 == 0: the matrix-core form (csrc/rank16_mfma.hip; r16_takes op 2 decides).  Its first
+  // row block writes D, the others leave [r][K] partials that are added in block order here
+  int64_t fold = 0;
+  if (r16_colreduce(x, ldx, t, d_out, M, K, r, x_dtype, out_layout, scale, beta, dropout_p, seed, offset, offset_dev, workspace,
+                    workspace_bytes, st, &fold)) {
+    if (fold > 0)
+      hipLaunchKernelGGL(colreduce_stage2_kernel, dim3((unsigned)(((int64_t)r * K + 63) / 64), 1), dim3(kThreads), 0, st,
+                         reinterpret_cast<const float *>(workspace), d_out, fold, K, r, r, 0, out_layout, 1.0f, 1.0f,
+                         BatchStride{0, 0, 0, 0, 0});
+    return check_launch("lora_amd_colreduce(mfma)");
+  }
   return by_dtype(x_dtype, [&](auto e) {
     using E = decltype(e);
     return masked ? launch_colreduce<E, true>(x, ldx, t, d_out, M, K, r, out_layout, scale, beta, dropout_p, seed,

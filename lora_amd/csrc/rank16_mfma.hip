@@ -1,7 +1,8 @@
 // Rank-tile-16 forms of the adapter's streaming kernels on the matrix cores (ranks 9..16, bf16 activations, f32 factors), and the
-// wide forms of the row product and the rank update (ranks 17..64: ceil(r / 16) rank-16 slices in one launch, template NS).
+// wide forms of the row product, the rank update and the column reduction (ranks 17..64: ceil(r / 16) rank-16 slices in one
+// launch, template NS).
 //
-// replaces: csrc/linear.hip's rowdot / rank_update kernels and csrc/linear_fused.hip's linear_bwd_g_kernel<E, 16> for
+// replaces: csrc/linear.hip's rowdot / rank_update / colreduce kernels and csrc/linear_fused.hip's linear_bwd_g_kernel<E, 16> for
 //           lora_diffusion/lora.py:53-58 (Linear) and lora.py:130-135 (Conv2d, channels-last rows) at rank 16 — BASELINE
 //           configs[3].  At rank 16 the VALU forms spend 16-32 FMAs per element and sit at 0.1-0.2 of the byte roof
 //           (profiles/r04_cfg3_by_grid_before_rank16.txt: 25-110 us per launch whatever the size); the contractions are dense enough for
@@ -24,6 +25,10 @@
 //                   then the two pieces go through the wave's own 32 x 32 LDS tile and come back column-major through
 //                   ds_read_b64_tr_b16 for phase 2 (A = G^T, B = T); the LDS queue of a wave is in order, so write -> transpose
 //                   read -> next write needs no wait beyond the data dependence.
+//   colreduce16:    D[r, K] | [K, r] = beta D + s T^T (mask . X)   ranks 9..64 (NS slices): phase 2 of bwd_g16 on its own, a wave =
+//                   one 32-column group over the rows of a 128 / 256-row block; the T fragments of four 32-row steps are the one
+//                   thing the four waves share (LDS image, two barriers per 128 rows).  Row block 0 writes D, the others
+//                   partials that linear.hip's colreduce_stage2_kernel adds in block order.
 //
 // The same row product also serves cli_svd (lora_diffusion/cli_svd.py:24-92 as restated in lora_amd/cli_svd.py): the residuals
 // dW = W_tuned - W_base are f32, which has no full-rate matrix-core path on gfx950, so they are held as TWO bf16 planes
@@ -40,6 +45,7 @@
 namespace lora_amd {
 
 int g_r16_mfma = 1;
+int g_cr_mfma = 1;
 
 constexpr int kR16Threads = 256;
 constexpr int kR16Pitch = 96;  // bytes per row of a wave's 32 x 32 16-bit tile: ds_write_b128 and the transpose reads conflict-free
@@ -478,6 +484,137 @@ __global__ __launch_bounds__(kR16Threads) void bwd_g16_mfma_kernel(
   }
 }
 
+// ============================================================================ colreduce16
+// D[r, K] | [K, r] = beta D + s T^T (mask . X) for ranks 9..64: phase 2 of bwd_g16 on its own, NS rank-16 slices in one
+// launch.  grid = row blocks of `rows_per_block` (a multiple of 128) x column tiles of 128 columns; a wave owns ONE 32-column
+// group over all the rows of the block, so its accumulators are 2 x NS quads (32 VGPRs at four slices: no second group per
+// wave).  Per 32-row step: two 16-byte pieces per lane, the dropout AND-mask (one Philox draw per chunk, whatever NS), the
+// wave's own LDS tile, two transpose reads, and 2 x NS x (hi, lo) MFMAs against the step's T fragments.  The T fragments
+// (scale and 1 / (1 - p) folded in) are what the four waves share: an LDS image of kR16CrSteps steps, one step built per
+// wave, between two workgroup barriers per 128 rows.
+// Row block 0 writes D itself (beta applied); row block b > 0 writes partial[b - 1][r][K], which the caller folds into D
+// with colreduce_stage2_kernel (beta = 1, block order fixed): (nb - 1) r K floats, inside lora_amd_colreduce_workspace's
+// ceil(M / 64) 16 K for the heights of r16_cr_rows.
+constexpr int kR16CrSteps = 4;  // 32-row steps of the T image
+template <class E, bool DROP, int NS>
+__global__ __launch_bounds__(kR16Threads) void colreduce16_mfma_kernel(
+    const typename E::storage *__restrict__ x, int64_t ldx, const float *__restrict__ t, float *__restrict__ d,
+    float *__restrict__ partial, int64_t M, int K, int r, int nct, int rows_per_block, int out_layout, float scale, float beta,
+    float p, uint64_t seed, uint64_t offset, const uint64_t *offset_dev) {
+  __shared__ __attribute__((aligned(16))) unsigned char s_stage[4 * 32 * kR16Pitch];   // a 32 x 32 tile per wave (12 KB)
+  __shared__ __attribute__((aligned(16))) mu32x4 s_tf[kR16CrSteps * NS * 2 * 64];       // [step][slice][hi, lo][lane]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, jj = lane & 15, q = lane >> 4;
+  const int64_t rb = blockIdx.x / nct;
+  const int ct = (int)(blockIdx.x - rb * nct);
+  const int64_t m0 = rb * rows_per_block;
+  const int nrows = (int)min((int64_t)rows_per_block, M - m0);
+  const int nsteps = (nrows + 31) >> 5;
+  const int col0 = (ct * 4 + wave) * 32;
+  const bool cok = col0 < K;  // wave-uniform; K % 32 == 0 (host check): the group is inside or outside as a whole
+  float sc = scale;
+  uint32_t thr = 0;
+  uint64_t off = 0;
+  if constexpr (DROP) {
+    sc = scale * (1.0f / (1.0f - p));
+    thr = (uint32_t)(p * 65536.0f + 0.5f);
+    off = dropout_offset(offset, offset_dev);
+  }
+  auto piece = [&](int rs, int rg) -> mu32x4 {
+    const int row = rs * 32 + rg * 16 + jj;
+    const bool ok = cok && row < nrows;
+    return *gl(reinterpret_cast<const mu32x4 *>(x + (m0 + (ok ? row : 0)) * ldx + (ok ? col0 : 0) + 8 * q));
+  };
+  auto finish = [&](mu32x4 v, int rs, int rg) -> mu32x4 {  // out-of-range pieces -> 0, the forward's mask
+    const int row = rs * 32 + rg * 16 + jj;
+    if (!(cok && row < nrows)) return r16_zero();
+    if constexpr (DROP) v &= dropout_and8(seed, off, (uint64_t)((m0 + row) * (int64_t)(K >> 3) + ((col0 >> 3) + q)), thr);
+    return v;
+  };
+  mf32x4 acc[2][NS];
+#pragma unroll
+  for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+    for (int sl = 0; sl < NS; ++sl) acc[nt][sl] = mf32x4{0.f, 0.f, 0.f, 0.f};
+  unsigned char *stage = s_stage + wave * 32 * kR16Pitch;
+  mu32x4 cur0 = piece(0, 0), cur1 = piece(0, 1);
+#pragma unroll 1
+  for (int ch = 0; ch < nsteps; ch += kR16CrSteps) {  // block-uniform trip count: the barriers are met by all four waves
+    __syncthreads();
+    // T fragments of step ch + wave (B operand): k slot 8 q + e <-> row 4 q + e (e < 4) / 16 + 4 q + e - 4 of the step —
+    // the order the two transpose reads deliver X's rows in; lane jj of slice sl <-> rank 16 sl + jj, zero at or past r
+    if (ch + wave < nsteps) {
+#pragma unroll
+      for (int sl = 0; sl < NS; ++sl) {
+        const int j = 16 * sl + jj;
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int row = (ch + wave) * 32 + (e < 4 ? 4 * q + e : 16 + 4 * q + (e - 4));
+          v[e] = (row < nrows && j < r) ? sc * gl(t)[(m0 + row) * r + j] : 0.f;
+        }
+        mu32x4 hi, lo;
+        split_hi_lo<E>(v, hi, lo);
+        s_tf[((wave * NS + sl) * 2 + 0) * 64 + lane] = hi;
+        s_tf[((wave * NS + sl) * 2 + 1) * 64 + lane] = lo;
+      }
+    }
+    __syncthreads();
+    if (!cok) continue;
+    const int kend = min(kR16CrSteps, nsteps - ch);
+#pragma unroll 1
+    for (int k = 0; k < kend; ++k) {
+      const int rs = ch + k;
+      mu32x4 nx0 = r16_zero(), nx1 = r16_zero();
+      if (rs + 1 < nsteps) { nx0 = piece(rs + 1, 0); nx1 = piece(rs + 1, 1); }
+      cur0 = finish(cur0, rs, 0);
+      cur1 = finish(cur1, rs, 1);
+      *reinterpret_cast<mu32x4 *>(stage + jj * kR16Pitch + q * 16) = cur0;
+      *reinterpret_cast<mu32x4 *>(stage + (16 + jj) * kR16Pitch + q * 16) = cur1;
+      asm volatile("" ::: "memory");  // the LDS queue of a wave is in order: only the compiler must keep the order
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        const unsigned char *pp = stage + (4 * q + (jj >> 2)) * kR16Pitch + (16 * nt + 4 * (jj & 3)) * 2;
+        union { ms16x4 h[2]; mu32x4 u; } a;
+        a.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ms16x4 __attribute__((address_space(3))) *)(pp));
+        a.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ms16x4 __attribute__((address_space(3))) *)(pp + 16 * kR16Pitch));
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) {
+          const mu32x4 th = s_tf[((k * NS + sl) * 2 + 0) * 64 + lane], tl = s_tf[((k * NS + sl) * 2 + 1) * 64 + lane];
+          acc[nt][sl] = FmMfma<E>::mma(fm_frag<E>(a.u), fm_frag<E>(th), acc[nt][sl]);
+          acc[nt][sl] = FmMfma<E>::mma(fm_frag<E>(a.u), fm_frag<E>(tl), acc[nt][sl]);
+        }
+      }
+      asm volatile("" ::: "memory");
+      cur0 = nx0;
+      cur1 = nx1;
+    }
+  }
+  if (!cok) return;
+  // lane (rank j = 16 sl + jj, columns n .. n + 3, n = col0 + 16 nt + 4 q)
+#pragma unroll
+  for (int sl = 0; sl < NS; ++sl) {
+    const int j = 16 * sl + jj;
+    if (j >= r) continue;
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      const int n = col0 + 16 * nt + 4 * q;
+      const mf32x4 a = acc[nt][sl];
+      if (rb > 0) {
+        *gl(reinterpret_cast<mf32x4 *>(partial + ((rb - 1) * r + j) * (int64_t)K + n)) = a;
+      } else if (out_layout == LORA_AMD_FACTOR_RK) {
+        mf32x4 *o = reinterpret_cast<mf32x4 *>(d + (int64_t)j * K + n);
+        *gl(o) = beta == 0.f ? a : beta * *gl(o) + a;
+      } else {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          float *o = d + (int64_t)(n + reg) * r + j;
+          *gl(o) = (beta == 0.f ? 0.f : beta * *gl(o)) + a[reg];
+        }
+      }
+    }
+  }
+}
+
 // ============================================================================ rowdot16 over hi + lo planes (cli_svd)
 // out[b][M, r] = X[b][M, C] F[b][C, r] for stacks of f32 matrices held as TWO 16-bit planes (X = hi + lo to ~16 mantissa
 // bits; same bytes as f32): the skinny products of the randomized subspace iteration (cli_svd.py:24-92 restated in
@@ -762,13 +899,23 @@ static int r16_ru_rows(int64_t M, int64_t ny, int ns) {
   return rows;
 }
 
-// THE predicate of the two launchers below (and of lora_amd_rank16_mfma_takes, which only exposes it): does this call run its
-// matrix-core form?  op 0 = rowdot (cols = C), 1 = rank_update (cols = N); `rows` is inspected for alignment only.
-// No shape class of ranks 17..64 is held back: profiles/r16_wide_kbench.txt has the wide forms ahead of the VALU kernels on
-// every shape of the leg.
+// rows of a colreduce16 row block per slice count: whole T images (128 rows), and tall enough that the partials of the
+// blocks after the first, (ceil(M / rows) - 1) r K floats, fit the ceil(M / 64) 16 K of lora_amd_colreduce_workspace:
+// (ceil(M / (64 ns)) - 1) 16 ns < M / 64 * 16
+static int r16_cr_rows(int ns) { return ns <= 2 ? 128 : 256; }
+
+// THE predicate of the three launchers below (and of lora_amd_rank16_mfma_takes / lora_amd_colreduce_mfma_takes, which only
+// expose it): does this call run its matrix-core form?  op 0 = rowdot (cols = C), 1 = rank_update (cols = N), 2 = colreduce
+// (cols = K; its own switch on top of the hook); `rows` is inspected for alignment only.
+// No shape class of ranks 17..64 is held back: profiles/r16_wide_kbench.txt and profiles/colreduce_mfma_kbench.txt have the
+// matrix-core forms ahead of the VALU kernels on every shape of the leg.
 bool r16_takes(int op, const void *rows, int64_t ld, int64_t M, int cols, int r, int act_dtype, int fdt, bool has_sel) {
   if (!r16_common_ok(act_dtype, fdt, r, 64) || has_sel || ld % 8 || ((uintptr_t)rows & 15u) || M <= 0 || cols <= 0) return false;
   if (op == 0) return cols % 32 == 0 && (M + 15) / 16 <= 0x7fffffff;
+  if (op == 2) {
+    const int rpb = r16_cr_rows((r + 15) / 16);
+    return g_cr_mfma && cols % 32 == 0 && ((M + rpb - 1) / rpb) * (((int64_t)cols + 127) / 128) <= 0x7fffffff;
+  }
   if (op != 1 || cols % 8) return false;
   const int64_t ny = ((int64_t)cols + 127) / 128;  // a wave = one 32-column group
   const int rpb = r16_ru_rows(M, ny, (r + 15) / 16);
@@ -819,6 +966,27 @@ bool r16_rank_update(void *y, int64_t ldy, const float *t, int nparts, int64_t p
   return true;
 }
 
+// *fold_blocks: the row-block partials [fold_blocks][r][K] left at the head of `workspace` for the caller to add to D in
+// block order (colreduce_stage2_kernel, beta = 1, scale = 1); 0 when the one row block wrote D whole.
+bool r16_colreduce(const void *x, int64_t ldx, const float *t, float *d, int64_t M, int K, int r, int act_dtype, int out_layout,
+                   float scale, float beta, float p, uint64_t seed, uint64_t offset, const uint64_t *offset_dev, void *workspace,
+                   size_t workspace_bytes, hipStream_t st, int64_t *fold_blocks) {
+  if (!r16_takes(2, x, ldx, M, K, r, act_dtype, LORA_AMD_F32, false) || ((uintptr_t)d & 15u)) return false;
+  const int ns = (r + 15) / 16, rows = r16_cr_rows(ns);
+  const int64_t nb = (M + rows - 1) / rows;
+  if (nb > 1 && (((uintptr_t)workspace & 15u) || !workspace || workspace_bytes < (size_t)(nb - 1) * r * K * sizeof(float))) return false;
+  const int nct = (K + 127) / 128;
+  by_bool(p > 0.f, [&](auto dr) {
+    by_int<1, 2, 3, 4>(ns, [&](auto n) {
+      hipLaunchKernelGGL((colreduce16_mfma_kernel<bf16_t, decltype(dr)::value, decltype(n)::value>), dim3((unsigned)(nb * nct)),
+                         dim3(kR16Threads), 0, st, reinterpret_cast<const bf16_t::storage *>(x), ldx, t, d,
+                         reinterpret_cast<float *>(workspace), M, K, r, nct, rows, out_layout, scale, beta, p, seed, offset, offset_dev);
+    });
+  });
+  *fold_blocks = nb - 1;
+  return true;
+}
+
 bool r16_bwd_g(const void *g, int64_t ldg, const float *t, const void *up, int fdt, float *gt_part, float *up_part, int64_t M,
                int N, int r, int log_ct8, int nct, int rows_per_block, int64_t nrb, int act_dtype, float scale, float p,
                uint64_t seed, uint64_t offset, const uint64_t *offset_dev, hipStream_t st, float *gt_out, unsigned *counters) {
@@ -846,10 +1014,26 @@ extern "C" int lora_amd_rank16_mfma(int32_t enable) {
   return prev;
 }
 
+// The column reduction's own switch, ANDed with the hook above: 0 keeps lora_amd_colreduce on the VALU two-stage kernel while
+// the row product and the rank update stay on the matrix cores (LORA_AMD_AB=COLREDUCE_MFMA=0/1 is an A/B of that one kernel).
+extern "C" int lora_amd_colreduce_mfma(int32_t enable) {
+  const int prev = lora_amd::g_cr_mfma;
+  if (enable >= 0) lora_amd::g_cr_mfma = enable ? 1 : 0;
+  return prev;
+}
+
+// Pure host: 1 when lora_amd_colreduce would run the matrix-core form on these arguments under the current settings of both
+// switches: r16_takes op 2, the launcher's own predicate.  An entry of its own: lora_amd_rank16_mfma_takes keeps answering 0
+// for every op but 0 and 1, as it always has.
+extern "C" int lora_amd_colreduce_mfma_takes(const void *x, int64_t ldx, int64_t M, int32_t K, int32_t r, int32_t x_dtype) {
+  return lora_amd::r16_takes(2, x, ldx, M, K, r, x_dtype, LORA_AMD_F32, false) ? 1 : 0;
+}
+
 // Pure host: 1 when lora_amd_rowdot[_masked] (op 0) / lora_amd_rank_update (op 1) would run the matrix-core form on these
-// arguments under the current hook setting — the launchers' own predicate, not a restatement of it.
+// arguments under the current hook setting — the launchers' own predicate, not a restatement of it.  Any other op: 0.
 extern "C" int lora_amd_rank16_mfma_takes(int32_t op, const void *rows, int64_t ld, int64_t M, int32_t cols, int32_t r,
                                           int32_t act_dtype, int32_t factor_dtype, int32_t has_selector) {
+  if (op != 0 && op != 1) return 0;
   return lora_amd::r16_takes(op, rows, ld, M, cols, r, act_dtype, factor_dtype, has_selector != 0) ? 1 : 0;
 }
 

@@ -637,13 +637,19 @@ WIDE_DROPOUT = True
 # ``lora_conv_branch`` (library convolutions in NCHW for the down-projection and its gradients)
 # (tests/test_gpu_conv_nhwc_wide.py runs both)
 CONV3_WIDE = True
+# ``colreduce`` of ranks 9..64 on bf16 rows (dUp / dDown of every site whose factor gradients are not deferred, dUp of the
+# channels-last 3x3 sites above) on the matrix cores (csrc/rank16_mfma.hip colreduce16_mfma_kernel: one pass over the rows
+# for all ceil(r / 16) slices; the library routes by shape, this constant is pushed into it at import); False = the VALU
+# two-stage kernel, ceil(r / 16) passes
+# (tests/test_gpu_colreduce_mfma.py runs both)
+COLREDUCE_MFMA = True
 
 
 def apply_ab_overrides(spec: str, namespace: dict) -> dict:
     """``LORA_AMD_AB="NAME=0,OTHER=1"``: the ONE measurement switch for same-box A/B runs — flips the module constants
     listed in ``allowed`` (and only those) without a code edit; every A/B log under profiles/ names the spec it ran with
     (a constant retired since then is an unknown name here)."""
-    allowed = ("ATTN_SHORT_BWD", "CONCAT_GROUPS", "CONV3_FUSED", "CONV3_WIDE", "GN_RESIDENT", "MASTER_MERGE", "MERGED_WIDE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
+    allowed = ("ATTN_SHORT_BWD", "COLREDUCE_MFMA", "CONCAT_GROUPS", "CONV3_FUSED", "CONV3_WIDE", "GN_RESIDENT", "MASTER_MERGE", "MERGED_WIDE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
                "WS_DROPOUT_WIDE_BWD", "WIDE_FACTORS", "WIDE_DROPOUT")
     done = {}
     for item in filter(None, (s.strip() for s in spec.split(","))):
@@ -657,6 +663,8 @@ def apply_ab_overrides(spec: str, namespace: dict) -> dict:
 apply_ab_overrides(os.environ.get("LORA_AMD_AB", ""), globals())
 if not GN_RESIDENT and _C.load() is not None:  # a library-side route: the setting has to be there before the first launch
     _C.groupnorm_nhwc_resident(0)
+if not COLREDUCE_MFMA and _C.load() is not None:
+    _C.colreduce_mfma(0)
 
 # Rounding of the in-step merge of 16-bit weights (csrc/merge_step.hip): "dither" (default) = nearest with a fixed
 # per-element dither, so that a delta below half an ulp of the frozen weight survives in the row sums; "once" = nearest even

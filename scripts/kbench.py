@@ -145,7 +145,7 @@ def bench_mstep(args):
 def bench_r16(args):
     """Rank-16 kernels of BASELINE configs[3] (768^2, batch 1, dropout 0.1): matrix-core form (csrc/rank16_mfma.hip) against
     the VALU kernel it replaces, same call, hook on / off.  Bytes: the activation once (rowdot, bwd_g) or twice (rank_update).
-    Ranks 32 and 64 (the wide forms of rowdot / rank_update: 2 and 4 rank-16 slices in one launch) on the same shapes; the
+    Ranks 32 and 64 (the wide forms of rowdot / rank_update / colreduce: 2 and 4 rank-16 slices in one launch) on the same shapes; the
     rank-16 lines are what they are read against (``mfma_over_r16`` / ``valu_over_r16``: the time ratios per kernel, next to
     the factor re-read ratio of the row product, 2 : 1 at rank 16, 8 : 1 at rank 64).  bwd_g exists at rank 16 only."""
     p, dt = 0.1, torch.bfloat16
@@ -158,7 +158,11 @@ def bench_r16(args):
             fkr, frk = torch.randn(C, r, device=DEV) * 0.2, torch.randn(r, C, device=DEV) * 0.2
             calls = {"rowdot_masked": (lambda: _C.rowdot(a, fkr, _C.FACTOR_KR, 0.7, None, False, p, 5, 9), M * C * 2),
                      "rowdot": (lambda: _C.rowdot(a, frk, _C.FACTOR_RK, 1.0), M * C * 2),
-                     "rank_update": (lambda: _C.rank_update_(a, t, fkr, _C.FACTOR_KR, 1e-3, p, 5, 9), 2 * M * C * 2)}
+                     "rank_update": (lambda: _C.rank_update_(a, t, fkr, _C.FACTOR_KR, 1e-3, p, 5, 9), 2 * M * C * 2),
+                     # dUp (masked G, [N, r]) and dDown (X, [r, K]) of a site's backward: colreduce16_mfma_kernel + its fold
+                     # launch against the VALU two-stage kernel's ceil(r / 16) passes (the global hook gates both)
+                     "colreduce_masked": (lambda: _C.colreduce(a, t, _C.FACTOR_KR, 0.7, dropout_p=p, seed=5, offset=9), M * C * 2),
+                     "colreduce": (lambda: _C.colreduce(a, t, _C.FACTOR_RK, 1.0), M * C * 2)}
             if r == 16:
                 plan = _C.linear_plan(M, 320, C, r)
                 gt_part = torch.empty(plan.gt_part_floats, device=DEV)

@@ -119,6 +119,118 @@ def rowdot16_step(X, F):
     return t
 
 
+PITCH = 96  # kR16Pitch: bytes per row of a wave's 32 x 32 16-bit staging tile
+
+
+def bf16_round(v):
+    """nearest-even bfloat16 of float32 values, as float64 (E::from_f of csrc/common.hpp for finite values)"""
+    u = np.asarray(v, np.float32).view(np.uint32).astype(np.uint64)
+    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    return u.astype(np.uint32).view(np.float32).astype(np.float64)
+
+
+def split_hi_lo(v):
+    """mfma16.hpp's split_hi_lo: v ~ hi + lo, both bf16"""
+    v32 = np.asarray(v, np.float32)
+    hi = bf16_round(v32)
+    lo = bf16_round((v32.astype(np.float64) - hi).astype(np.float32))
+    return hi, lo
+
+
+def colreduce16_step(X, T, sl, split=False):
+    """colreduce16_mfma_kernel, one wave, one 32-row step of one 32-column group, slice `sl`: the two 16-byte pieces per lane
+    go to the wave's staging tile (byte addresses at PITCH), come back column-major through the two transpose reads, and
+    meet the step's T fragment (lane jj <-> rank 16 sl + jj, zero at or past r; k slot 8 q + e <-> row 4 q + e / 16 + 4 q +
+    e - 4).  X: [rows <= 32, 32] (bf16-exact values), T: [rows, r].  Returns acc[nt][lane][reg]; split: T enters as
+    hi + lo into the same accumulator."""
+    rows, r = T.shape
+    stage = np.zeros(32 * PITCH // 2)   # the tile in 16-bit elements
+    for l in range(64):
+        jj, q = l & 15, l >> 4
+        for rg in range(2):
+            row = rg * 16 + jj
+            piece = X[row, 8 * q:8 * q + 8] if row < rows else np.zeros(8)
+            a0 = (row * PITCH + q * 16) // 2
+            stage[a0:a0 + 8] = piece
+    tile = np.zeros((32, 32))
+    for row in range(32):
+        tile[row] = stage[row * PITCH // 2:row * PITCH // 2 + 32]
+    tf = np.zeros((64, 8))
+    for l in range(64):
+        jj, q = l & 15, l >> 4
+        j = 16 * sl + jj
+        for e in range(8):
+            row = 4 * q + e if e < 4 else 16 + 4 * q + (e - 4)
+            tf[l][e] = T[row, j] if (row < rows and j < r) else 0.0
+    frags = split_hi_lo(tf) if split else (tf,)
+    acc = []
+    for nt in range(2):
+        a = np.zeros((64, 8))
+        for l in range(64):
+            jj, q = l & 15, l >> 4
+            a[l][:4] = tr_read(tile, PITCH, q, jj, 0, 16 * nt)
+            a[l][4:] = tr_read(tile, PITCH, q, jj, 16, 16 * nt)
+        d = np.zeros((64, 4))
+        for f in frags:
+            d = mfma(a, f, d)
+        acc.append(d)
+    return acc
+
+
+def colreduce16(X, T, layout="RK", split=False):
+    """D = T^T X for X [M, K] (K % 32 == 0), T [M, r], 9 <= r <= 64, as the kernel's waves walk it: NS = ceil(r / 16) slices,
+    32-row steps (the last one ragged), one wave per 32-column group; the store map lane (rank j = 16 sl + jj, columns
+    n .. n + 3, n = col0 + 16 nt + 4 q) into D[r, K] (RK) or D[K, r] (KR).  Ranks at or past r are never stored: the
+    accumulators of those lanes are returned in `dead` (they must be zero)."""
+    M, K = X.shape
+    r = T.shape[1]
+    ns = (r + 15) // 16
+    D = np.full((r, K) if layout == "RK" else (K, r), np.nan)
+    dead = []
+    for col0 in range(0, K, 32):
+        acc = [[np.zeros((64, 4)) for _ in range(ns)] for _ in range(2)]
+        for m0 in range(0, M, 32):
+            for sl in range(ns):
+                step = colreduce16_step(X[m0:m0 + 32, col0:col0 + 32], T[m0:m0 + 32], sl, split)
+                for nt in range(2):
+                    acc[nt][sl] += step[nt]
+        for sl in range(ns):
+            for l in range(64):
+                jj, q = l & 15, l >> 4
+                j = 16 * sl + jj
+                for nt in range(2):
+                    if j >= r:
+                        dead.append(acc[nt][sl][l])
+                        continue
+                    for reg in range(4):
+                        nn = col0 + 16 * nt + 4 * q + reg
+                        if layout == "RK":
+                            D[j, nn] = acc[nt][sl][l][reg]
+                        else:
+                            D[nn, j] = acc[nt][sl][l][reg]
+    return D, np.array(dead)
+
+
+def check_colreduce16():
+    rng = np.random.default_rng(1)
+    for r, M in ((9, 32), (17, 45), (64, 70)):   # whole steps; a ragged last step; three steps, four slices
+        X = bf16_round(rng.standard_normal((M, 64)).astype(np.float32))
+        T = rng.standard_normal((M, r)).astype(np.float32).astype(np.float64)
+        for layout in ("RK", "KR"):
+            D, dead = colreduce16(X, T, layout)
+            want = T.T @ X
+            assert np.allclose(D, want if layout == "RK" else want.T)
+            assert not np.isnan(D).any() and not dead.any() and (len(dead) > 0) == (r % 16 != 0)
+        # hi + lo: T to ~16 mantissa bits, against 8 for hi alone
+        Ds, _ = colreduce16(X, T, "RK", split=True)
+        bound = np.abs(T).T @ np.abs(X)
+        assert np.all(np.abs(Ds - T.T @ X) <= 2.0 ** -15 * bound)
+        hi, lo = split_hi_lo(T)
+        assert np.allclose(Ds, (hi + lo).T @ X, rtol=0, atol=1e-12 * bound.max())
+        assert np.abs(hi.T @ X - T.T @ X).max() > 2.0 ** -15 * bound.max()
+    return True
+
+
 def check():
     rng = np.random.default_rng(0)
     for r in (16, 12, 9):
@@ -135,4 +247,4 @@ def check():
 
 
 if __name__ == "__main__":
-    print("ok" if check() else "mismatch")
+    print("ok" if check() and check_colreduce16() else "mismatch")
