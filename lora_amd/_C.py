@@ -1638,7 +1638,10 @@ def linear_bwd_g_blocks(M: int, N: int, r: int) -> int:
 
 
 def linear_bwd_g_folded_ok(g: torch.Tensor, up: torch.Tensor, r: int) -> bool:
-    return g.dtype == torch.bfloat16 and up.dtype == torch.float32 and 8 < r <= 16
+    """Does ``lora_amd_linear_bwd_g_folded`` take this G pass?  Matrix-core form only: bf16 rows, f32 factors, rank 9..16 and
+    the hook of those forms on (``rank16_mfma``) — with it off the entry answers LORA_AMD_EUNSUPPORTED and the caller's other
+    path is ``linear_bwd_g`` + ``sum_parts``."""
+    return g.dtype == torch.bfloat16 and up.dtype == torch.float32 and 8 < r <= 16 and rank16_mfma(-1) == 1
 
 
 def linear_bwd_g_folded(g: torch.Tensor, t: torch.Tensor, up: torch.Tensor, gt_part: torch.Tensor, gt_out: torch.Tensor,

@@ -1915,6 +1915,8 @@ def conv_native_ok(x: torch.Tensor, weight: torch.Tensor, r: int, stride, paddin
     if kh != kw or kh not in (1, 3) or tuple(padding) != ((kh - 1) // 2,) * 2:
         return False
     B, Ci, H, W = x.shape
+    if r > _C.MAX_RANK:  # the plan answers LORA_AMD_ERANK there, not native = 0: such a site takes lora_conv_branch
+        return False
     return bool(_C.conv_plan(B, Ci, weight.shape[0], H, W, kh, r).native)
 
 
