@@ -255,8 +255,11 @@ int lora_amd_colreduce(const void *x, int64_t ldx, const float *t, float *d_out,
  * launch instead of one torch.linalg.svd per site).
  *   rowdot_batched:    T_b[M, r] (f32) = scale * X_b[M, K] @ F_b^T           (F_b [r, K] or [K, r])
  *   colreduce_batched: D_b (f32, [r, K] or [K, r]) = scale * T_b^T @ X_b     (workspace: batch * colreduce_workspace)
- *   chol_inverse_batched: out_b = L_b^{-1} with G_b + shift_rel * tr(G_b)/l * I = L_b L_b^T  (l <= 32), so that
- *                      Q_b = Y_b L_b^{-T} = rowdot_batched(Y_b, out_b) is orthonormal when G_b = Y_b^T Y_b. */
+ *   chol_inverse_batched: out_b = L_b^{-1} with G_b + shift_rel * tr(G_b)/l * I = L_b L_b^T  (l <= 80), so that
+ *                      Q_b = Y_b L_b^{-T} = rowdot_batched(Y_b, out_b) is orthonormal when G_b = Y_b^T Y_b.  f64 inside; a
+ *                      pivot below 1e-30 + 1e-6 max diag is dropped (its row and column of out_b are zero).  l <= 32: one
+ *                      wave per matrix; 33 <= l <= 80 (the sketches of cli_svd's ranks 17..64): one workgroup of two waves
+ *                      per matrix, the inverse formed in place, the same arithmetic. */
 int lora_amd_rowdot_batched(const void *x, int64_t ldx, int64_t stride_x, const void *factor, int64_t stride_factor,
                             float *t_out, int64_t stride_t, int32_t batch, int64_t M, int32_t K, int32_t r,
                             int32_t x_dtype, int32_t factor_dtype, int32_t factor_layout, float scale, void *stream);
@@ -293,7 +296,10 @@ int lora_amd_rowdot_ragged(const lora_amd_ragged_desc *descs_dev, int32_t n, int
 int lora_amd_colreduce_ragged(const lora_amd_ragged_desc *descs_dev, int32_t n, int64_t grid1, int64_t grid2, int32_t r,
                               int32_t out_layout, float scale, void *stream);
 /* The same skinny products on the matrix cores for stacks held as two 16-bit planes (X = hi + lo, the bytes of f32):
- * out[b] [M, r] = X[b] [M, C] @ F[b] [C, r]  (r <= 16, C % 32 == 0).  lora_amd_split16_ragged makes the planes of flat f32
+ * out[b] [M, r] = X[b] [M, C] @ F[b] [C, r]  (r <= 80, C % 32 == 0).  17 <= r <= 80 (the sketches of cli_svd's ranks 17..64) is
+ * the wide form: the same plan and grid, ceil(r / 16) 16-column slices of F fed from ONE read of the planes; column block s of
+ * `out` has the bits of the 16-column launch on F[:, 16 s : 16 s + 16].  C <= 2^21 (the plan checks).
+ * lora_amd_split16_ragged makes the planes of flat f32
  * arrays (n % 8 == 0 each; `begin` = running count of 4096-element blocks, filled by the caller).
  * replaces: the colreduce passes over dW / dW^T of the subspace iteration (cli_svd.py:24-92 as restated in cli_svd.py). */
 typedef struct lora_amd_planes_desc {

@@ -775,7 +775,8 @@ def colreduce_batched(x: torch.Tensor, t: torch.Tensor, layout: int = FACTOR_RK,
 
 
 def chol_inverse_batched(gram: torch.Tensor, shift_rel: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """L^{-1} [B, l, l] for G + shift_rel * tr(G)/l * I = L L^T (l <= 32): the small dense step of CholeskyQR."""
+    """L^{-1} [B, l, l] for G + shift_rel * tr(G)/l * I = L L^T (l <= 80; above 32 one workgroup per matrix instead of
+    one wave): the small dense step of CholeskyQR."""
     lib = require()
     _dev_check(gram)
     if gram.dim() != 3 or gram.shape[1] != gram.shape[2] or gram.dtype != torch.float32 or not gram.is_contiguous():

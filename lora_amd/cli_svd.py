@@ -32,6 +32,11 @@ largest-magnitude entry of every ``down`` row positive, so results are reproduci
 (tests/test_gpu_parity_r2.py) compares, after aligning each pair's sign to the reference's, the factors, the clamp
 threshold and the clamped factors with the reference recipe.
 
+Ranks 17..64 (``WIDE``): the non-fused ragged iteration on a sketch of 16 ceil((rank + oversample) / 16) columns (32..80) — the
+products with dW / dW^T as ONE launch each over the planes whatever the width (``lora_amd_rowdot16_planes`` at r = l), CholeskyQR3
+through ``lora_amd_chol_inverse_batched`` (l <= 80), one batched l x l core SVD; sites whose shape is no multiple of 32 both ways or
+narrower than the sketch: one exact SVD on the device.  ``ROUTES`` counts the sites per route.
+
 CPU tensors take the reference's exact full-SVD path (plumbing).
 """
 from __future__ import annotations
@@ -41,7 +46,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _C
+from . import _C, ops
 from .lora import (LoraInjectedConv2d, LoraInjectedLinear, inject_trainable_lora, inject_trainable_lora_extended,
                    save_all)
 
@@ -68,6 +73,20 @@ RES_TOL, MIN_ITER, MAX_ITER = 1e-3, 4, 12   # MIN_ITER = the fixed count of roun
 # iterations' `dW Qz` and b = Q^T dW) read both planes.  False: every pass on both planes (rounds 4-5).
 HI_ONLY_ITERATIONS = True
 LAST_ITERATIONS = None  # power iterations the last fused distillation ran (evidence for bench.py)
+# Ranks 17..64 on the planes: a sketch of l = 16 ceil((rank + oversample) / 16) columns (32..80), the four products with
+# dW / dW^T as ONE wide launch each over the planes (``lora_amd_rowdot16_planes`` at r = l: ceil(l / 16) column slices fed from one
+# read), CholeskyQR3 on ``lora_amd_chol_inverse_batched`` up to l = 80, fixed iteration count.  False (LORA_AMD_AB ``SVD_WIDE=0``):
+# ranks 17..32 on a sketch capped at 32 columns through the f32 passes, ranks above 32 one exact SVD per site.
+WIDE = ops.SVD_WIDE
+WIDE_MAX_RANK = 64
+# sites distilled since import, by the route they took (tests and scripts/bench_svd_rank.py read differences): "fused16" = the
+# 16-wide sketch with the fused small steps, "ragged_f32" = the batched / ragged launches of rounds 2-4 (sketches of 16..32
+# columns), "wide_planes" = ranks 17..64 on the planes, "exact" = one full torch.linalg.svd of the site's residual
+ROUTES = {"fused16": 0, "ragged_f32": 0, "wide_planes": 0, "exact": 0}
+
+
+def _wide(rank: int) -> bool:
+    return WIDE and 16 < rank <= WIDE_MAX_RANK
 
 
 def _iter_lora(model):  # ref :16-21
@@ -87,16 +106,22 @@ def _orth(y: torch.Tensor) -> torch.Tensor:
     """Columns of every matrix of the stack ``y`` [B, M, l] orthonormalised on the device: shifted CholeskyQR3
     (Fukaya et al.): the first pass adds a shift to the Gram matrix so that the f32 Cholesky cannot break down on an
     ill-conditioned block (power iteration drives the columns towards each other), the two clean passes restore
-    orthonormality to f32 precision.  9 small batched launches; no host round trip."""
+    orthonormality to f32 precision.  9 small batched launches; no host round trip.  Blocks wider than the 64 columns of
+    the batched launches (the 80-column sketch of ranks 57..64): Gram matrix and Y L^{-T} by ``torch.bmm``, as the ragged
+    iteration runs them at that width."""
+    wide = y.shape[2] > _C.MAX_RANK
     for shift in (1e-4, 0.0, 0.0):
-        gram = _C.colreduce_batched(y, y, _C.FACTOR_RK)                  # [B, l, l] = Y^T Y
+        gram = torch.bmm(y.transpose(1, 2), y) if wide else _C.colreduce_batched(y, y, _C.FACTOR_RK)   # [B, l, l] = Y^T Y
         linv = _C.chol_inverse_batched(gram, shift)                       # L^{-1}
-        y = _C.rowdot_batched(y, linv, _C.FACTOR_RK)                      # Y L^{-T}
+        y = torch.bmm(y, linv.transpose(1, 2)) if wide else _C.rowdot_batched(y, linv, _C.FACTOR_RK)   # Y L^{-T}
     return y
 
 
 def _sketch_width(rank: int, oversample: int, N: int, K: int) -> int:
-    """Sketch columns: rank + max(oversample, rank) rounded up to the kernels' 8-column granule, at most 32."""
+    """Sketch columns: rank + max(oversample, rank) rounded up to the kernels' 8-column granule, at most 32; ranks 17..64
+    (``WIDE``): rank + oversample rounded up to the 16 columns of a matrix-core slice (32..80 at the default oversample)."""
+    if _wide(rank):
+        return -(-(rank + oversample) // 16) * 16
     l = -(-(rank + max(oversample, rank)) // 8) * 8
     return min(l, 32)
 
@@ -104,6 +129,8 @@ def _sketch_width(rank: int, oversample: int, N: int, K: int) -> int:
 def group_supported(N: int, K: int, rank: int, oversample: int = 8) -> bool:
     """Shapes the batched device path takes: 16-byte-friendly rows and a sketch that fits the small dense kernels."""
     l = _sketch_width(rank, oversample, N, K)
+    if _wide(rank):   # the planes and their 32 x 32 tiles both ways; any other site of these ranks: the exact SVD
+        return N % 32 == 0 and K % 32 == 0 and rank <= l <= min(N, K, 80)
     return K % 8 == 0 and rank <= l <= min(N, K)
 
 
@@ -118,6 +145,9 @@ def topr_svd_batched(delta: torch.Tensor, rank: int, oversample: int = 8, n_iter
     if not group_supported(N, K, rank, oversample):
         raise ValueError(f"topr_svd_batched: shape {N}x{K} rank {rank} is outside the batched device path")
     delta = delta.float().contiguous()
+    if _wide(rank):   # a single group is a table of one
+        return topr_svd_ragged([delta], rank, oversample, n_iter, generator)[0]
+    ROUTES["ragged_f32"] += B
     # both products of the iteration as column-reduction passes (the faster primitive: ~2 TB/s on f32 rows, the row-dot
     # form re-stages its factor tile per few rows of a tall-and-wide weight): dW^T Q streams dW, dW Qz streams the
     # resident transposed stack (a second f32 layout of the residuals; 288 GB of HBM)
@@ -150,6 +180,7 @@ def topr_svd(delta: torch.Tensor, rank: int, oversample: int = 8, n_iter: Option
     device).  CPU tensors: exact ``torch.linalg.svd`` (what the reference runs)."""
     N, K = delta.shape
     if not delta.is_cuda or not group_supported(N, K, rank, oversample):
+        ROUTES["exact"] += 1
         U, S, Vh = torch.linalg.svd(delta.float(), full_matrices=False)
         U, S, Vh = U[:, :rank], S[:rank], Vh[:rank]
         if delta.is_cuda:  # same deterministic sign rule as the batched path
@@ -366,6 +397,7 @@ def _distill_thin(pairs, rank: int, clamp_quantile: float, n_iter, generator):
     """``topr_svd_ragged`` + ``_clamp_pairs`` with the small steps fused, from (tuned, base) weight lists per shape group:
     returns per group (up [B, N, r], down [B, r, K])."""
     st = _subspace_thin(None, rank, n_iter, generator, pairs=pairs)
+    ROUTES["fused16"] += st.nb
     dev = st.ya.device
     # up = Q Ub[:, :r] diag(S) diag(sign)
     _C.thin_rotate(st.ty, st.yb, st.ubt, rank, st.uo, scale_a=st.s, scale_b=st.sign)
@@ -408,22 +440,33 @@ def _thin_ok(dims, rank: int, oversample: int) -> bool:
 
 
 def topr_svd_ragged(deltas, rank: int, oversample: int = 8, n_iter: Optional[int] = 4,
-                    generator: Optional[torch.Generator] = None):
+                    generator: Optional[torch.Generator] = None, pairs=None):
     """``topr_svd_batched`` for a LIST of stacks of different shapes ([B_g, N_g, K_g] f32, contiguous) run in lock-step:
     every step of the iteration is ONE launch (pair) for the whole model — ``lora_amd_colreduce_ragged`` /
     ``lora_amd_rowdot_ragged`` over a descriptor table with one entry per shape group, ``chol_inverse_batched`` and the
     l x l core SVD over the concatenation of all groups.  SD1.5 extended (224 sites, 31 shapes): ~110 launches instead
-    of ~3100.  Returns per group (U [B,N,r], S [B,r], Vh [B,r,K]) with the deterministic sign rule of the batched path."""
+    of ~3100.  Returns per group (U [B,N,r], S [B,r], Vh [B,r,K]) with the deterministic sign rule of the batched path.
+    Ranks 17..64 (``WIDE``): the same steps on a sketch of 32..80 columns, the products with dW / dW^T as one wide launch each
+    over the planes; ``pairs`` = [(tuned list, base list)] per group instead of ``deltas``: the planes come straight out of the
+    launch that forms the residuals (``lora_amd_split16_residual``)."""
     _C.require()
-    dev = deltas[0].device
-    dims = [tuple(d.shape) for d in deltas]
+    wide = _wide(rank)
+    if pairs is not None:
+        if not wide:
+            raise ValueError("topr_svd_ragged: (tuned, base) pairs are taken by the wide path only")
+        dev = pairs[0][0][0].device
+        dims = [(len(t), t[0].shape[0], t[0].numel() // t[0].shape[0]) for t, _ in pairs]
+    else:
+        dev = deltas[0].device
+        dims = [tuple(d.shape) for d in deltas]
     l = _sketch_width(rank, oversample, dims[0][1], dims[0][2])
     for (B, N, K) in dims:
         if not group_supported(N, K, rank, oversample) or _sketch_width(rank, oversample, N, K) != l:
             raise ValueError(f"topr_svd_ragged: shape {N}x{K} rank {rank} is outside the batched device path")
     nb = sum(B for B, _, _ in dims)
-    planes = PLANES and l == 16 and all(N % 32 == 0 and K % 32 == 0 for _, N, K in dims)
-    if planes and THIN:
+    planes = wide or (PLANES and l == 16 and all(N % 32 == 0 and K % 32 == 0 for _, N, K in dims))
+    if planes and THIN and not wide:
+        ROUTES["fused16"] += nb
         st = _subspace_thin([d.contiguous() for d in deltas], rank, n_iter, generator)
         _C.thin_rotate(st.ty, st.yb, st.ubt, rank, st.uo, scale_a=st.sign)        # U = Q Ub[:, :r] diag(sign)
         vt = torch.empty_like(st.vo)
@@ -436,6 +479,7 @@ def topr_svd_ragged(deltas, rank: int, oversample: int = 8, n_iter: Optional[int
         return out
     if n_iter is None:
         n_iter = 4
+    ROUTES["wide_planes" if wide else "ragged_f32"] += nb
     # second resident layout of the residuals (f32 passes only: the planes of dW^T come out of the split launch)
     delta_t = None if planes else [d.transpose(1, 2).contiguous() for d in deltas]
     yshape = [(B, N, l) for B, N, K in dims]
@@ -458,12 +502,33 @@ def topr_svd_ragged(deltas, rank: int, oversample: int = 8, n_iter: Optional[int
         o += B
     per = lambda t: [t[o:o + B] for o, (B, _, _) in zip(boffs, dims)]  # noqa: E731
     G, L, Cr, Ub, Vb = per(gram), per(linv), per(core), per(ubt), per(vb)
-    ws = [torch.empty(B * max(_C.colreduce_workspace_floats(N, K, l), _C.colreduce_workspace_floats(K, N, l)),
-                      dtype=torch.float32, device=dev) for B, N, K in dims]
+    # the small dense steps (Gram, Y L^-T, the l x l core, the rotation to `rank` columns): ragged launches over all groups up to
+    # their 64 columns; the 80-column sketch of ranks 57..64: one torch.bmm per shape group and step (a few MB per distillation)
+    dense_ragged = l <= _C.MAX_RANK
+    if dense_ragged:
+        ws = [torch.empty(B * max(_C.colreduce_workspace_floats(N, K, l), _C.colreduce_workspace_floats(K, N, l)),
+                          dtype=torch.float32, device=dev) for B, N, K in dims]
+        prog = _C.RaggedProgram(dev)
 
-    prog = _C.RaggedProgram(dev)
-    cr = lambda xs, fs, outs: prog.table(_C.RAGGED_COLREDUCE, l, list(zip(xs, fs, outs, ws)))  # noqa: E731
-    rd = lambda xs, fs, outs, r=l: prog.table(_C.RAGGED_ROWDOT, r, [(x, f, o_, None) for x, f, o_ in zip(xs, fs, outs)])  # noqa: E731
+        def cr(xs, fs, outs):                # outs[g] = fs[g]^T xs[g]
+            h = prog.table(_C.RAGGED_COLREDUCE, l, list(zip(xs, fs, outs, ws)))
+            return lambda: prog.run(h, _C.FACTOR_RK)
+
+        def rd(xs, fs, outs, r=l):           # outs[g] = xs[g] fs[g]^T
+            h = prog.table(_C.RAGGED_ROWDOT, r, [(x, f, o_, None) for x, f, o_ in zip(xs, fs, outs)])
+            return lambda: prog.run(h, _C.FACTOR_RK)
+    else:
+        def cr(xs, fs, outs):
+            def run():
+                for x, f, o_ in zip(xs, fs, outs):
+                    torch.bmm(f.transpose(1, 2), x, out=o_)
+            return run
+
+        def rd(xs, fs, outs, r=l):
+            def run():
+                for x, f, o_ in zip(xs, fs, outs):
+                    torch.bmm(x, f.transpose(1, 2), out=o_)
+            return run
     if planes:
         # dW and dW^T as (hi, lo) bf16 planes — the bytes of two f32 stacks, all four written by ONE launch that reads dW once
         # (lora_amd_split16_transpose); every product with them is then a row product on the matrix cores: Y = dW F streams
@@ -473,8 +538,11 @@ def topr_svd_ragged(deltas, rank: int, oversample: int = 8, n_iter: Optional[int
                     [torch.empty(sh, dtype=torch.bfloat16, device=dev) for sh in shapes_])
         dh, dl = planes_of([(B, N, K) for B, N, K in dims])
         th, tl = planes_of([(B, K, N) for B, N, K in dims])
-        _C.split16_transpose([d.contiguous() for d in deltas], dh, dl, th, tl)
-        pprog = _C.PlanesProgram(dev, l)
+        if pairs is not None:
+            _C.split16_residual(pairs, dims, dh, dl, th, tl)
+        else:
+            _C.split16_transpose([d.contiguous() for d in deltas], dh, dl, th, tl)
+        pprog = _C.PlanesProgram(dev, l)      # l > 16: the wide launch, ceil(l / 16) column slices from one read of the planes
         p_sketch = pprog.table(list(zip(dh, dl, Zc, Ya)))     # Y = dW Omega
         p_fwd = pprog.table(list(zip(th, tl, Yb, Za)))        # Z = dW^T Q
         p_back = pprog.table(list(zip(dh, dl, Zb, Ya)))       # Y = dW Qz
@@ -483,10 +551,11 @@ def topr_svd_ragged(deltas, rank: int, oversample: int = 8, n_iter: Optional[int
         big = {"sketch": lambda: pprog.run(p_sketch), "fwd": lambda: pprog.run(p_fwd), "back": lambda: pprog.run(p_back),
                "b": lambda: pprog.run(p_b)}
     else:
-        t_sketch = cr(delta_t, Zc, Ya)          # Y = dW Omega
-        t_fwd = cr(deltas, Yb, Za)              # Z = dW^T Q
-        t_back = cr(delta_t, Zb, Ya)            # Y = dW Qz
-        t_b = cr(deltas, Yb, Zc)                # b^T = dW^T Q
+        kr = lambda xs, fs, outs: prog.table(_C.RAGGED_COLREDUCE, l, list(zip(xs, fs, outs, ws)))  # noqa: E731
+        t_sketch = kr(delta_t, Zc, Ya)          # Y = dW Omega
+        t_fwd = kr(deltas, Yb, Za)              # Z = dW^T Q
+        t_back = kr(delta_t, Zb, Ya)            # Y = dW Qz
+        t_b = kr(deltas, Yb, Zc)                # b^T = dW^T Q
         big = {"sketch": lambda: prog.run(t_sketch, _C.FACTOR_KR), "fwd": lambda: prog.run(t_fwd, _C.FACTOR_KR),
                "back": lambda: prog.run(t_back, _C.FACTOR_KR), "b": lambda: prog.run(t_b, _C.FACTOR_KR)}
     t_core = cr(Za, Zc, Cr)                 # b Qb  [l, l]
@@ -494,15 +563,16 @@ def topr_svd_ragged(deltas, rank: int, oversample: int = 8, n_iter: Optional[int
     apply_l = {(id(a[0]), id(b[0])): rd(a, L, b) for a, b in ((Ya, Yb), (Yb, Ya), (Za, Zb), (Zb, Za), (Zc, Za))}
     t_u = rd(Yb, Ub, Uo, rank)
     t_v = rd(Za, Vb, Vo, rank)
-    prog.upload()
+    if dense_ragged:
+        prog.upload()
     lib_chol = _C.chol_inverse_batched
 
     def orth(chain):
         """CholeskyQR3 along ``chain`` = (src, tmp, ..., dst): shifted first pass, two clean ones (see ``_orth``)."""
         for shift, (a, b) in zip((1e-4, 0.0, 0.0), zip(chain[:-1], chain[1:])):
-            prog.run(gram_of[id(a[0])], _C.FACTOR_RK)
+            gram_of[id(a[0])]()
             lib_chol(gram, shift, out=linv)
-            prog.run(apply_l[(id(a[0]), id(b[0]))], _C.FACTOR_RK)
+            apply_l[(id(a[0]), id(b[0]))]()
 
     zc_flat.normal_(generator=generator)                          # Omega, every group at once
     big["sketch"]()
@@ -514,12 +584,18 @@ def topr_svd_ragged(deltas, rank: int, oversample: int = 8, n_iter: Optional[int
         orth((Ya, Yb, Ya, Yb))
     big["b"]()                                                    # b^T [K, l] in Zc
     orth((Zc, Za, Zb, Za))                                        # qb in Za
-    prog.run(t_core, _C.FACTOR_RK)
-    ub, s, vbh = torch.linalg.svd(core, full_matrices=False)      # [sum B, l, l]: one batched call for the model
+    t_core()
+    if l > 32:
+        # the library's batched device SVD stops at 32 x 32: above it the call walks the batch, one solver launch sequence per
+        # core (224 cores: 340 ms at l = 48, 880 ms at l = 80, nine tenths of the distillation; profiles/svd_wide_ab.txt).  The
+        # cores are a few MB: one copy to the host, LAPACK there, one copy back
+        ub, s, vbh = (t.to(dev) for t in torch.linalg.svd(core.cpu(), full_matrices=False))
+    else:
+        ub, s, vbh = torch.linalg.svd(core, full_matrices=False)  # [sum B, l, l]: one batched call for the model
     ubt.copy_(ub[:, :, :rank].transpose(1, 2))
     vb.copy_(vbh[:, :rank])
-    prog.run(t_u, _C.FACTOR_RK)                                   # U = Q Ub[:, :r]
-    prog.run(t_v, _C.FACTOR_RK)                                   # Vh^T = Qb Vb[:r]^T
+    t_u()                                                         # U = Q Ub[:, :r]
+    t_v()                                                         # Vh^T = Qb Vb[:r]^T
     out = []
     for (o, (B, N, K)), u, vt in zip(zip(boffs, dims), Uo, Vo):
         idx = vt.abs().argmax(dim=1, keepdim=True)                # [B, 1, r]: the largest-magnitude entry of each down row
@@ -563,6 +639,14 @@ def distill_model(groups, rank: int, clamp_quantile: float = 0.99, generator: Op
             for (gi, _, _, _), ud in zip(thin, res):
                 results[gi] = ud
         if not ents:
+            continue
+        if _wide(rank):
+            # residuals and their planes in one launch, then the wide iteration over every group at once
+            flat2 = [([t.reshape(t.shape[0], -1) for t in groups[gi][0]], [b.reshape(b.shape[0], -1) for b in groups[gi][1]])
+                     for gi, _, _, _ in ents]
+            trip = topr_svd_ragged(None, rank, generator=generator, pairs=flat2, **svd_kw)
+            for (gi, _, _, _), (U, S, Vh) in zip(ents, trip):
+                results[gi] = _clamp_pairs(U * S[:, None, :], Vh, clamp_quantile)
             continue
         _, deltas = _flat_stacks([(B, N, K) for _, B, N, K in ents], dev)
         pairs, outs = [], []

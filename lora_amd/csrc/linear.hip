@@ -1011,10 +1011,69 @@ __global__ __launch_bounds__(64) void chol_inverse_kernel(const float *__restric
   }
 }
 
+// The same for 33 <= l <= 80 (the sketches of cli_svd's ranks 17..64): one workgroup of two waves per matrix, thread = row of
+// the factorisation and column of the inverse, the arithmetic of the one-wave kernel (f64, relative shift, pivot floor with its
+// infinite pivot).  80 x 81 doubles are 52 KB, so the inverse is formed IN PLACE: column c of X = L^{-1} (rows below c) goes
+// to row c of the strict upper triangle, which L does not use and only thread c touches; the diagonal of X to its own array.
+constexpr int kCholWideMax = 80, kCholWideThreads = 128;
+__global__ __launch_bounds__(kCholWideThreads) void chol_inverse_wide_kernel(const float *__restrict__ gram, float *__restrict__ out,
+                                                                             int l, float shift_rel) {
+  __shared__ double A[kCholWideMax][kCholWideMax + 1];
+  __shared__ double xd[kCholWideMax];
+  const int t = threadIdx.x;
+  const float *g = gram + (int64_t)blockIdx.x * l * l;
+  float *o = out + (int64_t)blockIdx.x * l * l;
+  double tr = 0.0;
+  for (int i = 0; i < l; ++i) tr += (double)g[i * l + i];
+  const double shift = (double)shift_rel * tr / (double)l;
+  for (int idx = t; idx < l * l; idx += kCholWideThreads) {
+    const int i = idx / l, j = idx - i * l;
+    A[i][j] = 0.5 * ((double)g[i * l + j] + (double)g[j * l + i]) + (i == j ? shift : 0.0);
+  }
+  __syncthreads();
+  double dmax = 0.0;
+  for (int i = 0; i < l; ++i) dmax = fmax(dmax, A[i][i]);
+  const double floor_ = 1e-30 + 1e-6 * dmax;   // see chol_inverse_kernel
+  for (int j = 0; j < l; ++j) {
+    double d = A[j][j];
+    d = d > floor_ ? sqrt(d) : (double)INFINITY;
+    __syncthreads();
+    if (t == j) A[j][j] = d;
+    if (t > j && t < l) A[t][j] /= d;
+    __syncthreads();
+    if (t > j && t < l) {
+      const double lij = A[t][j];
+      for (int k = j + 1; k <= t; ++k) A[t][k] -= lij * A[k][j];
+    }
+    __syncthreads();
+  }
+  // forward substitution, thread = column c of the inverse: L x = e_c; x_i = 0 above the diagonal, so the sums start at c
+  if (t < l) {
+    const double xcc = 1.0 / A[t][t];
+    xd[t] = xcc;
+    for (int i = t + 1; i < l; ++i) {
+      double s = 0.0;
+      s -= A[i][t] * xcc;
+      for (int k = t + 1; k < i; ++k) s -= A[i][k] * A[t][k];
+      A[t][i] = s / A[i][i];
+    }
+  }
+  __syncthreads();
+  for (int idx = t; idx < l * l; idx += kCholWideThreads) {
+    const int i = idx / l, j = idx - i * l;
+    o[idx] = (float)(i > j ? A[j][i] : i == j ? xd[i] : 0.0);
+  }
+}
+
 extern "C" int lora_amd_chol_inverse_batched(const float *gram, float *out, int32_t l, int32_t batch, float shift_rel,
                                              void *stream) {
-  LORA_AMD_CHECK(gram && out && l >= 1 && l <= 32 && batch >= 1, LORA_AMD_EINVAL,
-                 "chol_inverse_batched: l in [1,32], batch >= 1");
+  LORA_AMD_CHECK(gram && out && l >= 1 && l <= kCholWideMax && batch >= 1, LORA_AMD_EINVAL,
+                 "chol_inverse_batched: l in [1,80], batch >= 1");
+  if (l > 32) {
+    hipLaunchKernelGGL(chol_inverse_wide_kernel, dim3((unsigned)batch), dim3(kCholWideThreads), 0, (hipStream_t)stream, gram, out, l,
+                       shift_rel);
+    return check_launch("lora_amd_chol_inverse_batched");
+  }
   hipLaunchKernelGGL(chol_inverse_kernel, dim3((unsigned)batch), dim3(64), 0, (hipStream_t)stream, gram, out, l, shift_rel);
   return check_launch("lora_amd_chol_inverse_batched");
 }

@@ -34,6 +34,8 @@
 // dW = W_tuned - W_base are f32, which has no full-rate matrix-core path on gfx950, so they are held as TWO bf16 planes
 // (dW = hi + lo to ~16 mantissa bits: the bytes of f32) written by split16_transpose_kernel (one read of dW -> the planes of
 // dW and of dW^T), and rowdot16_planes_kernel computes out = X F as hi F_hi + hi F_lo + lo F_hi: 3.6 TB/s per pass.
+// rowdot16_planes_wide_kernel is the same product for 17..80 output columns (cli_svd's ranks 17..64): every 16-column slice of
+// the factor from ONE read of the planes.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -795,6 +797,161 @@ __global__ __launch_bounds__(1024) void rowdot16_planes_kernel(const lora_amd_pl
   }
 }
 
+// The wide form (17 <= r <= 80 output columns: the sketches of cli_svd's ranks 17..64): NSL 16-column slices s0 .. s0 + NSL - 1
+// of the factor [C][r] against the same plan, grid and dealing as the 16-column launch.  The passes are byte-bound, so a wave
+// fetches each 16-byte piece of the hi and lo planes ONCE and feeds every slice's accumulators from it; the fragment pair of a
+// slice and k-step (r16_factor_load at j0 = 16 slice + split, ~50 VALU instructions) is built once and meets BOTH slabs of the
+// wave (kPlNS), where the 16-column f32-factor form above builds it per slab.  Per (slab, slice) the k-steps a wave takes, the
+// order of the three products and the order of the cross-wave sum are those of the 16-column kernel: column block s of the
+// output has the bits of that launch on F[:, 16 s : 16 s + 16].  The cross-wave meeting goes slice by slice through one
+// 32 KB image (two barriers per slice).  AHEAD: data pieces in flight ahead of the MFMAs (registers: 16 dwords per step).
+template <class E, int NSL, int AHEAD>
+__global__ __launch_bounds__(1024) void rowdot16_planes_wide_kernel(const lora_amd_planes_desc *__restrict__ descs, int n, int r,
+                                                                    int s0) {
+  using S = typename E::storage;
+  constexpr int NS = kPlNS;
+  __shared__ __attribute__((aligned(16))) float s_red[16 * NS * 4 * 64];
+  __shared__ int64_t s_begin[64];
+  const int tid = threadIdx.x, lane = tid & 63, jj = lane & 15, q = lane >> 4;
+  // wave and group are the same for every lane of a wave: in scalar registers, and with them the descriptor, every base
+  // address and the loop bounds (the accumulators of five slices leave the vector file no room for them)
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int lo = 0, hi = n - 1;
+  if (n <= 64) {
+    if (tid < n) s_begin[tid] = descs[tid].wg_begin;
+    __syncthreads();
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (s_begin[mid] <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+  } else {
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (descs[mid].wg_begin <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+  }
+  lo = __builtin_amdgcn_readfirstlane(lo);
+  const lora_amd_planes_desc d = descs[lo];
+  const int wps = d.wps, spw = NS * (16 / wps);   // == d.slabs_per_wg (lora_amd_rowdot16_planes_plan)
+  const int64_t nslabs = (d.M + 15) >> 4, wgs_per = (nslabs + spw - 1) / spw;
+  const int64_t wg = (int64_t)blockIdx.x - d.wg_begin;
+  const int64_t b = wg / wgs_per;
+  const int sl = wave / wps, cw = wave - sl * wps;
+  const int64_t slab0 = (wg - b * wgs_per) * spw + (int64_t)sl * NS;   // this wave's NS consecutive slabs
+  const int C = d.C, nks = C >> 5;
+  mf32x4 acc[NSL][NS];
+#pragma unroll
+  for (int t = 0; t < NSL; ++t)
+#pragma unroll
+    for (int s = 0; s < NS; ++s) acc[t][s] = mf32x4{0.f, 0.f, 0.f, 0.f};
+  if (slab0 < nslabs) {
+    // every load is a buffer load: a descriptor in scalar registers (this wave's 32 rows of a plane; the factor of the
+    // matrix), ONE per-lane byte offset that never changes, and the k-step as the scalar offset.  A row past M and a factor
+    // column at or past r lie outside their descriptor and read zero, as r16_factor_load's guard gives them.
+    const int64_t row0 = slab0 * 16;
+    const int64_t rows_left = d.M - row0;
+    const uint32_t xbytes = (uint32_t)((rows_left < 16 * NS ? rows_left : 16 * NS) * C * (int)sizeof(S));
+    const int64_t ebase = (b * d.M + row0) * (int64_t)C;
+    const auto rh = __builtin_amdgcn_make_buffer_rsrc(const_cast<S *>(reinterpret_cast<const S *>(d.hi) + ebase), 0, xbytes, 0x00020000);
+    const auto rl = __builtin_amdgcn_make_buffer_rsrc(const_cast<S *>(reinterpret_cast<const S *>(d.lo) + ebase), 0, xbytes, 0x00020000);
+    int xo[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) xo[s] = ((16 * s + jj) * C + 8 * q) * (int)sizeof(S);
+    constexpr int kOutside = 0x40000000;   // a per-lane offset past every descriptor: the load moves no bytes and gives zero
+    // (a k-step past the row is such a load, not a branch: a loop body without branches lets the compiler count its loads in
+    // flight instead of draining them)
+    auto piece = [&](decltype(rh) rs, int off, int ks) -> mu32x4 {
+      return __builtin_bit_cast(mu32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, ks < nks ? off : kOutside, ks * 32 * (int)sizeof(S), 0));
+    };
+    mu32x4 h0[NS], l0[NS], h1[NS], l1[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      h0[s] = piece(rh, xo[s], cw); l0[s] = piece(rl, xo[s], cw);
+      if constexpr (AHEAD == 2) { h1[s] = piece(rh, xo[s], cw + wps); l1[s] = piece(rl, xo[s], cw + wps); }
+    }
+    // the factor [C][r] as r16_factor_load(KR, j0 = 16 slice) reads it: lane (jj, q) of slice t holds F[32 ks + 8 q + e][16 (s0
+    // + t) + jj].  ONE raw fragment is in flight ahead of the one being split (the next slice's; after the last slice the next
+    // k-step's first): 16 registers whatever the slice count.
+    const auto rf = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(d.f + b * (int64_t)C * r), 0, C * r * 4, 0x00020000);
+    int vf[NSL];
+#pragma unroll
+    for (int t = 0; t < NSL; ++t) vf[t] = 16 * (s0 + t) + jj < r ? (8 * q * r + 16 * (s0 + t) + jj) * 4 : kOutside;
+    auto fload = [&](int t, int ks) -> R16Raw {
+      R16Raw w;
+      const int off = ks < nks ? vf[t] : kOutside;
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        w.v[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rf, off, (ks * 32 + e) * r * 4, 0));
+      return w;
+    };
+    R16Raw nxt = fload(0, cw);
+#pragma unroll 1
+    for (int ks = cw; ks < nks; ks += wps) {
+      mu32x4 h2[NS], l2[NS];
+#pragma unroll
+      for (int s = 0; s < NS; ++s) { h2[s] = piece(rh, xo[s], ks + AHEAD * wps); l2[s] = piece(rl, xo[s], ks + AHEAD * wps); }
+#pragma unroll
+      for (int t = 0; t < NSL; ++t) {
+        R16Raw cur = nxt;
+        if (t + 1 < NSL) nxt = fload(t + 1, ks);
+        else nxt = fload(0, ks + wps);
+        // the loads above stay above: left alone, the scheduler sinks each to its first use to save registers that a
+        // 1024-thread workgroup cannot turn into occupancy, and a slice then waits for four round trips to L2 in a row
+        __builtin_amdgcn_sched_barrier(0);
+        mu32x4 fh, fl;
+        r16_factor_split<E>(cur, 1.0f, fh, fl);
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          acc[t][s] = FmMfma<E>::mma(fm_frag<E>(h0[s]), fm_frag<E>(fh), acc[t][s]);
+          acc[t][s] = FmMfma<E>::mma(fm_frag<E>(h0[s]), fm_frag<E>(fl), acc[t][s]);
+          acc[t][s] = FmMfma<E>::mma(fm_frag<E>(l0[s]), fm_frag<E>(fh), acc[t][s]);
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if constexpr (AHEAD == 2) { h0[s] = h1[s]; l0[s] = l1[s]; h1[s] = h2[s]; l1[s] = l2[s]; }
+        else { h0[s] = h2[s]; l0[s] = l2[s]; }
+      }
+    }
+  }
+  if (wps > 1) {  // workgroup-uniform (one descriptor per workgroup)
+#pragma unroll
+    for (int t = 0; t < NSL; ++t) {
+      if (t > 0) __syncthreads();
+      if (cw > 0) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) s_red[((wave * NS + s) * 4 + reg) * 64 + lane] = acc[t][s][reg];
+      }
+      __syncthreads();
+      if (cw == 0) {
+        for (int k = 1; k < wps; ++k)
+#pragma unroll
+          for (int s = 0; s < NS; ++s)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) acc[t][s][reg] += s_red[(((wave + k) * NS + s) * 4 + reg) * 64 + lane];
+      }
+    }
+  }
+  if (cw > 0) return;
+  float *o = d.out + b * d.M * r;
+#pragma unroll
+  for (int t = 0; t < NSL; ++t) {
+    const int col = 16 * (s0 + t) + jj;
+    if (col >= r) continue;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      if (slab0 + s >= nslabs) continue;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int64_t rw = (slab0 + s) * 16 + 4 * q + reg;
+        if (rw < d.M) o[rw * r + col] = acc[t][s][reg];
+      }
+    }
+  }
+}
+
 // f32 -> (hi, lo) 16-bit planes of flat arrays, one launch over a table (8 elements per thread, 4096 per workgroup)
 template <class E>
 __global__ __launch_bounds__(256) void split16_ragged_kernel(const lora_amd_split_desc *__restrict__ descs, int n) {
@@ -1047,6 +1204,8 @@ extern "C" int lora_amd_rowdot16_planes_plan(lora_amd_planes_desc *descs, int32_
     LORA_AMD_CHECK(d.hi && d.lo && d.f && d.out && d.M >= 1 && d.batch >= 1, LORA_AMD_EINVAL, "rowdot16_planes_plan: group %d: null pointer / empty", i);
     LORA_AMD_CHECK(d.C >= 32 && d.C % 32 == 0 && (((uintptr_t)d.hi | (uintptr_t)d.lo) & 15u) == 0, LORA_AMD_EINVAL,
                    "rowdot16_planes_plan: group %d: C = %d must be a multiple of 32, planes 16-byte aligned", i, d.C);
+    // the wide form addresses a wave's 32 plane rows and the matrix's factor [C][<= 80] through 32-bit buffer offsets
+    LORA_AMD_CHECK(d.C <= (1 << 21), LORA_AMD_EINVAL, "rowdot16_planes_plan: group %d: C = %d above 2^21", i, d.C);
     // waves per slab: >= 4 k-steps each (a wave's chain of dependent loads is what bounds a long row)
     const int nks = d.C >> 5;
     int wps = 1;
@@ -1065,9 +1224,23 @@ extern "C" int lora_amd_rowdot16_planes_plan(lora_amd_planes_desc *descs, int32_
 extern "C" int lora_amd_rowdot16_planes(const lora_amd_planes_desc *descs_dev, int32_t n, int64_t grid, int32_t r,
                                         int32_t plane_dtype, void *stream) {
   LORA_AMD_CHECK(descs_dev && n >= 1 && grid >= 1 && grid < (1ll << 31), LORA_AMD_EINVAL, "rowdot16_planes: bad argument");
-  LORA_AMD_CHECK(r >= 1 && r <= 16, LORA_AMD_ERANK, "rowdot16_planes: %d output columns outside [1,16]", r);
+  LORA_AMD_CHECK(r >= 1 && r <= 80, LORA_AMD_ERANK, "rowdot16_planes: %d output columns outside [1,80]", r);
   LORA_AMD_CHECK(plane_dtype == LORA_AMD_BF16 || plane_dtype == LORA_AMD_F16, LORA_AMD_EINVAL, "rowdot16_planes: 16-bit planes only");
   hipStream_t st = (hipStream_t)stream;
+  if (r > 16) {
+    const int nsl = (r + 15) / 16;
+    by_dtype<f16_t, bf16_t>(plane_dtype, [&](auto e) {
+      using E = decltype(e);
+      auto go = [&](auto kern, int s0) { hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(1024), 0, st, descs_dev, n, r, s0); };
+      switch (nsl) {
+        case 2: go(rowdot16_planes_wide_kernel<E, 2, 2>, 0); break;
+        case 3: go(rowdot16_planes_wide_kernel<E, 3, 2>, 0); break;
+        case 4: go(rowdot16_planes_wide_kernel<E, 4, 2>, 0); break;
+        default: go(rowdot16_planes_wide_kernel<E, 5, 2>, 0); break;
+      }
+    });
+    return check_launch("lora_amd_rowdot16_planes");
+  }
   by_dtype<f16_t, bf16_t>(plane_dtype, [&](auto e) {
     hipLaunchKernelGGL((rowdot16_planes_kernel<decltype(e), false>), dim3((unsigned)grid), dim3(1024), 0, st, descs_dev, n, r);
   });

@@ -643,13 +643,16 @@ CONV3_WIDE = True
 # two-stage kernel, ceil(r / 16) passes
 # (tests/test_gpu_colreduce_mfma.py runs both)
 COLREDUCE_MFMA = True
+# cli_svd's distillation to ranks 17..64 on the matrix-core subspace iteration (cli_svd.WIDE takes its default from here, so
+# that the one A/B switch below reaches it); False = the capped 32-column sketch up to rank 32 and one exact SVD per site above
+SVD_WIDE = True
 
 
 def apply_ab_overrides(spec: str, namespace: dict) -> dict:
     """``LORA_AMD_AB="NAME=0,OTHER=1"``: the ONE measurement switch for same-box A/B runs — flips the module constants
     listed in ``allowed`` (and only those) without a code edit; every A/B log under profiles/ names the spec it ran with
     (a constant retired since then is an unknown name here)."""
-    allowed = ("ATTN_SHORT_BWD", "COLREDUCE_MFMA", "CONCAT_GROUPS", "CONV3_FUSED", "CONV3_WIDE", "GN_RESIDENT", "MASTER_MERGE", "MERGED_WIDE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
+    allowed = ("ATTN_SHORT_BWD", "COLREDUCE_MFMA", "CONCAT_GROUPS", "CONV3_FUSED", "CONV3_WIDE", "GN_RESIDENT", "MASTER_MERGE", "MERGED_WIDE", "SVD_WIDE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
                "WS_DROPOUT_WIDE_BWD", "WIDE_FACTORS", "WIDE_DROPOUT")
     done = {}
     for item in filter(None, (s.strip() for s in spec.split(","))):

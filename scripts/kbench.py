@@ -1041,6 +1041,63 @@ def bench_gn(args):
                                                       for k, v in tot.items()}}), flush=True)
 
 
+def bench_svd_wide(args):
+    """cli_svd's products with dW / dW^T at sketch widths 32..80 (LoRA ranks 17..64): ONE wide launch of
+    lora_amd_rowdot16_planes (every 16-column slice fed from one read of the planes) against ceil(l / 16) launches of the
+    16-column kernel on the slices, per SD1.5 shape group (the stack of the group's residuals, Y = dW F) and for the whole
+    model in one table both ways (Y = dW F and Z = dW^T Q: the passes the iteration runs).  Bytes = both planes."""
+    from collections import Counter
+
+    shapes = sorted(Counter(sd15_lora_site_shapes(extended=True)).items())
+    dev = torch.device(DEV)
+    g = torch.Generator(device=DEV).manual_seed(0)
+    planes = []
+    for (N, K), cnt in shapes:
+        x = torch.randn(cnt, N, K, device=DEV, generator=g) * 0.05
+        hi, lo = torch.empty_like(x, dtype=torch.bfloat16), torch.empty_like(x, dtype=torch.bfloat16)
+        th, tl = (torch.empty(cnt, K, N, dtype=torch.bfloat16, device=DEV) for _ in range(2))
+        _C.split16_transpose([x], [hi], [lo], [th], [tl])
+        planes.append((hi, lo, th, tl))
+        del x
+
+    def legs(rows, l):
+        """rows = [(hi, lo)]: (one wide launch, the per-slice launch sequence) as callables"""
+        fs = [torch.randn(h.shape[0], h.shape[2], l, device=DEV, generator=g) for h, _ in rows]
+        outs = [torch.empty(h.shape[0], h.shape[1], l, device=DEV) for h, _ in rows]
+        wide = _C.PlanesProgram(dev, l)
+        hw = wide.table([(h, lo_, f, o) for (h, lo_), f, o in zip(rows, fs, outs)])
+        wide.upload()
+        ns = -(-l // 16)
+        fsl = [[f[:, :, 16 * s:16 * s + 16].contiguous() for f in fs] for s in range(ns)]
+        osl = [[torch.empty(h.shape[0], h.shape[1], 16, device=DEV) for h, _ in rows] for _ in range(ns)]
+        p16 = _C.PlanesProgram(dev, 16)
+        hs = [p16.table([(h, lo_, f, o) for (h, lo_), f, o in zip(rows, fsl[s], osl[s])]) for s in range(ns)]
+        p16.upload()
+
+        def sliced():
+            for h_ in hs:
+                p16.run(h_)
+        return (lambda: wide.run(hw)), sliced, (wide, p16, fs, outs, fsl, osl)
+
+    for l in (32, 48, 64, 80):
+        for ((N, K), cnt), (hi, lo, th, tl) in zip(shapes, planes):
+            one, many, keep = legs([(hi, lo)], l)
+            t1, t2 = timeit(one, iters=args.iters, inner=5)[0], timeit(many, iters=args.iters, inner=5)[0]
+            byts = 4 * cnt * N * K
+            print(json.dumps({"op": "svd_wide_planes", "l": l, "sites": cnt, "M": N, "C": K, "wide_us": round(t1 * 1e6, 1),
+                              "sliced_us": round(t2 * 1e6, 1), "slices": -(-l // 16), "wide_TBps": round(byts / t1 / 1e12, 2),
+                              "wide_leads": bool(t1 < t2)}), flush=True)
+            del one, many, keep
+        for name, rows in (("dW F", [(p[0], p[1]) for p in planes]), ("dW^T Q", [(p[2], p[3]) for p in planes])):
+            one, many, keep = legs(rows, l)
+            t1, t2 = timeit(one, iters=args.iters, inner=5)[0], timeit(many, iters=args.iters, inner=5)[0]
+            byts = 4 * sum(N * K * c for (N, K), c in shapes)
+            print(json.dumps({"op": "svd_wide_planes_model", "pass": name, "l": l, "wide_us": round(t1 * 1e6, 1),
+                              "sliced_us": round(t2 * 1e6, 1), "plane_bytes": byts, "wide_TBps": round(byts / t1 / 1e12, 2),
+                              "wide_leads": bool(t1 < t2)}), flush=True)
+            del one, many, keep
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--what", default="merge,linear,ws,conv,hostops")
@@ -1087,3 +1144,5 @@ if __name__ == "__main__":
         bench_temb(a)
     if "gn" in a.what.split(","):
         bench_gn(a)
+    if "svdwide" in a.what.split(","):
+        bench_svd_wide(a)
