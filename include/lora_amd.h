@@ -174,6 +174,11 @@ int lora_amd_rank16_mfma_takes(int32_t op, const void *rows, int64_t ld, int64_t
  * on these arguments under the current settings of lora_amd_rank16_mfma AND lora_amd_colreduce_mfma.  x is inspected for
  * alignment only.  An entry of its own, so that lora_amd_rank16_mfma_takes answers for ops 0 and 1 what it always did. */
 int lora_amd_colreduce_mfma_takes(const void *x, int64_t ldx, int64_t M, int32_t K, int32_t r, int32_t x_dtype);
+/* The same for lora_amd_rank_update_rowscale (the launchers' op 1, no selector): 1 exactly when it would run the row-table
+ * form of the matrix-core rank update on these arguments under the current setting of lora_amd_rank16_mfma.  y is inspected
+ * for alignment only.  An entry of its own, so that lora_amd_rank16_mfma_takes keeps its answers. */
+int lora_amd_rank_update_rowscale_mfma_takes(const void *y, int64_t ldy, int64_t M, int32_t N, int32_t r, int32_t y_dtype,
+                                             int32_t factor_dtype);
 
 /* Tuning knobs of the planner/launcher (<= 0 keeps the current value):
  * target elements per tile and resident workgroups per CU (the LDS-slab kernel's grid cap).  blocks_per_cu >= 100
@@ -218,7 +223,11 @@ int lora_amd_rank_update(void *y, int64_t ldy, const float *t, const void *facto
 /* Per-sample multipliers (forward of a batch that carries one LoRA setting per sample): lora_amd_rank_update with row
  * m's T row multiplied by row_scale[((m / rows_per_sample) % nsel) * r + j] (f32 [nsel, r], device) before it meets F:
  * Y += scale * mask * (T o row_scale[sample]) @ F.  nsel >= 1, rows_per_sample >= 1, 1 <= r <= LORA_AMD_MAX_RANK.
- * Dropout as lora_amd_rank_update (offset given by value). */
+ * Dropout as lora_amd_rank_update (offset given by value).
+ * bf16 rows with f32 factors, 9 <= r <= 64, N % 8 == 0, 16-byte aligned rows (y, ldy % 8): the matrix-core form of
+ * lora_amd_rank_update with the multipliers applied in f32 as the T rows are staged, ahead of the (hi, lo) split (the table
+ * needs no alignment; an all-ones table gives lora_amd_rank_update's bits); anything else the VALU kernel.
+ * lora_amd_rank_update_rowscale_mfma_takes tells which. */
 int lora_amd_rank_update_rowscale(void *y, int64_t ldy, const float *t, const void *factor, int64_t M, int32_t N,
                                   int32_t r, int32_t y_dtype, int32_t factor_dtype, int32_t factor_layout, float scale,
                                   const float *row_scale, int32_t nsel, int64_t rows_per_sample, float dropout_p,

@@ -295,6 +295,7 @@ FUNCTIONS = (
     ("lora_amd_colreduce_mfma", cint, (i32,)),
     ("lora_amd_rank16_mfma_takes", cint, (i32, vp, i64, i64, i32, i32, i32, i32, i32)),
     ("lora_amd_colreduce_mfma_takes", cint, (vp, i64, i64, i32, i32, i32)),
+    ("lora_amd_rank_update_rowscale_mfma_takes", cint, (vp, i64, i64, i32, i32, i32, i32)),
     ("lora_amd_merge_set_tuning", cint, (i64, i64)),
     ("lora_amd_rowdot", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32, vp)),
     ("lora_amd_rank_update", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, f32, u64, u64, vp, vp)),
@@ -651,6 +652,15 @@ def rank16_mfma_takes(op: int, tensor: torch.Tensor, r: int, factor_dtype: torch
         return int(require().lora_amd_colreduce_mfma_takes(t.data_ptr(), t.stride(0), M, cols, int(r), dtype_code(t.dtype)))
     return int(require().lora_amd_rank16_mfma_takes(int(op), t.data_ptr(), t.stride(0), M, cols, int(r), dtype_code(t.dtype),
                                                     dtype_code(factor_dtype), int(bool(has_selector))))
+
+
+def rank_update_rowscale_takes(y: torch.Tensor, r: int, factor_dtype: torch.dtype = torch.float32) -> int:
+    """1 when ``rank_update_rowscale_`` of the 2-D ``y`` at rank ``r`` would run the row-table form of the matrix-core rank
+    update under the current hook setting (``lora_amd_rank_update_rowscale_mfma_takes``: host arithmetic, any device)."""
+    t = _as2d(y)
+    M, N = t.shape
+    return int(require().lora_amd_rank_update_rowscale_mfma_takes(t.data_ptr(), t.stride(0), M, N, int(r), dtype_code(t.dtype),
+                                                                  dtype_code(factor_dtype)))
 
 
 def merge_step_set_tuning(tile: int = -1, dither: int = -1) -> None:

@@ -759,6 +759,10 @@ extern "C" int lora_amd_rank_update_rowscale(void *y, int64_t ldy, const float *
   LORA_AMD_CHECK(dropout_p >= 0.f && dropout_p < 1.f, LORA_AMD_EINVAL, "rank_update_rowscale: dropout p=%f", dropout_p);
   hipStream_t st = (hipStream_t)stream;
   const bool drop = dropout_p > 0.f;
+  // ranks 9..64 on bf16 rows: the row-table form of the matrix-core kernel (csrc/rank16_mfma.hip; r16_takes op 1 decides)
+  if (r16_rank_update(y, ldy, t, 1, 0, factor, factor_dtype, factor_layout, M, N, r, y_dtype, scale, dropout_p, seed, offset,
+                      nullptr, st, row_scale, nsel, rows_per_sample))
+    return check_launch("lora_amd_rank_update_rowscale(mfma)");
   return by_dtype(y_dtype, [&](auto e) {
     using E = decltype(e);
     return drop ? launch_rank_update<E, true, true>(y, ldy, t, factor, M, N, r, factor_dtype, factor_layout, scale,

@@ -202,12 +202,18 @@ __global__ __launch_bounds__(1024) void rowdot16_mfma_kernel(
 // so the slices chain into the same two accumulators of a slab (slice 0 first: zero ranks beyond 16 change no bit of the
 // narrow kernel's result): Y is read, masked and written once.  A fragments ua[NS][2]; the T image holds NS fragment pairs
 // per slab, and the rows of a workgroup come down with it (kR16RuSlabs: at most 32 KB of LDS).
+// RSC (lora_amd_rank_update_rowscale, the row-table form): row m's T values are multiplied by
+// row_scale[((m / rps) % nsel) * r + j] as they are staged, after the partials are summed and before the (hi, lo) split —
+// where the VALU kernel applies the table.  The table row belongs to the ROW: one division per lane and slab, ahead of the
+// slices, in 32 bits when M < 2^31 (the launcher passes rps <= M then).  The table form fetches the eight multipliers and
+// eight T values of a whole chunk in one round trip.  Nothing after the staging knows about the table;
+// RSC = false is the code as it was (the three trailing arguments are never read).
 constexpr int kR16RuSlabs[5] = {0, 16, 8, 4, 4};  // 16-row slabs of a workgroup's T image per slice count
-template <class E, bool DROP, int NS = 1>
+template <class E, bool DROP, int NS = 1, bool RSC = false>
 __global__ __launch_bounds__(kR16Threads) void rank_update16_mfma_kernel(
     typename E::storage *__restrict__ y, int64_t ldy, const float *__restrict__ t, int nparts, int64_t part_stride,
     const float *__restrict__ f, int layout, int64_t M, int N, int r, int rows_per_block, float scale, float p, uint64_t seed,
-    uint64_t offset, const uint64_t *offset_dev) {
+    uint64_t offset, const uint64_t *offset_dev, const float *__restrict__ row_scale = nullptr, int nsel = 1, int64_t rps = 1) {
   __shared__ __attribute__((aligned(16))) mu32x4 s_t[kR16RuSlabs[NS] * NS * 2 * 64];  // [slab][slice][hi, lo][lane]: B operands
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, mm = lane & 15, q = lane >> 4;
   const int64_t m0 = (int64_t)blockIdx.x * rows_per_block;
@@ -218,6 +224,13 @@ __global__ __launch_bounds__(kR16Threads) void rank_update16_mfma_kernel(
   // B operands: T of the block's 16-row slabs, (hi | hi) and (lo | lo) along k
   for (int s = wave; s < nslabs; s += 4) {
     const int64_t row = m0 + s * 16 + mm;
+    const float *rs = row_scale;  // RSC: the table row of this lane's row, once for all slices
+    if constexpr (RSC) {
+      if (row < M) {
+        const int64_t smp = M <= 0x7fffffff ? (int64_t)(((uint32_t)row / (uint32_t)rps) % (uint32_t)nsel) : (row / rps) % nsel;
+        rs = row_scale + smp * r;
+      }
+    }
 #pragma unroll
     for (int sl = 0; sl < NS; ++sl) {
       float v[8];
@@ -225,11 +238,42 @@ __global__ __launch_bounds__(kR16Threads) void rank_update16_mfma_kernel(
       for (int e = 0; e < 8; ++e) v[e] = 0.f;
       if (row < M) {
         const int j0 = 16 * sl + 8 * (q & 1);
-        for (int pi = 0; pi < nparts; ++pi) {
-          const float *tp = t + pi * part_stride + row * r;
+        if constexpr (RSC) {
+          // a chunk of eight ranks that lies inside r whole (every chunk when r % 8 == 0) fetches its multipliers and its
+          // T values as sixteen unconditional loads at constant offsets from the lane's two row addresses: they issue
+          // back to back, one round trip per slice.  A load under `if (j < r)` is a branch with its own wait (the
+          // ragged chunk below, and the loop that RSC = false keeps as it is)
+          float mlt[8];
+          if (j0 + 8 <= r) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e)
-            if (j0 + e < r) v[e] += gl(tp)[j0 + e];
+            for (int e = 0; e < 8; ++e) mlt[e] = gl(rs)[j0 + e];
+            for (int pi = 0; pi < nparts; ++pi) {
+              const float *tp = t + pi * part_stride + row * r;
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] += gl(tp)[j0 + e];
+            }
+          } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              mlt[e] = 0.f;
+              if (j0 + e < r) mlt[e] = gl(rs)[j0 + e];
+            }
+            for (int pi = 0; pi < nparts; ++pi) {
+              const float *tp = t + pi * part_stride + row * r;
+#pragma unroll
+              for (int e = 0; e < 8; ++e)
+                if (j0 + e < r) v[e] += gl(tp)[j0 + e];
+            }
+          }
+#pragma unroll
+          for (int e = 0; e < 8; ++e) v[e] *= mlt[e];
+        } else {
+          for (int pi = 0; pi < nparts; ++pi) {
+            const float *tp = t + pi * part_stride + row * r;
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              if (j0 + e < r) v[e] += gl(tp)[j0 + e];
+          }
         }
       }
       mu32x4 hi, lo;
@@ -1107,17 +1151,22 @@ bool r16_rowdot(const void *x, int64_t ldx, const void *f, int fdt, int layout, 
 
 bool r16_rank_update(void *y, int64_t ldy, const float *t, int nparts, int64_t part_stride, const void *f, int fdt, int layout,
                      int64_t M, int N, int r, int act_dtype, float scale, float p, uint64_t seed, uint64_t offset,
-                     const uint64_t *offset_dev, hipStream_t st) {
+                     const uint64_t *offset_dev, hipStream_t st, const float *row_scale, int nsel, int64_t rps) {
   if (!r16_takes(1, y, ldy, M, N, r, act_dtype, fdt, false) || nparts < 1) return false;
   const int64_t ny = (N + 127) / 128;
   const int ns = (r + 15) / 16, rows = r16_ru_rows(M, ny, ns);
   const int64_t gx = (M + rows - 1) / rows;
   const float *ff = reinterpret_cast<const float *>(f);
+  // the row-table form: every row below M of rps >= M is sample 0, so rps <= M goes down — with M < 2^31 the kernel's
+  // row / rps is a 32-bit division
+  if (row_scale != nullptr) rps = std::min(rps, M);
   by_bool(p > 0.f, [&](auto d) {
-    by_int<1, 2, 3, 4>(ns, [&](auto n) {
-      hipLaunchKernelGGL((rank_update16_mfma_kernel<bf16_t, decltype(d)::value, decltype(n)::value>), dim3((unsigned)gx, (unsigned)ny),
-                         dim3(kR16Threads), 0, st, reinterpret_cast<bf16_t::storage *>(y), ldy, t, nparts, part_stride, ff, layout,
-                         M, N, r, rows, scale, p, seed, offset, offset_dev);
+    by_bool(row_scale != nullptr, [&](auto rsc) {
+      by_int<1, 2, 3, 4>(ns, [&](auto n) {
+        hipLaunchKernelGGL((rank_update16_mfma_kernel<bf16_t, decltype(d)::value, decltype(n)::value, decltype(rsc)::value>),
+                           dim3((unsigned)gx, (unsigned)ny), dim3(kR16Threads), 0, st, reinterpret_cast<bf16_t::storage *>(y), ldy, t,
+                           nparts, part_stride, ff, layout, M, N, r, rows, scale, p, seed, offset, offset_dev, row_scale, nsel, rps);
+      });
     });
   });
   return true;
@@ -1184,6 +1233,14 @@ extern "C" int lora_amd_colreduce_mfma(int32_t enable) {
 // for every op but 0 and 1, as it always has.
 extern "C" int lora_amd_colreduce_mfma_takes(const void *x, int64_t ldx, int64_t M, int32_t K, int32_t r, int32_t x_dtype) {
   return lora_amd::r16_takes(2, x, ldx, M, K, r, x_dtype, LORA_AMD_F32, false) ? 1 : 0;
+}
+
+// Pure host: 1 when lora_amd_rank_update_rowscale would run the row-table form of rank_update16_mfma_kernel on these arguments
+// under the current hook setting: r16_takes op 1 without a selector, what r16_rank_update itself decides by (no shape class is
+// held back: profiles/per_sample_mfma_kbench.txt).  An entry of its own, as lora_amd_colreduce_mfma_takes is.
+extern "C" int lora_amd_rank_update_rowscale_mfma_takes(const void *y, int64_t ldy, int64_t M, int32_t N, int32_t r,
+                                                        int32_t y_dtype, int32_t factor_dtype) {
+  return lora_amd::r16_takes(1, y, ldy, M, N, r, y_dtype, factor_dtype, false) ? 1 : 0;
 }
 
 // Pure host: 1 when lora_amd_rowdot[_masked] (op 0) / lora_amd_rank_update (op 1) would run the matrix-core form on these

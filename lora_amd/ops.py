@@ -1965,6 +1965,7 @@ def lora_conv_branch(x, y0, down_w, up_w, sel, stride, padding, dilation, groups
 #   * PS_RING: the LDS-ring kernel with the multiplier in its epilogue (lora_amd_linear_gemm_fwd_rowscale, one launch);
 #   * PS_LIB: library GEMM + rowdot (T, the module's selector if it keeps one) + lora_amd_rank_update_rowscale — any rank,
 #     dropout, the shapes the ring kernel refuses, and the channels-last conv sites (T from the 3x3 down-conv kernel).
+#     Ranks 9..64 on bf16 rows: both launches on the matrix cores (the rank update's row-table form).
 # NCHW conv sites: conv_down_fwd + lora_amd_conv_up_fwd_rowscale (the multiplier where the T planes are loaded).
 PS_LIB, PS_RING = 0, 1
 
@@ -2038,7 +2039,12 @@ def lora_linear_per_sample(x, weight, bias, down, up, sel, scale, dropout_p, row
         y = F.linear(x2, weight, bias)  # frozen dense GEMM (hipBLASLt)
         if not _C._rows_ok(y):
             y = y.contiguous()
-        t = rowdot_any(x2, down_c, _C.FACTOR_RK, 1.0, sel, False)
+        if sel is not None and _C.rank16_mfma_takes(0, x2, r, down_c.dtype):
+            # a selector inside the launch keeps the whole row product on the VALU kernel: where the matrix-core form takes
+            # the product without it, apply the [r, r] selector to the [M, r] result (what rowdot_any does past rank 64)
+            t = (rowdot_any(x2, down_c, _C.FACTOR_RK, 1.0) @ sel.float().t()).contiguous()
+        else:
+            t = rowdot_any(x2, down_c, _C.FACTOR_RK, 1.0, sel, False)
         seed, off = _ps_dropout(dropout_p)
         rank_update_rowscale_any_(y, t, up_c, _C.FACTOR_KR, scale, rows, rps, dropout_p, seed, off)
         _log("fwd", "ps_lib", M, K, N, r)

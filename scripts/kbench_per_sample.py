@@ -5,9 +5,16 @@
                  route (GEMM + rowdot + rank_update_rowscale), per SD1.5 shape at batch 8 (us per call, hipGraph-timed);
                  the NCHW conv up-projection with the multiplier inside (conv_up_fwd_rowscale) against a separate pass
                  over T followed by conv_up_fwd
+  --what rank_update  lora_amd_rank_update_rowscale at ranks 16 / 32 / 64, p = 0 / 0.1, on the eight shapes of DESIGN
+                 §3.4b's rank_update table (batch-8 rows per sample): the row-table form of the matrix-core kernel (hook
+                 on) against the VALU kernel (hook off), alternating, and the plain lora_amd_rank_update matrix-core
+                 launch of the same shape beside them; --what rank_update_near: the maskless launch on a grid of shapes
+                 around the one line of that table the VALU kernel wins
   --what unet    no-grad SD1.5 stand-in UNet forward at 512^2, bf16, batch 8 (CFG over 4 settings), reference-default
                  injection rank 4: (a) one scale for the batch (today's routes), (b) four per-sample alphas in one call,
-                 (c) four sequential batch-2 calls with tune_lora_scale (ms per batch of 8)
+                 (c) four sequential batch-2 calls with tune_lora_scale (ms per batch of 8).
+                 With --members 3 --rank 16: a LoRAManager of three rank-16 member files (joined rank 48) and four member
+                 mixes through tune_per_sample, hook on and off alternating in the one call
   --what trace   (b) alone, a few calls: the run to put under rocprofv3 --kernel-trace --stats
 """
 import argparse
@@ -73,6 +80,96 @@ def kernel(args):
         emit({"conv_up": [B, C, H, H], "r": r, "rowscale_inside_us": inside, "pass_then_conv_up_us": timeit(separate)[0] * 1e6})
 
 
+# (M, N) of DESIGN §3.4b's rank_update table: batch-8 rows of the 64x64 .. 8x8 maps and of the text tokens
+RU_SHAPES = [(9216, 320), (9216, 2560), (2304, 640), (2304, 5120), (576, 1280), (576, 10240), (144, 1280), (77, 1280)]
+
+
+def rank_update(args):
+    """lora_amd_rank_update_rowscale with the hook on (row-table form of the matrix-core kernel) and off (VALU kernel),
+    alternating, and the plain lora_amd_rank_update matrix-core launch of the same shape beside it."""
+    nsel = 4
+    for M, N in RU_SHAPES:
+        for r in (16, 32, 64):
+            for p in (0.0, 0.1):
+                y = torch.randn(M, N, device=DEV).to(torch.bfloat16)
+                t = torch.randn(M, r, device=DEV) * 1e-3
+                up = torch.randn(N, r, device=DEV) * 0.05
+                rows = torch.rand(nsel, r, device=DEV)
+                rps = max(M // 8, 1)
+                fns = {"mfma": lambda: _C.rank_update_rowscale_(y, t, up, _C.FACTOR_KR, 0.7, rows, rps, p, 5, 9),
+                       "valu": lambda: _C.rank_update_rowscale_(y, t, up, _C.FACTOR_KR, 0.7, rows, rps, p, 5, 9),
+                       "plain_mfma": lambda: _C.rank_update_(y, t, up, _C.FACTOR_KR, 0.7, p, 5, 9)}
+                takes = _C.rank_update_rowscale_takes(y, r)
+                meds = {k: [] for k in fns}
+                for _ in range(args.rounds):
+                    for tag, fn in fns.items():
+                        prev = _C.rank16_mfma(0 if tag == "valu" else 1)
+                        try:
+                            meds[tag].append(timeit(fn, args.reps)[0] * 1e6)
+                        finally:
+                            _C.rank16_mfma(prev)
+                res = {"M": M, "N": N, "r": r, "p": p, "rps": rps, "takes": takes}
+                for tag, v in meds.items():
+                    res[tag + "_us"] = round(min(v), 2)
+                    res[tag + "_rounds_us"] = [round(u, 2) for u in v]
+                res["valu_over_mfma"] = round(res["valu_us"] / res["mfma_us"], 2)
+                res["mfma_over_plain"] = round(res["mfma_us"] / res["plain_mfma_us"], 3)
+                emit(res)
+
+
+def rank_update_near(args):
+    """The maskless launch around the one line of --what rank_update that the VALU kernel wins (2304 x 5120, rank 32):
+    ranks 17 / 24 / 32 / 48 on a grid of row counts and widths, hook on / off twice each, alternating."""
+    for r in (17, 24, 32, 48):
+        for M in (1024, 2048, 2304, 4096, 8192):
+            for N in (2560, 5120, 10240):
+                y = torch.randn(M, N, device=DEV).to(torch.bfloat16)
+                t = torch.randn(M, r, device=DEV) * 1e-3
+                up = torch.randn(N, r, device=DEV) * 0.05
+                rows = torch.rand(4, r, device=DEV)
+                rps = max(M // 8, 1)
+                fn = lambda: _C.rank_update_rowscale_(y, t, up, _C.FACTOR_KR, 0.7, rows, rps)
+                res = {"M": M, "N": N, "r": r}
+                for tag, hook in (("mfma", 1), ("valu", 0), ("mfma2", 1), ("valu2", 0)):
+                    prev = _C.rank16_mfma(hook)
+                    try:
+                        res[tag] = round(timeit(fn, args.reps)[0] * 1e6, 2)
+                    finally:
+                        _C.rank16_mfma(prev)
+                res["valu_over_mfma"] = round(min(res["valu"], res["valu2"]) / min(res["mfma"], res["mfma2"]), 3)
+                emit(res)
+
+
+def build_joined(args):
+    """The stand-in UNet with a LoRAManager of ``args.members`` member files of rank ``args.rank`` each (written to a
+    temporary directory from freshly drawn factors): one joined adapter of rank members * rank per site."""
+    import tempfile
+    import types
+
+    from bench import build_unet
+    from lora_amd import trainer as T
+    from lora_amd.lora_manager import LoRAManager
+
+    torch.manual_seed(0)
+    unet = build_unet(torch.device(DEV), torch.bfloat16, seed=0)
+    unet.to(memory_format=torch.channels_last)
+    with tempfile.TemporaryDirectory() as tmp:
+        paths = []
+        L.inject_trainable_lora(unet, r=args.rank)
+        for i in range(args.members):
+            for up, down in L.extract_lora_ups_down(unet):
+                up.weight.data.normal_(0, 0.02)
+                down.weight.data.normal_(0, 1.0 / args.rank)
+            paths.append(os.path.join(tmp, f"member{i}.safetensors"))
+            L.save_safeloras({"unet": (unet, L.DEFAULT_TARGET_REPLACE)}, paths[-1])
+        L.monkeypatch_remove_lora(unet)
+        pipe = types.SimpleNamespace(unet=unet, text_encoder=torch.nn.Identity(), tokenizer=None)
+        mgr = LoRAManager(paths, pipe)
+    T.promote_lora_to_fp32(unet)
+    unet.eval()
+    return mgr, unet
+
+
 def build(args):
     from bench import build_unet
     from lora_amd import trainer as T
@@ -85,11 +182,15 @@ def build(args):
     for up, _ in L.extract_lora_ups_down(unet):
         up.weight.data.normal_(0, 0.02)
     unet.eval()
+    return (unet,) + inputs()
+
+
+def inputs():
     g = torch.Generator(device=DEV).manual_seed(1)
     x = torch.randn(8, 4, 64, 64, device=DEV, generator=g).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
     t = torch.full((8,), 500, device=DEV)
     ehs = torch.randn(8, 77, 768, device=DEV, generator=g).to(torch.bfloat16)
-    return unet, x, t, ehs
+    return x, t, ehs
 
 
 def time_ms(fn, reps):
@@ -109,7 +210,39 @@ def time_ms(fn, reps):
 
 
 @torch.no_grad()
+def unet_joined(args):
+    """Four member mixes through LoRAManager.tune_per_sample at joined rank members * rank: the per-sample rank update of
+    every site on the matrix cores (hook on) and on the VALU kernel (hook off), alternating in one call."""
+    mgr, net = build_joined(args)
+    x, t, ehs = inputs()
+    mixes = [[1.0] + [0.0] * (args.members - 1), [0.0] * (args.members - 1) + [1.0], [0.5] * args.members,
+             [1.5, 0.25] + [1.0] * (args.members - 2)]
+    mgr.tune_per_sample(mixes)
+    ops.PATH_LOG = log = []
+    net(x, t, ehs)
+    ops.PATH_LOG = None
+    routes = {}
+    for _, path, *_ in log:
+        routes[path] = routes.get(path, 0) + 1
+    res = {"on": [], "off": []}
+    for _ in range(args.rounds):
+        for tag, hook in (("on", 1), ("off", 0)):
+            prev = _C.rank16_mfma(hook)
+            try:
+                res[tag].append(time_ms(lambda: net(x, t, ehs), args.reps))
+            finally:
+                _C.rank16_mfma(prev)
+    on, off = min(m for m, _ in res["on"]), min(m for m, _ in res["off"])
+    emit({"metric": "SD1.5 stand-in UNet forward, 512^2, bf16, batch 8, no grad, LoRAManager.tune_per_sample of 4 mixes "
+                    "(ms, median / best per round)", "members": args.members, "member_rank": args.rank,
+          "joined_rank": args.members * args.rank, "routes": routes, "hook_on": res["on"], "hook_off": res["off"],
+          "hook_on_ms": on, "hook_off_ms": off, "off_over_on": off / on})
+
+
+@torch.no_grad()
 def unet(args):
+    if args.members > 1:
+        return unet_joined(args)
     net, x, t, ehs = build(args)
     alphas = [0.25, 0.5, 1.0, 1.5]
 
@@ -146,8 +279,12 @@ def trace(args):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", choices=["kernel", "unet", "trace"], default="kernel")
+    ap.add_argument("--what", choices=["kernel", "rank_update", "rank_update_near", "unet", "trace"], default="kernel")
     ap.add_argument("--rank", type=int, default=4)
+    ap.add_argument("--members", type=int, default=1,
+                    help="--what unet: > 1 joins that many member files of --rank through a LoRAManager")
+    ap.add_argument("--rounds", type=int, default=2, help="alternating hook-on / hook-off rounds of one call")
     ap.add_argument("--reps", type=int, default=10)
     a = ap.parse_args()
-    {"kernel": kernel, "unet": unet, "trace": trace}[a.what](a)
+    {"kernel": kernel, "rank_update": rank_update, "rank_update_near": rank_update_near, "unet": unet,
+     "trace": trace}[a.what](a)

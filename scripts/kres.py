@@ -36,4 +36,5 @@ if __name__ == "__main__":
             except OSError:
                 name = r["name"]
             print(f"{name[:110]:110s} vgpr {r.get('VGPRs')} agpr {r.get('AGPRs')} spill v{r.get('VGPRs Spill')} s{r.get('SGPRs Spill')} "
-                  f"lds {r.get('LDS Size [bytes/block]')} occ {r.get('Occupancy [waves/SIMD]')}")
+                  f"scratch {r.get('ScratchSize [bytes/lane]')} lds {r.get('LDS Size [bytes/block]')} "
+                  f"occ {r.get('Occupancy [waves/SIMD]')}")

@@ -231,6 +231,81 @@ def check_colreduce16():
     return True
 
 
+def rank_update16_rows(T, U, scale=1.0, row_scale=None, nsel=1, rps=1, m0=0):
+    """rank_update16_mfma_kernel on the rows m0 .. m0 + len(T) - 1 of one 32-column group, as a workgroup walks them: 16-row
+    slabs (the last one ragged), NS = ceil(r / 16) slices chained into the same two accumulators, T and U as hi + lo fragments
+    (k = 32 holds (hi | lo) of U's 16 ranks against T's hi twice, then T's lo twice).  T: [rows, r] f32 values, U: [32, r].
+    row_scale [nsel, r] (the row-table form, lora_amd_rank_update_rowscale): the lane of row m looks its table row
+    (m // rps) % nsel up ONCE per slab, and every slice multiplies its eight T values by that row's entries in f32 before the
+    split.  Returns scale * (T o row_scale[q]) U^T [rows, 32] (the accumulators in float64; `scale` is the epilogue's
+    multiplier, applied as f32)."""
+    rows, r = T.shape
+    ns = (r + 15) // 16
+    T32 = np.asarray(T, np.float32)
+    RS32 = None if row_scale is None else np.asarray(row_scale, np.float32)
+    ua = [[None, None] for _ in range(ns)]
+    for sl in range(ns):
+        for tile in range(2):
+            v = np.zeros((64, 8))
+            for l in range(64):
+                mm, q = l & 15, l >> 4
+                n = 8 * (mm >> 2) + 4 * tile + (mm & 3)
+                for e in range(8):
+                    j = 16 * sl + 8 * (q & 1) + e
+                    v[l][e] = U[n, j] if j < r else 0.0
+            hi, lo = split_hi_lo(v)
+            ua[sl][tile] = np.where((KQ < 2)[:, None], hi, lo)
+    out = np.zeros((rows, 32))
+    for s0 in range(0, rows, 16):
+        d = [np.zeros((64, 4)), np.zeros((64, 4))]
+        sample = [((m0 + s0 + mm) // rps) % nsel for mm in range(16)]   # per lane and slab, ahead of the slices
+        for sl in range(ns):
+            v = np.zeros((64, 8), np.float32)
+            for l in range(64):
+                mm, q = l & 15, l >> 4
+                if s0 + mm >= rows:
+                    continue
+                for e in range(8):
+                    j = 16 * sl + 8 * (q & 1) + e
+                    if j < r:
+                        v[l][e] = T32[s0 + mm, j]
+                        if RS32 is not None:
+                            v[l][e] = np.float32(v[l][e] * RS32[sample[mm], j])
+            th, tl = split_hi_lo(v)
+            for tile in range(2):
+                d[tile] = mfma(ua[sl][tile], th, d[tile])
+                d[tile] = mfma(ua[sl][tile], tl, d[tile])
+        for l in range(64):
+            mm, q = l & 15, l >> 4
+            if s0 + mm < rows:
+                out[s0 + mm, 8 * q:8 * q + 4] = d[0][l]
+                out[s0 + mm, 8 * q + 4:8 * q + 8] = d[1][l]
+    return np.float64(np.float32(scale)) * out
+
+
+def check_rank_update16_rows():
+    """the wide and the row-table staging against float64 (hi + lo on both operands: the 2^-15 of check_colreduce16), and
+    the two bit rules of the table: all ones -> the plain form's bits; a constant power of two c per sample -> the plain
+    form at scale c on that sample's rows"""
+    rng = np.random.default_rng(2)
+    for r, rows, nsel, rps, m0 in ((9, 16, 2, 5, 0), (17, 23, 3, 7, 64), (64, 40, 2, 13, 128)):
+        T = rng.standard_normal((rows, r)).astype(np.float32)
+        U = rng.standard_normal((32, r)).astype(np.float32).astype(np.float64)
+        RS = (rng.random((nsel, r)) * 2 - 0.5).astype(np.float32)
+        q = ((m0 + np.arange(rows)) // rps) % nsel
+        TS = T.astype(np.float64) * RS.astype(np.float64)[q]
+        got = rank_update16_rows(T, U, 0.75, RS, nsel, rps, m0)
+        assert np.all(np.abs(got - 0.75 * TS @ U.T) <= 2.0 ** -15 * 0.75 * (np.abs(TS) @ np.abs(U).T))
+        plain = rank_update16_rows(T, U, 0.75)
+        assert np.all(np.abs(plain - 0.75 * T.astype(np.float64) @ U.T) <= 2.0 ** -15 * 0.75 * (np.abs(T) @ np.abs(U).T))
+        assert np.array_equal(rank_update16_rows(T, U, 0.75, np.ones((nsel, r)), nsel, rps, m0), plain)
+        c = np.array([2.0, 0.5, 1.0])[:nsel]
+        got = rank_update16_rows(T, U, 0.75, np.repeat(c[:, None], r, 1), nsel, rps, m0)
+        for k in range(nsel):
+            assert np.array_equal(got[q == k], rank_update16_rows(T, U, 0.75 * c[k])[q == k])
+    return True
+
+
 def check():
     rng = np.random.default_rng(0)
     for r in (16, 12, 9):
@@ -247,4 +322,4 @@ def check():
 
 
 if __name__ == "__main__":
-    print("ok" if check() and check_colreduce16() else "mismatch")
+    print("ok" if check() and check_colreduce16() and check_rank_update16_rows() else "mismatch")
