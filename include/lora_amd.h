@@ -934,9 +934,11 @@ typedef struct lora_amd_adamw_group {
 } lora_amd_adamw_group;
 
 /* One fused pass over the flat buffers.  clip coefficient is computed on the
- * device from sumsq[0]: c = min(1, max_norm / (sqrt(sumsq) + 1e-6))
- * (torch.nn.utils.clip_grad_norm_); max_norm <= 0 disables clipping.
- * grad_scale multiplies g before clipping (1/world_size after a SUM all-reduce).
+ * device from sumsq[0] = sum(g^2) of the gradient as stored:
+ *   c = min(1, max_norm / (|grad_scale| * sqrt(sumsq) + 1e-6))
+ * (torch.nn.utils.clip_grad_norm_ of grad_scale * g, the reference's reduce ->
+ * average -> clip order); max_norm <= 0 disables clipping.  The update uses
+ * grad_scale * c * g (grad_scale = 1/world_size after a SUM all-reduce).
  * `step` is the 1-based optimiser step (bias correction).  zero_grad != 0
  * writes zeros back to g (optimizer.zero_grad, train_lora_dreambooth.py:888). */
 int lora_amd_clip_adamw(float *p, float *g, float *exp_avg, float *exp_avg_sq,

@@ -1101,6 +1101,8 @@ def sumsq(g: torch.Tensor, out: torch.Tensor, ws: Optional[torch.Tensor] = None)
     _dev_check(g, out)
     if g.dtype != torch.float32 or not g.is_contiguous() or out.dtype != torch.float32:
         raise ValueError("sumsq: contiguous f32 tensors expected")
+    if g.data_ptr() % 16:  # the kernel reads float4; the launcher refuses too (LORA_AMD_EINVAL)
+        raise ValueError("sumsq: g must be 16-byte aligned")
     nbytes = lib.lora_amd_sumsq_workspace(g.numel())
     if ws is None:
         ws = torch.empty(nbytes // 4, dtype=torch.float32, device=g.device)
@@ -2207,10 +2209,12 @@ def ti_rows_step(table: torch.Tensor, table_grad: torch.Tensor, ids: torch.Tenso
                  grad_scale: float = 1.0, decay_lambda: float = -1.0, target_norm: float = 0.4) -> None:
     """Placeholder-row AdamW + norm decay + scatter in one launch (see include/lora_amd.h)."""
     _dev_check(table, table_grad, ids, rows, m, v)
-    if not (table.is_contiguous() and table_grad.is_contiguous() and rows.is_contiguous()):
+    if not all(t.is_contiguous() for t in (table, table_grad, ids, rows, m, v)):
         raise ValueError("ti_rows_step: contiguous tensors expected")
     if ids.dtype != torch.int64 or rows.dtype != torch.float32 or table_grad.dtype != table.dtype:
         raise ValueError("ti_rows_step: ids int64, rows f32, grad in the table's dtype expected")
+    if m.dtype != torch.float32 or v.dtype != torch.float32 or m.shape != rows.shape or v.shape != rows.shape:
+        raise ValueError("ti_rows_step: Adam moments must be f32 tensors of the rows' shape")
     _check(require().lora_amd_ti_rows_step(table.data_ptr(), table_grad.data_ptr(), ids.data_ptr(), ids.numel(),
                                            table.shape[1], dtype_code(table.dtype), rows.data_ptr(), m.data_ptr(),
                                            v.data_ptr(), float(lr), float(betas[0]), float(betas[1]), float(eps),

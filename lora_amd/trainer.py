@@ -73,6 +73,7 @@ class FlatLoraState:
             self._ws = torch.empty(1024, dtype=torch.float32, device=self.device)
             self._groups_dev = _C.make_adamw_groups(self._group_rows(), self.device)
             self._step_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self._dev_steps: Optional[int] = 0  # host's knowledge of _step_dev, see _sync_step_counter()
         self.scaler: Optional[torch.Tensor] = None  # fp16 loss-scaling state, see enable_loss_scaling()
         self._scaler_cfg = (2.0, 0.5, 2000)
         # DDP broadcasts the parameters of rank 0 when it wraps the model (the reference's accelerator.prepare,
@@ -177,14 +178,54 @@ class FlatLoraState:
             return 1.0 / dist.get_world_size()
         return 1.0
 
+    def _sync_step_counter(self, graph_safe: bool) -> None:
+        """Keep the host's ``step_count`` and the device counter of the ``graph_safe`` form telling the same number of
+        applied steps (no loss scaling; see ``step``).  ``_dev_steps``: what the device counter holds as far as the host
+        knows, None once a captured graph owns it.  Costs the ``graph_safe=False`` path one comparison."""
+        if not graph_safe:
+            if self._dev_steps is None:
+                raise RuntimeError("FlatLoraState.step: a graph_safe step was captured into a graph, whose replays advance "
+                                   "the device step counter only; the host step count is stale, so step with "
+                                   "graph_safe=True from here on")
+            return
+        if torch.cuda.is_current_stream_capturing():
+            if self._dev_steps is not None and self._dev_steps != self.step_count:
+                raise RuntimeError(f"FlatLoraState.step: capturing a graph_safe step after {self.step_count} applied steps "
+                                   f"while the device step counter holds {self._dev_steps}; run one step with "
+                                   "graph_safe=True outside capture (the warm-up) first")
+            self._dev_steps = None
+        elif self._dev_steps is not None:
+            if self._dev_steps != self.step_count:  # graph_safe=False steps went by: they never touch the device counter
+                self._step_dev.fill_(self.step_count)
+            self._dev_steps = self.step_count + 1
+
     def step(self, grad_scale: float = 1.0, graph_safe: bool = False) -> None:
-        """clip_grad_norm_(max_grad_norm) -> AdamW -> zero_grad over the flat buffers (ref :878-888)."""
+        """clip_grad_norm_(max_grad_norm) -> AdamW -> zero_grad over the flat buffers (ref :878-888).
+
+        Where the step number of the bias correction comes from (device tensors):
+
+        * ``graph_safe=False`` without loss scaling: the host's ``step_count``, passed by value.  No launch and no
+          synchronisation beyond ``sumsq`` + ``clip_adamw``.
+        * ``graph_safe=True``: a device counter that one extra launch advances, so that the launches are the same from
+          step to step and the call can be captured into a hipGraph and replayed.  Issued outside capture after
+          ``graph_safe=False`` steps, the call first seeds the counter with the number of steps applied so far: the two
+          forms may be mixed freely as long as nothing was captured.
+        * Capturing a ``graph_safe=True`` step hands the counter to the graph: replays advance it where the host cannot
+          see it without a synchronisation.  The counter must hold the applied steps at that point, which is so for a
+          fresh state and after a ``graph_safe=True`` warm-up step; otherwise the capture raises ``RuntimeError``.
+          From then on every step must be ``graph_safe=True`` (a replay or an eager call, both read the device
+          counter); a ``graph_safe=False`` step raises ``RuntimeError`` instead of stepping with a stale host count.
+        * With loss scaling (``enable_loss_scaling``) the device counter is used in every form, since only the device
+          knows whether a step was applied; the forms mix freely.
+        """
         self.reduce_pending()
-        self.step_count += 1
         b1, b2 = self.betas
         if self.on_device:
             clip = self.max_grad_norm if self.max_grad_norm and self.max_grad_norm > 0 else 0.0
             scaling = self.scaler is not None
+            if not scaling:
+                self._sync_step_counter(graph_safe)
+            self.step_count += 1
             if clip > 0 or scaling:
                 _C.sumsq(self.flat_g, self._sumsq, self._ws)
             if scaling:  # finite check, un-scale factor, scale adaptation; the step counter advances only if applied
@@ -202,6 +243,7 @@ class FlatLoraState:
                           b1, b2, self.eps, step, True, scaler=self.scaler)
             return
         # CPU plumbing path (same maths as csrc/optim.hip)
+        self.step_count += 1
         if self.scaler is not None:
             growth, backoff, interval = self._scaler_cfg
             scale = float(self.scaler[0])
