@@ -1017,6 +1017,26 @@ int lora_amd_groupnorm_nhwc_bwd(const void *x, const void *gout, const void *gam
  * under the current setting, 0 for streaming, LORA_AMD_EINVAL for a geometry the entry points refuse. */
 int lora_amd_groupnorm_nhwc_resident(int32_t enable);
 int lora_amd_groupnorm_nhwc_route(int32_t B, int32_t C, int32_t HW, int32_t groups, int32_t dtype, int32_t backward);
+/* The backward with a second gradient: dx = rn(rn(d groupnorm / d x) + gsum), rn = rounding to the activation dtype, i.e. the
+ * bits of lora_amd_groupnorm_nhwc_bwd followed by a separate add of gsum (the gradient that reaches x past the norm: the
+ * shortcut of a ResnetBlock2D, the closing residual of a Transformer2DModel).  gsum is [B * HW] rows of C channels, ld_gsum
+ * elements apart (ld_gsum = C: dx's layout; larger: a channel slice of a wider channels_last gradient, as the backward of a
+ * concatenation hands it out; a multiple of 8), aligned like dx, and may be dx itself; NULL: exactly
+ * lora_amd_groupnorm_nhwc_bwd.  The statistics launches are the same; the resident
+ * launch holds one operand more in registers, so fewer geometries fit it: lora_amd_groupnorm_nhwc_route_add answers
+ * like lora_amd_groupnorm_nhwc_route (backward) for a call with gsum given. */
+int lora_amd_groupnorm_nhwc_bwd_add(const void *x, const void *gout, const void *gsum, int64_t ld_gsum, const void *gamma,
+                                    const float *aff, void *dx, void *workspace, size_t workspace_bytes, int32_t B,
+                                    int32_t C, int32_t HW, int32_t groups, int32_t act, int32_t dtype, void *stream);
+int lora_amd_groupnorm_nhwc_route_add(int32_t B, int32_t C, int32_t HW, int32_t groups, int32_t dtype);
+
+/* The tail of a ResnetBlock2D in one launch, on dense channels_last rows ([rows][C], C % 8 == 0, row strides in elements,
+ * multiples of 8): out = rn(rn(h + b2) + (bs ? rn(r + bs) : r)) with rn = rounding to the activation dtype, the bits of
+ * "conv2 bias add, conv_shortcut bias add, shortcut + h" as three separate adds.  h = conv2 output without bias, r = the
+ * block input or the conv_shortcut output without bias, b2 / bs [C] in the activation dtype (bs NULL: r is taken as it
+ * is).  out may be h or r.  Pointers 16-byte (f32: 32-byte) aligned. */
+int lora_amd_resnet_tail(const void *h, int64_t ldh, const void *r, int64_t ldr, const void *b2, const void *bs,
+                         void *out, int64_t ldo, int64_t rows, int32_t C, int32_t dtype, void *stream);
 
 /* The per-(sample, channel) term every ResnetBlock2D adds in front of its norm2, for all blocks in ONE launch:
  *   out[out_offset + b * N + n] = float(rn(rn(dot(silu(temb[b]), weight[n]) + bias[n]) + conv_bias[n]))

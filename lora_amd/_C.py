@@ -407,6 +407,9 @@ FUNCTIONS = (
     ("lora_amd_groupnorm_nhwc_bwd", cint, (vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp)),
     ("lora_amd_groupnorm_nhwc_resident", cint, (i32,)),
     ("lora_amd_groupnorm_nhwc_route", cint, (i32, i32, i32, i32, i32, i32)),
+    ("lora_amd_groupnorm_nhwc_bwd_add", cint, (vp, vp, vp, i64, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_groupnorm_nhwc_route_add", cint, (i32, i32, i32, i32, i32)),
+    ("lora_amd_resnet_tail", cint, (vp, i64, vp, i64, vp, vp, vp, i64, i64, i32, i32, vp)),
     ("lora_amd_temb_addends_supported", cint, (i32, i32, i32)),
     ("lora_amd_temb_addends", cint, (vp, i32, i64, vp, vp, i32, i32, i32, vp)),
     ("lora_amd_layernorm_supported", cint, (i32,)),
@@ -2367,17 +2370,28 @@ def groupnorm_nhwc_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
 
 
 def groupnorm_nhwc_bwd(x: torch.Tensor, gout: torch.Tensor, gamma: torch.Tensor, aff: torch.Tensor, groups: int,
-                       act: bool) -> torch.Tensor:
-    _dev_check(x, gout, gamma, aff)
+                       act: bool, gsum: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dx of the channels_last GroupNorm; ``gsum`` (x's shape and dtype, dense channels_last rows: ``gsum_takes``): a second
+    gradient of x, added to the rounded dx inside the launch that writes it (the bits of ``groupnorm_nhwc_bwd(...) + gsum``)."""
+    _dev_check(x, gout, gamma, aff, gsum)
     B, C_ = x.shape[0], x.shape[1]
     HW = x.numel() // (B * C_)
     nbytes = groupnorm_nhwc_workspace(B, C_, HW, groups)
     dx = torch.empty_like(x)
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-    _check(require().lora_amd_groupnorm_nhwc_bwd(x.data_ptr(), gout.data_ptr(), gamma.data_ptr(), aff.data_ptr(),
-                                                 dx.data_ptr(), ws.data_ptr(), nbytes, B, C_, HW, groups,
-                                                 1 if act else 0, dtype_code(x.dtype), _stream()),
-           "lora_amd_groupnorm_nhwc_bwd")
+    if gsum is None:
+        _check(require().lora_amd_groupnorm_nhwc_bwd(x.data_ptr(), gout.data_ptr(), gamma.data_ptr(), aff.data_ptr(),
+                                                     dx.data_ptr(), ws.data_ptr(), nbytes, B, C_, HW, groups,
+                                                     1 if act else 0, dtype_code(x.dtype), _stream()),
+               "lora_amd_groupnorm_nhwc_bwd")
+        return dx
+    if not gsum_takes(x, gsum):
+        raise ValueError("groupnorm_nhwc_bwd: gsum must have x's shape and dtype, in aligned channels_last rows")
+    _check(require().lora_amd_groupnorm_nhwc_bwd_add(x.data_ptr(), gout.data_ptr(), gsum.data_ptr(), _nhwc_rows(gsum),
+                                                     gamma.data_ptr(),
+                                                     aff.data_ptr(), dx.data_ptr(), ws.data_ptr(), nbytes, B, C_, HW,
+                                                     groups, 1 if act else 0, dtype_code(x.dtype), _stream()),
+           "lora_amd_groupnorm_nhwc_bwd_add")
     return dx
 
 
@@ -2392,6 +2406,58 @@ def groupnorm_nhwc_route(B: int, C_: int, HW: int, groups: int, dtype: torch.dty
     if rc < 0:
         _check(rc, "lora_amd_groupnorm_nhwc_route")
     return rc == 1
+
+
+def groupnorm_nhwc_route_add(B: int, C_: int, HW: int, groups: int, dtype: torch.dtype) -> bool:
+    """``groupnorm_nhwc_route`` of a backward call that is given ``gsum``."""
+    rc = int(require().lora_amd_groupnorm_nhwc_route_add(B, C_, HW, groups, dtype_code(dtype)))
+    if rc < 0:
+        _check(rc, "lora_amd_groupnorm_nhwc_route_add")
+    return rc == 1
+
+
+def _nhwc_rows(t: torch.Tensor) -> Optional[int]:
+    """Row stride (elements) of a [B, C, H, W] tensor whose memory is dense [B*H*W] rows of C channels, else None."""
+    B, C_, H, W = t.shape
+    ld = t.stride(3) if W > 1 else (t.stride(2) if H > 1 else (t.stride(0) if B > 1 else C_))
+    want = (H * W * ld, 1, W * ld, ld)
+    ok = all(n == 1 or s == w for n, s, w in zip(t.shape, t.stride(), want))
+    return ld if ok and ld >= C_ and ld % 8 == 0 else None
+
+
+def gsum_takes(x: torch.Tensor, gsum: torch.Tensor) -> bool:
+    """``groupnorm_nhwc_bwd`` takes ``gsum`` next to a channels_last ``x``: same shape, dtype and device, dense rows of C
+    channels (x's own layout, or a channel slice of a wider channels_last tensor), aligned like x."""
+    return (gsum.shape == x.shape and gsum.dtype == x.dtype and gsum.device == x.device
+            and gsum.data_ptr() % (32 if x.dtype == torch.float32 else 16) == 0 and _nhwc_rows(gsum) is not None)
+
+
+def resnet_tail_supported(h: torch.Tensor, r: torch.Tensor, b2: torch.Tensor, bs: Optional[torch.Tensor]) -> bool:
+    """``resnet_tail`` takes these tensors: one device and dtype, C % 8 == 0, dense channels_last rows, aligned pointers."""
+    if not (h.is_cuda and h.dim() == 4 and h.shape == r.shape and h.dtype in _DT and h.numel() > 0
+            and h.shape[1] % 8 == 0):
+        return False
+    al = 32 if h.dtype == torch.float32 else 16
+    for t in (h, r, b2, bs):
+        if t is not None and (t.dtype != h.dtype or t.device != h.device or t.data_ptr() % al):
+            return False
+    if any(b is not None and (b.dim() != 1 or b.shape[0] != h.shape[1] or not b.is_contiguous()) for b in (b2, bs)):
+        return False
+    return _nhwc_rows(h) is not None and _nhwc_rows(r) is not None
+
+
+def resnet_tail(h: torch.Tensor, r: torch.Tensor, b2: torch.Tensor, bs: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``(h + b2[None, :, None, None]) + (r + bs[None, :, None, None])`` (``bs`` None: ``+ r``) on channels_last rows in
+    one launch, rounded to the activation dtype after each of the three adds; returns a channels_last tensor."""
+    _dev_check(h, r, b2, bs)
+    if not resnet_tail_supported(h, r, b2, bs):
+        raise ValueError("resnet_tail: tensors must be channels_last rows of one dtype, C % 8 == 0, 16-byte aligned")
+    B, C_, H, W = h.shape
+    out = torch.empty((B, C_, H, W), dtype=h.dtype, device=h.device, memory_format=torch.channels_last)
+    _check(require().lora_amd_resnet_tail(h.data_ptr(), _nhwc_rows(h), r.data_ptr(), _nhwc_rows(r), b2.data_ptr(),
+                                          _ptr(bs), out.data_ptr(), C_, B * H * W, C_, dtype_code(h.dtype), _stream()),
+           "lora_amd_resnet_tail")
+    return out
 
 
 # ----------------------------------------------------------------------------- time-embedding addends (hostops.hip)

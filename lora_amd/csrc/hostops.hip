@@ -8,6 +8,9 @@
 //                        Here: NCHW 2 launches each way (slice statistics, apply), only x and [B,G] (mean, rstd) kept;
 //                        channels_last 3 each way (statistics, finalize, apply), or ONE where a bundle of groups fits in
 //                        a workgroup's registers (maps up to 32x32); only x and the per-channel aff [B,4,C] kept.
+//                        The channels_last backward takes a second gradient of x (gsum: the shortcut of a ResnetBlock2D, the
+//                        closing residual of a Transformer2DModel) and adds it in the launch that writes dx.
+//   ResnetBlock2D tail   conv2 bias, conv_shortcut bias and shortcut + h: three ATen adds -> one launch with their roundings.
 //   GEGLU gate           GEGLU.forward right behind the adapted `proj` (lora_diffusion/lora.py:14 targets GEGLU):
 //                        h * gelu(gate): ATen = chunk, gelu, mul (5 tensor passes) forward and
 //                        gelu_backward, 2 mul, cat (13 passes) backward.  Here: one launch each way (3 / 5 passes);
@@ -795,6 +798,20 @@ __global__ __launch_bounds__(kHT) void gn_nhwc_apply_kernel(const typename E::st
   }
 }
 
+// a + b as its own rounded operation: never contracted with a product that made a or b
+__device__ inline float add_alone(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+// o = rn(o) + g, to be rounded once more by the store: what a separate add of g behind the stored o gives
+template <class E>
+__device__ inline void add_rounded8(float (&o)[8], const Raw8<E> &g) {
+  float gv[8];
+  unpack8_sel<E>(g, true, gv);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = add_alone(round_to<E>(o[e]), gv[e]);
+}
+
 // backward: t = gamma * dz, xh = (x - mean) * rstd;  per channel and pixel slice: sum t, sum t*xh
 template <class E, bool ACT>
 __device__ inline void gn_nhwc_terms(const float (&v)[8], const float (&go)[8], const float (&ga)[8],
@@ -809,15 +826,20 @@ __device__ inline void gn_nhwc_terms(const float (&v)[8], const float (&go)[8], 
   }
 }
 
-template <class E, bool ACT, bool APPLY>
+// ADD (with APPLY): gsum, a second gradient of x as [B * HW] rows of C channels ldg elements apart (dx's layout when
+// ldg = C; a channel slice of a wider gradient otherwise), is loaded next to x and gout and added to the rounded dx (the bits
+// of a separate add behind this launch); gsum may be dx itself, each chunk is read before it is written.
+template <class E, bool ACT, bool APPLY, bool ADD = false>
 __global__ __launch_bounds__(kHT) void gn_nhwc_bwd_kernel(const typename E::storage *__restrict__ x,
                                                           const typename E::storage *__restrict__ gout,
+                                                          const typename E::storage *gsum, int64_t ldg,
                                                           const typename E::storage *__restrict__ gamma,
                                                           const float *__restrict__ aff,
                                                           float *__restrict__ part,        // !APPLY: out [B][S][2][C]
                                                           const float *__restrict__ cvec,  // APPLY: [B][2][C] = c1, c2
-                                                          typename E::storage *__restrict__ dx, int C, int HW, int cw,
+                                                          typename E::storage *dx, int C, int HW, int cw,
                                                           int tiles, int nslots, int px, int S) {
+  static_assert(APPLY || !ADD, "the statistics pass has no second gradient");
   __shared__ __attribute__((aligned(16))) float s_red[APPLY ? 8 : 2 * kHT * 8];
   const NhwcBlock k = nhwc_block(C, HW, cw, tiles, nslots, px, S);
   float ga[8], be[8], mean[8], rstd[8], gam[8], c1[8], c2[8], s1[8], s2[8];
@@ -834,14 +856,16 @@ __global__ __launch_bounds__(kHT) void gn_nhwc_bwd_kernel(const typename E::stor
       ld8f(cvec + (int64_t)k.b * 2 * C + (int64_t)k.col * 8, c1);
       ld8f(cvec + (int64_t)k.b * 2 * C + C + (int64_t)k.col * 8, c2);
     }
+    const int64_t gbase = ((int64_t)k.b * HW + (int64_t)k.s * px) * ldg + (int64_t)k.col * 8;
     for (int p = k.slot; p < k.np; p += nslots * kNU) {
-      Raw8<E> xr[kNU], gr[kNU];
+      Raw8<E> xr[kNU], gr[kNU], sr[ADD ? kNU : 1];
 #pragma unroll
       for (int u = 0; u < kNU; ++u) {
         const int pp = p + u * nslots;
         const int64_t off = k.base + (int64_t)(pp < k.np ? pp : p) * C;
         xr[u] = load8_raw<E>(x + off);
         gr[u] = load8_raw<E>(gout + off);
+        if (ADD) sr[u] = load8_raw<E>(gsum + gbase + (int64_t)(pp < k.np ? pp : p) * ldg);
       }
       LORA_AMD_LOADS_ISSUED();
 #pragma unroll
@@ -856,6 +880,7 @@ __global__ __launch_bounds__(kHT) void gn_nhwc_bwd_kernel(const typename E::stor
             float o[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = rstd[e] * (t[e] - c1[e] - xh[e] * c2[e]);
+            if (ADD) add_rounded8<E>(o, sr[u]);
             store8<E>(dx + k.base + (int64_t)pp * C, o);
           } else {
 #pragma unroll
@@ -1095,23 +1120,28 @@ __global__ __launch_bounds__(T) void gn_nhwc_res_fwd_kernel(const typename E::st
   }
 }
 
-template <class E, bool ACT, int T, int NP>
+// ADD: as in gn_nhwc_bwd_kernel (gsum rows ldg elements apart); the gsum chunks are a third raw operand, loaded with the
+// other two.
+template <class E, bool ACT, int T, int NP, bool ADD = false>
 __global__ __launch_bounds__(T) void gn_nhwc_res_bwd_kernel(const typename E::storage *__restrict__ x,
                                                             const typename E::storage *__restrict__ gout,
+                                                            const typename E::storage *gsum, int64_t ldg,
                                                             const typename E::storage *__restrict__ gamma,
                                                             const float *__restrict__ aff,
-                                                            typename E::storage *__restrict__ dx, int C, int HW, int cpg,
+                                                            typename E::storage *dx, int C, int HW, int cpg,
                                                             int nch, int nslots) {
   __shared__ __attribute__((aligned(16))) ResLds<T, 2> l;
   __shared__ float gs[2][kResMaxGroups];
   const ResBlock k = res_block(C, HW, cpg, nch, nslots);
-  Raw8<E> xr[NP], gr[NP];
+  Raw8<E> xr[NP], gr[NP], sr[ADD ? NP : 1];
 #pragma unroll
   for (int u = 0; u < NP; ++u) {
     const int p = k.slot + u * nslots;
-    const int64_t off = k.base + (int64_t)(k.active && p < HW ? p : 0) * C;
+    const int pc = k.active && p < HW ? p : 0;
+    const int64_t off = k.base + (int64_t)pc * C;
     xr[u] = load8_raw<E>(x + off);
     gr[u] = load8_raw<E>(gout + off);
+    if (ADD) sr[u] = load8_raw<E>(gsum + ((int64_t)k.b * HW + pc) * ldg + (int64_t)k.col * 8);
   }
   float ga[8], be[8], mean[8], rstd[8], gam[8];
   const float *ab = aff + (int64_t)k.b * 4 * C + (int64_t)k.col * 8;
@@ -1157,7 +1187,58 @@ __global__ __launch_bounds__(T) void gn_nhwc_res_bwd_kernel(const typename E::st
       gn_nhwc_terms<E, ACT>(v, go, ga, be, mean, rstd, gam, t, xh);
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = rstd[e] * (t[e] - c1[e] - xh[e] * c2[e]);
+      if (ADD) add_rounded8<E>(o, sr[u]);
       store8<E>(dx + k.base + (int64_t)p * C, o);
+    }
+  }
+}
+
+// ---- tail of a ResnetBlock2D: both convolution biases and the residual add in one pass ---------------------------------
+// out = rn(rn(h + b2) + (bs ? rn(r + bs) : r)) on dense channels_last rows: the three ATen adds behind conv2 and
+// conv_shortcut (two strided bias adds, one vectorised add), rounded where they round.  Column-owner mapping as above: a
+// thread keeps one 16-byte channel chunk (its bias chunks are loaded once) and walks rows, kNU in flight.
+template <class E, bool SB>
+__global__ __launch_bounds__(kHT) void resnet_tail_kernel(const typename E::storage *h, int64_t ldh,
+                                                          const typename E::storage *r, int64_t ldr,
+                                                          const typename E::storage *__restrict__ b2,
+                                                          const typename E::storage *__restrict__ bs,
+                                                          typename E::storage *out, int64_t ldo, int64_t rows, int c8,
+                                                          int cw, int tiles, int nslots, int rpb) {
+  const int64_t blk = blockIdx.x / tiles;
+  const int tile = (int)(blockIdx.x - blk * tiles);
+  const int slot = threadIdx.x / cw, cl = threadIdx.x - slot * cw;
+  if (slot >= nslots) return;
+  const int64_t col = ((int64_t)tile * cw + cl) * 8;
+  const int64_t r0 = blk * rpb;
+  const int np = (int)min((int64_t)rpb, rows - r0);
+  float bv2[8], bvs[8];
+  unpack8_sel<E>(load8_raw<E>(b2 + col), true, bv2);
+  unpack8_sel<E>(load8_raw<E>(SB ? bs + col : b2 + col), SB, bvs);
+  for (int p = slot; p < np; p += nslots * kNU) {
+    Raw8<E> hr[kNU], rr[kNU];
+#pragma unroll
+    for (int u = 0; u < kNU; ++u) {
+      const int pp = p + u * nslots;
+      const int64_t row = r0 + (pp < np ? pp : p);
+      hr[u] = load8_raw<E>(h + row * ldh + col);
+      rr[u] = load8_raw<E>(r + row * ldr + col);
+    }
+    LORA_AMD_LOADS_ISSUED();
+#pragma unroll
+    for (int u = 0; u < kNU; ++u) {
+      const int pp = p + u * nslots;
+      if (pp < np) {
+        float hv[8], rv[8], o[8];
+        unpack8_sel<E>(hr[u], true, hv);
+        unpack8_sel<E>(rr[u], true, rv);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float a = round_to<E>(hv[e] + bv2[e]);
+          const float b = SB ? round_to<E>(rv[e] + bvs[e]) : rv[e];
+          o[e] = a + b;
+        }
+        store8<E>(out + (r0 + pp) * ldo + col, o);
+      }
     }
   }
 }
@@ -1468,12 +1549,16 @@ constexpr GnResForm kResForms[] = {{256, 2}, {512, 4}, {512, 8}, {512, 16}};
 constexpr int kResNForms = (int)(sizeof(kResForms) / sizeof(kResForms[0]));
 constexpr int res_raw_regs(int form, int esize, bool bwd) { return kResForms[form].NP * esize * 2 * (bwd ? 2 : 1); }
 constexpr bool res_form_fits(int form, int esize, bool bwd) { return res_raw_regs(form, esize, bwd) <= (bwd ? 64 : 128); }
+// the backward with gsum keeps a third raw operand; the same working set has to fit beside it
+constexpr bool res_form_fits_add(int form, int esize) {
+  return res_form_fits(form, esize, true) && res_raw_regs(form, esize, true) * 3 / 2 <= 96;
+}
 
 struct GnResPlan {
   int form, cpg, nch, nslots;  // form < 0: no resident form holds this geometry
   unsigned grid;
 };
-static GnResPlan gn_nhwc_res_plan(int B, int C, int HW, int G, int dtype, bool bwd) {
+static GnResPlan gn_nhwc_res_plan(int B, int C, int HW, int G, int dtype, bool bwd, bool add = false) {
   GnResPlan p{-1, 0, 0, 0, 0};
   p.cpg = C / G;
   int bch = p.cpg;
@@ -1483,7 +1568,8 @@ static GnResPlan gn_nhwc_res_plan(int B, int C, int HW, int G, int dtype, bool b
   p.grid = (unsigned)(B * (C / bch));
   for (int f = 0; f < kResNForms; ++f) {
     const int nslots = std::min(kResForms[f].T / p.nch, HW);
-    if (!res_form_fits(f, dtype_size(dtype), bwd) || (int64_t)nslots * kResForms[f].NP < HW) continue;
+    const bool fits = add ? res_form_fits_add(f, dtype_size(dtype)) : res_form_fits(f, dtype_size(dtype), bwd);
+    if (!fits || (int64_t)nslots * kResForms[f].NP < HW) continue;
     p.form = f;
     p.nslots = nslots;
     break;
@@ -1501,9 +1587,9 @@ static bool gn_nhwc_res_faster(int B, int C, int HW, int G, int dtype, bool bwd)
 }
 
 // 1 = resident, 0 = streaming; a pure function of the geometry (a captured graph replays the same kernels everywhere)
-static int gn_nhwc_route(int B, int C, int HW, int G, int dtype, int dir) {
+static int gn_nhwc_route(int B, int C, int HW, int G, int dtype, int dir, bool add = false) {
   if (!g_gn_resident.load(std::memory_order_relaxed)) return 0;
-  return gn_nhwc_res_plan(B, C, HW, G, dtype, dir != 0).form >= 0 && gn_nhwc_res_faster(B, C, HW, G, dtype, dir != 0) ? 1 : 0;
+  return gn_nhwc_res_plan(B, C, HW, G, dtype, dir != 0, add).form >= 0 && gn_nhwc_res_faster(B, C, HW, G, dtype, dir != 0) ? 1 : 0;
 }
 
 extern "C" int lora_amd_groupnorm_nhwc_resident(int32_t enable) {
@@ -1518,6 +1604,13 @@ extern "C" int lora_amd_groupnorm_nhwc_route(int32_t B, int32_t C, int32_t HW, i
                  "groupnorm_nhwc_route: geometry B=%d C=%d HW=%d groups=%d not supported", B, C, HW, groups);
   LORA_AMD_CHECK(dtype_ok(dtype), LORA_AMD_EINVAL, "groupnorm_nhwc_route: bad dtype %d", dtype);
   return gn_nhwc_route(B, C, HW, groups, dtype, backward);
+}
+
+extern "C" int lora_amd_groupnorm_nhwc_route_add(int32_t B, int32_t C, int32_t HW, int32_t groups, int32_t dtype) {
+  LORA_AMD_CHECK(gn_nhwc_geo(B, C, HW, groups).ok, LORA_AMD_EINVAL,
+                 "groupnorm_nhwc_route_add: geometry B=%d C=%d HW=%d groups=%d not supported", B, C, HW, groups);
+  LORA_AMD_CHECK(dtype_ok(dtype), LORA_AMD_EINVAL, "groupnorm_nhwc_route_add: bad dtype %d", dtype);
+  return gn_nhwc_route(B, C, HW, groups, dtype, 1, true);
 }
 
 // f(int_c<form>) for the plan's form
@@ -1581,23 +1674,38 @@ extern "C" int lora_amd_groupnorm_nhwc_fwd(const void *x, const void *gamma, con
 extern "C" int lora_amd_groupnorm_nhwc_bwd(const void *x, const void *gout, const void *gamma, const float *aff,
                                            void *dx, void *workspace, size_t workspace_bytes, int32_t B, int32_t C,
                                            int32_t HW, int32_t groups, int32_t act, int32_t dtype, void *stream) {
+  return lora_amd_groupnorm_nhwc_bwd_add(x, gout, nullptr, C, gamma, aff, dx, workspace, workspace_bytes, B, C, HW, groups, act,
+                                         dtype, stream);
+}
+
+extern "C" int lora_amd_groupnorm_nhwc_bwd_add(const void *x, const void *gout, const void *gsum, int64_t ld_gsum,
+                                               const void *gamma, const float *aff, void *dx, void *workspace,
+                                               size_t workspace_bytes,
+                                               int32_t B, int32_t C, int32_t HW, int32_t groups, int32_t act,
+                                               int32_t dtype, void *stream) {
   GN_NHWC_CHECKS("groupnorm_nhwc_bwd");
   LORA_AMD_CHECK(x && gout && gamma && aff && dx && workspace, LORA_AMD_EINVAL, "groupnorm_nhwc_bwd: null pointer");
   LORA_AMD_CHECK(aligned_for(x, dtype) && aligned_for(gout, dtype) && aligned_for(dx, dtype) &&
-                     aligned_for(gamma, dtype) && ((uintptr_t)aff % 32) == 0,
+                     aligned_for(gamma, dtype) && aligned_for(gsum, dtype) && ((uintptr_t)aff % 32) == 0,
                  LORA_AMD_EINVAL, "groupnorm_nhwc_bwd: unaligned tensor");
-  if (gn_nhwc_route(B, C, HW, groups, dtype, 1)) {
-    const GnResPlan p = gn_nhwc_res_plan(B, C, HW, groups, dtype, true);
+  const bool add = gsum != nullptr;
+  LORA_AMD_CHECK(!add || (ld_gsum >= C && ld_gsum % 8 == 0), LORA_AMD_EINVAL,
+                 "groupnorm_nhwc_bwd: gsum row stride %lld (a multiple of 8, at least C = %d)", (long long)ld_gsum, C);
+  if (gn_nhwc_route(B, C, HW, groups, dtype, 1, add)) {
+    const GnResPlan p = gn_nhwc_res_plan(B, C, HW, groups, dtype, true, add);
     by_dtype(dtype, [&](auto e) {
       by_bool(act != 0, [&](auto a) {
-        res_by_form(p.form, [&](auto f) {
-          using E = decltype(e);
-          using S = typename E::storage;
-          constexpr int F = decltype(f)::value;
-          if constexpr (res_form_fits(F, (int)sizeof(S), true))
-            hipLaunchKernelGGL((gn_nhwc_res_bwd_kernel<E, decltype(a)::value, kResForms[F].T, kResForms[F].NP>), dim3(p.grid),
-                               dim3(kResForms[F].T), 0, st, (const S *)x, (const S *)gout, (const S *)gamma, aff, (S *)dx, C,
-                               HW, p.cpg, p.nch, p.nslots);
+        by_bool(add, [&](auto ad) {
+          res_by_form(p.form, [&](auto f) {
+            using E = decltype(e);
+            using S = typename E::storage;
+            constexpr int F = decltype(f)::value;
+            constexpr bool AD = decltype(ad)::value;
+            if constexpr (AD ? res_form_fits_add(F, (int)sizeof(S)) : res_form_fits(F, (int)sizeof(S), true))
+              hipLaunchKernelGGL((gn_nhwc_res_bwd_kernel<E, decltype(a)::value, kResForms[F].T, kResForms[F].NP, AD>),
+                                 dim3(p.grid), dim3(kResForms[F].T), 0, st, (const S *)x, (const S *)gout, (const S *)gsum,
+                                 ld_gsum, (const S *)gamma, aff, (S *)dx, C, HW, p.cpg, p.nch, p.nslots);
+          });
         });
       });
     });
@@ -1609,15 +1717,48 @@ extern "C" int lora_amd_groupnorm_nhwc_bwd(const void *x, const void *gout, cons
       using S = typename E::storage;
       constexpr bool A = decltype(a)::value;
       hipLaunchKernelGGL((gn_nhwc_bwd_kernel<E, A, false>), grid, block, 0, st, (const S *)x, (const S *)gout,
-                         (const S *)gamma, aff, part, (const float *)nullptr, (S *)nullptr, C, HW, q.cw, q.tiles,
-                         q.nslots, q.px, q.S);
+                         (const S *)nullptr, (int64_t)0, (const S *)gamma, aff, part, (const float *)nullptr, (S *)nullptr, C, HW, q.cw,
+                         q.tiles, q.nslots, q.px, q.S);
       hipLaunchKernelGGL(gn_nhwc_bwd_finalize_kernel, gridg, block, 0, st, part, cvec, C, HW, groups, q.S);
-      hipLaunchKernelGGL((gn_nhwc_bwd_kernel<E, A, true>), grid, block, 0, st, (const S *)x, (const S *)gout,
-                         (const S *)gamma, aff, (float *)nullptr, cvec, (S *)dx, C, HW, q.cw, q.tiles, q.nslots,
-                         q.px, q.S);
+      by_bool(add, [&](auto ad) {
+        hipLaunchKernelGGL((gn_nhwc_bwd_kernel<E, A, true, decltype(ad)::value>), grid, block, 0, st, (const S *)x,
+                           (const S *)gout, (const S *)gsum, ld_gsum, (const S *)gamma, aff, (float *)nullptr, cvec, (S *)dx, C, HW,
+                           q.cw, q.tiles, q.nslots, q.px, q.S);
+      });
     });
   });
   return check_launch("lora_amd_groupnorm_nhwc_bwd");
+}
+
+// ---- ResnetBlock2D tail entry point ------------------------------------------------------------------------------------
+extern "C" int lora_amd_resnet_tail(const void *h, int64_t ldh, const void *r, int64_t ldr, const void *b2, const void *bs,
+                                    void *out, int64_t ldo, int64_t rows, int32_t C, int32_t dtype, void *stream) {
+  LORA_AMD_CHECK(dtype_ok(dtype), LORA_AMD_EINVAL, "resnet_tail: bad dtype %d", dtype);
+  LORA_AMD_CHECK(rows >= 0 && C > 0 && C % 8 == 0 && ldh >= C && ldr >= C && ldo >= C && ldh % 8 == 0 && ldr % 8 == 0 &&
+                     ldo % 8 == 0,
+                 LORA_AMD_EINVAL, "resnet_tail: bad shape rows=%lld C=%d strides %lld / %lld / %lld", (long long)rows, C,
+                 (long long)ldh, (long long)ldr, (long long)ldo);
+  if (rows == 0) return LORA_AMD_OK;
+  LORA_AMD_CHECK(h && r && b2 && out, LORA_AMD_EINVAL, "resnet_tail: null pointer");
+  LORA_AMD_CHECK(aligned_for(h, dtype) && aligned_for(r, dtype) && aligned_for(out, dtype) && aligned_for(b2, dtype) &&
+                     aligned_for(bs, dtype),
+                 LORA_AMD_EINVAL, "resnet_tail: unaligned tensor");
+  const GnNhwcGeo q = gn_nhwc_geo(1, C, 1, 1);  // the column-owner split of C: cw chunks x nslots rows per workgroup
+  // rows per workgroup: ~1024 workgroups on the large maps, at least kNU rows per slot
+  int64_t rpb = std::max<int64_t>((int64_t)kNU * q.nslots, rows * q.tiles / 1024);
+  rpb = std::min<int64_t>(rpb, rows);
+  const int64_t nblk = (rows + rpb - 1) / rpb;
+  LORA_AMD_CHECK(nblk * q.tiles < (1ll << 31), LORA_AMD_EINVAL, "resnet_tail: %lld rows exceed the grid", (long long)rows);
+  const dim3 grid((unsigned)(nblk * q.tiles)), block(kHT);
+  by_dtype(dtype, [&](auto e) {
+    by_bool(bs != nullptr, [&](auto sb) {
+      using S = typename decltype(e)::storage;
+      hipLaunchKernelGGL((resnet_tail_kernel<decltype(e), decltype(sb)::value>), grid, block, 0, (hipStream_t)stream,
+                         (const S *)h, ldh, (const S *)r, ldr, (const S *)b2, (const S *)bs, (S *)out, ldo, rows, q.c8, q.cw,
+                         q.tiles, q.nslots, (int)rpb);
+    });
+  });
+  return check_launch("lora_amd_resnet_tail");
 }
 
 // ---- time-embedding addends entry points ------------------------------------------------------------------------------

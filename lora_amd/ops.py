@@ -616,6 +616,15 @@ TEMB_ONE_LAUNCH = True
 # gn_nhwc_res_*_kernel; the library routes by geometry); False = the three streaming launches everywhere
 # (tests/test_gn_resident_route.py and tests/test_gpu_gn_resident.py run both)
 GN_RESIDENT = True
+# the tail of every ResnetBlock2D (conv2 bias, conv_shortcut bias, shortcut + h) as ONE launch behind the bias-free convolutions
+# (csrc/hostops.hip resnet_tail_kernel, the roundings of the three adds); False = the library's bias adds and the ATen add
+# (tests/test_block_glue_route.py and tests/test_gpu_block_glue.py run both)
+RESNET_TAIL = True
+# the second gradient of a norm's input (the shortcut of a ResnetBlock2D, the closing residual of a Transformer2DModel, the
+# residual stream past norm1 of a BasicTransformerBlock) added inside the norm's backward launch (standin/fused.py
+# group_norm_fork / layer_norm_fork; csrc/hostops.hip gsum operands); False = autograd's own accumulation, one add each
+# (tests/test_block_glue_route.py and tests/test_gpu_block_glue.py run both)
+NORM_FORK = True
 # maskless Linear adapters of rank 17..64 on the step's merged weights (csrc/merge_step.hip merge_step_wide_kernel: the
 # in-step merge walks the rank in chunks; factor gradients: WIDE_FACTORS below);
 # False = the frozen GEMM + primitives route of LoraLinearFunction, forward and backward
@@ -652,7 +661,7 @@ def apply_ab_overrides(spec: str, namespace: dict) -> dict:
     """``LORA_AMD_AB="NAME=0,OTHER=1"``: the ONE measurement switch for same-box A/B runs — flips the module constants
     listed in ``allowed`` (and only those) without a code edit; every A/B log under profiles/ names the spec it ran with
     (a constant retired since then is an unknown name here)."""
-    allowed = ("ATTN_SHORT_BWD", "COLREDUCE_MFMA", "CONCAT_GROUPS", "CONV3_FUSED", "CONV3_WIDE", "GN_RESIDENT", "MASTER_MERGE", "MERGED_WIDE", "SVD_WIDE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
+    allowed = ("ATTN_SHORT_BWD", "COLREDUCE_MFMA", "CONCAT_GROUPS", "CONV3_FUSED", "CONV3_WIDE", "GN_RESIDENT", "MASTER_MERGE", "MERGED_WIDE", "NORM_FORK", "RESNET_TAIL", "SVD_WIDE", "TEMB_ONE_LAUNCH", "WS_HEADS", "WS_DROPOUT", "WS_DROPOUT_WIDE",
                "WS_DROPOUT_WIDE_BWD", "WIDE_FACTORS", "WIDE_DROPOUT")
     done = {}
     for item in filter(None, (s.strip() for s in spec.split(","))):

@@ -107,6 +107,71 @@ def group_norm_act(x: torch.Tensor, norm: nn.GroupNorm, act: bool = True,
     return F.silu(y) if act else y
 
 
+class _GroupNormForkNHWC(torch.autograd.Function):
+    """``_GroupNormActNHWC`` that also hands its input on: ``(x, y)``.  Everything else that reads x takes the first output,
+    so x's two gradients arrive here together and the second is added inside the launch that writes the first."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, groups: int, eps: float, act: bool, addend):
+        ctx.set_materialize_grads(False)
+        add32 = None if addend is None else addend.detach().to(torch.float32).contiguous()
+        y, aff = _C.groupnorm_nhwc_fwd(x, weight, bias, groups, eps, act, add32)
+        ctx.save_for_backward(x, weight, aff)
+        ctx.groups, ctx.act = groups, act
+        ctx.add_dtype = None if addend is None else addend.dtype
+        return x, y
+
+    @staticmethod
+    def backward(ctx, gs, gy):
+        x, weight, aff = ctx.saved_tensors
+        if gy is None:  # only the input was used downstream
+            return (gs if ctx.needs_input_grad[0] else None), None, None, None, None, None, None
+        dx = dadd = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[6]:
+            gy = gy.contiguous(memory_format=torch.channels_last)
+            inside = (gs is not None and ctx.needs_input_grad[0] and not ctx.needs_input_grad[6]
+                      and _C.gsum_takes(x, gs))
+            dx = _C.groupnorm_nhwc_bwd(x, gy, weight, aff, ctx.groups, ctx.act, gs if inside else None)
+            if ctx.needs_input_grad[6]:
+                dadd = dx.sum(dim=(2, 3), dtype=torch.float32).to(ctx.add_dtype)
+            if not ctx.needs_input_grad[0]:
+                dx = None
+            elif gs is not None and not inside:
+                dx = dx + gs
+        return dx, None, None, None, None, None, dadd
+
+
+def group_norm_fork(x: torch.Tensor, norm: nn.GroupNorm, act: bool = True, addend: Optional[torch.Tensor] = None):
+    """``(x_pass, group_norm_act(x, norm, act, addend))`` for an x that something else reads as well (the shortcut of a
+    ResnetBlock2D, the closing residual of a Transformer2DModel): read it through ``x_pass`` and the backward of the norm
+    adds that gradient to its own in the launch that writes it, in place of autograd's separate accumulation.  Where the
+    channels_last kernels do not apply, or x takes no gradient, x_pass is x itself."""
+    if torch.is_grad_enabled() and x.requires_grad and _gn_native_nhwc(x, norm):
+        return _GroupNormForkNHWC.apply(x, norm.weight, norm.bias, norm.num_groups, norm.eps, act, addend)
+    return x, group_norm_act(x, norm, act, addend)
+
+
+class _ResnetTail(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, r, b2, bs):
+        return _C.resnet_tail(h, r, b2, bs)
+
+    @staticmethod
+    def backward(ctx, g):  # a sum: both operands take the incoming gradient as it is
+        return g, g, None, None
+
+
+def resnet_tail(h: torch.Tensor, r: torch.Tensor, b2: torch.Tensor, bs: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``(r + bs) + (h + b2)`` with the biases broadcast over [B, C, H, W] (``bs`` None: ``r + (h + b2)``): the tail of a
+    ResnetBlock2D behind bias-free convolutions.  One launch on channels_last tensors (frozen biases); the three ATen adds,
+    which give the same bits, everywhere else."""
+    frozen = not (torch.is_grad_enabled() and (b2.requires_grad or (bs is not None and bs.requires_grad)))
+    if _ENABLED and frozen and _C.resnet_tail_supported(h, r, b2, bs):
+        return _ResnetTail.apply(h, r, b2, bs)
+    h = h + b2.view(1, -1, 1, 1)
+    return (r if bs is None else r + bs.view(1, -1, 1, 1)) + h
+
+
 class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps: float):
@@ -132,6 +197,27 @@ def layer_norm(x: torch.Tensor, norm: nn.LayerNorm) -> torch.Tensor:
     return norm(x)
 
 
+class _LayerNormFork(torch.autograd.Function):
+    """``_LayerNorm`` that also hands its input on (``group_norm_fork``'s twin); the backward is the input gradient of a
+    LayerNorm plus the gradient of the residual stream, which ``add_layernorm_bwd`` computes in one launch."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps: float):
+        ctx.set_materialize_grads(False)
+        y, stats = _C.layernorm_fwd(x, weight, bias, eps)
+        ctx.save_for_backward(x, weight, stats)
+        return x, y
+
+    @staticmethod
+    def backward(ctx, gs, gy):
+        x, weight, stats = ctx.saved_tensors
+        if gy is None or not ctx.needs_input_grad[0]:
+            return (gs if ctx.needs_input_grad[0] else None), None, None, None
+        inside = gs is not None and gs.dtype == x.dtype and gs.shape == x.shape
+        dx = _C.add_layernorm_bwd(x, gy.contiguous(), gs.contiguous() if inside else None, weight, stats)
+        return (dx if inside or gs is None else dx + gs), None, None, None
+
+
 class _AddLayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, weight, bias, eps: float):
@@ -154,6 +240,14 @@ def _ln_native(x: torch.Tensor, norm: nn.LayerNorm) -> bool:
             and len(norm.normalized_shape) == 1 and w is not None and b is not None
             and not (w.requires_grad or b.requires_grad) and w.dtype == x.dtype and b.dtype == x.dtype
             and x.data_ptr() % 32 == 0 and _C.layernorm_supported(x.shape[-1]))
+
+
+def layer_norm_fork(x: torch.Tensor, norm: nn.LayerNorm):
+    """``(x_pass, layer_norm(x, norm))`` for an x that the residual stream reads as well (norm1 of a
+    BasicTransformerBlock); see ``group_norm_fork``."""
+    if torch.is_grad_enabled() and x.requires_grad and _ln_native(x, norm):
+        return _LayerNormFork.apply(x, norm.weight, norm.bias, norm.eps)
+    return x, layer_norm(x, norm)
 
 
 def add_layer_norm(a: torch.Tensor, b: torch.Tensor, norm: nn.LayerNorm):

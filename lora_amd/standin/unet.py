@@ -22,7 +22,7 @@ import torch.nn.functional as F
 from . import attention
 from .attention import sdpa
 from . import fused
-from .fused import add_layer_norm, geglu, group_norm_act, layer_norm
+from .fused import add_layer_norm, geglu, group_norm_act, group_norm_fork, layer_norm, layer_norm_fork
 from .. import _C, ops
 from torch.utils.checkpoint import checkpoint
 
@@ -161,6 +161,11 @@ def _trains(module: nn.Module) -> bool:
     return any(p.requires_grad for p in module.parameters())
 
 
+def _hooked(module: nn.Module) -> bool:
+    """Someone registered a hook on the module: only its own ``__call__`` runs them."""
+    return bool(module._forward_hooks or module._forward_pre_hooks or module._backward_hooks or module._backward_pre_hooks)
+
+
 def _project(lin: nn.Module, x: torch.Tensor, in_heads, out_heads) -> torch.Tensor:
     """A q / k / v / out projection on head-padded activations: adapters handle the layout themselves
     (``forward_heads``), a plain Linear gets dense copies around it."""
@@ -205,7 +210,9 @@ class BasicTransformerBlock(nn.Module):
 
     def forward(self, x, context):
         # each residual add runs inside the LayerNorm pass that follows it (fused.add_layer_norm)
-        x, n = add_layer_norm(self.attn1(layer_norm(x, self.norm1)), x, self.norm2)
+        # x feeds norm1 and the residual stream: through the fork its two gradients meet in norm1's backward launch
+        x, n = layer_norm_fork(x, self.norm1) if ops.NORM_FORK else (x, layer_norm(x, self.norm1))
+        x, n = add_layer_norm(self.attn1(n), x, self.norm2)
         x, n = add_layer_norm(self.attn2(n, context), x, self.norm3)
         return self.ff(n) + x
 
@@ -221,7 +228,8 @@ class Transformer2DModel(nn.Module):
 
     def forward(self, x, context):
         B, C, H, W = x.shape
-        n = group_norm_act(x, self.norm, act=False)
+        # the closing "+ x" reads x through the fork: its gradient is added inside norm's backward launch
+        x, n = group_norm_fork(x, self.norm, act=False) if ops.NORM_FORK else (x, group_norm_act(x, self.norm, act=False))
         nhwc = n.is_contiguous(memory_format=torch.channels_last) and not n.is_contiguous()
         # A 1x1 convolution IS the token-major linear map: one library GEMM with the bias in its epilogue instead of a
         # MIOpen call (on NCHW activations wrapped in NCHW<->NHWC transposes) plus a strided bias add.  On channels_last
@@ -261,7 +269,9 @@ class ResnetBlock2D(nn.Module):
 
     def forward(self, x, temb):
         """``temb``: a tensor or :class:`TembAddends`."""
-        n1 = group_norm_act(x, self.norm1)  # GroupNorm + SiLU as HIP passes (fused.py)
+        # GroupNorm + SiLU as HIP passes (fused.py); the shortcut reads x through the fork, so that its gradient is added
+        # inside norm1's backward launch
+        x, n1 = group_norm_fork(x, self.norm1) if ops.NORM_FORK else (x, group_norm_act(x, self.norm1))
         t = None
         if isinstance(temb, TembAddends):
             t, temb = temb.addends.get(self), temb.temb
@@ -270,8 +280,7 @@ class ResnetBlock2D(nn.Module):
             # term norm2 takes
             c1 = self.conv1
             h = F.conv2d(n1, c1.weight, None, c1.stride, c1.padding, c1.dilation, c1.groups)
-            h = self.conv2(self.dropout(group_norm_act(h, self.norm2, addend=t)))
-            return (x if self.conv_shortcut is None else self.conv_shortcut(x)) + h
+            return self._tail(x, self.dropout(group_norm_act(h, self.norm2, addend=t)))
         t = self.time_emb_proj(self.nonlinearity(temb))  # [B, C_out]
         if type(self.conv1) is nn.Conv2d and self.conv1.bias is not None:
             # the convolution's bias and the time embedding are both per-(sample, channel) terms in front of norm2:
@@ -281,8 +290,26 @@ class ResnetBlock2D(nn.Module):
             t = t + c1.bias
         else:
             h = self.conv1(n1)
-        h = self.conv2(self.dropout(group_norm_act(h, self.norm2, addend=t)))
-        return (x if self.conv_shortcut is None else self.conv_shortcut(x)) + h
+        return self._tail(x, self.dropout(group_norm_act(h, self.norm2, addend=t)))
+
+    def _tail(self, x, n2):
+        """``shortcut(x) + conv2(n2)``.  On channels_last device tensors with plain, frozen convolutions the biases of both
+        and the add are ONE launch behind the bias-free convolutions (fused.resnet_tail, ops.RESNET_TAIL); everywhere else
+        (CPU, NCHW, LORA_AMD_HOSTOPS=0, an adapter in place of a convolution, a trained or missing bias, a convolution that
+        carries hooks: they fire only when the module itself is called) the modules run."""
+        c2, cs = self.conv2, self.conv_shortcut
+        convs = (c2,) if cs is None else (c2, cs)
+        if (ops.RESNET_TAIL and fused._ENABLED and x.is_cuda and x.dim() == 4 and not x.is_contiguous()
+                and x.is_contiguous(memory_format=torch.channels_last) and n2.dtype == x.dtype
+                and all(type(c) is nn.Conv2d and not _hooked(c) and c.bias is not None and c.weight.dtype == x.dtype
+                        and c.bias.dtype == x.dtype and isinstance(c.padding, tuple)
+                        and not (torch.is_grad_enabled() and (c.weight.requires_grad or c.bias.requires_grad))
+                        for c in convs)):
+            h = F.conv2d(n2, c2.weight, None, c2.stride, c2.padding, c2.dilation, c2.groups)
+            r = x if cs is None else F.conv2d(x, cs.weight, None, cs.stride, cs.padding, cs.dilation, cs.groups)
+            return fused.resnet_tail(h, r, c2.bias, None if cs is None else cs.bias)
+        h = c2(n2)
+        return (x if cs is None else cs(x)) + h
 
 
 class Downsample2D(nn.Module):
