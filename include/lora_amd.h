@@ -1108,6 +1108,70 @@ int lora_amd_attn_short_bwd(const void *q, const int64_t *q_strides_host, const 
                             const int64_t *dv_strides_host, int32_t B, int32_t H, int64_t Sq, int32_t Sk, int32_t D,
                             float scale, int32_t dtype, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Resize a LoRA to a lower rank from its factors alone (csrc/lora_resize.hip; cli_svd.resize_pairs).  Per site
+ * A = up diag(scale) [N][R], D = down [R][K] (conv factors flattened from dim 1), dW = A D is never formed:
+ *   lora_amd_resize_gram   f64 partials of Gu = A^T A and Gd = D D^T, one R x R block per 256 rows of A / of D^T
+ *   lora_amd_resize_core   one workgroup per site: sums the partials in block order, Gu = E L E^T and
+ *                          M = L^1/2 E^T Gd E L^1/2 = F S^2 F^T by cyclic Jacobi in f64 (matrices in LDS, round-robin pair
+ *                          ordering, at most 24 sweeps each, early exit once a sweep rotates nothing), then
+ *                          Pu = (E L^-1/2 F S)[:, :r] and Pd = (S^-1 F^T L^1/2 E^T)[:r] into the workspace
+ *   lora_amd_resize_apply  up_out [N][r] = A Pu (= U S), down_out [r][K] = Pd D (= V^T), f64 sums rounded once to f32
+ *   lora_amd_resize_sign   the largest-|.| entry of every down_out row (the first among equals) becomes positive and the
+ *                          matching up_out column is flipped with it (cli_svd._fix_signs)
+ * so up_out down_out is the rank-r truncation of dW.  Eigenvalues at or below tol * (the largest one) count as zero, in
+ * both eigenproblems (tol is relative to SQUARED singular values): their rows of down_out and columns of up_out are
+ * exactly zero, as is their entry of S.  Rank-deficient input (up = 0, a zero scale, repeated columns, r > rank) is
+ * normal input.  All launches take the same device table (grid.y = site) and the geometry lora_amd_resize_table_plan
+ * filled on the host; they are independent of the launch order of workgroups and use no atomics: the same bits on every
+ * run, and a site's bits do not depend on the other sites of its table.
+ *   s_out  [n_sites][LORA_AMD_MAX_RANK] f64: entries [0, R) of a site's row = the singular values of dW, descending
+ *   status [n_sites]: 0, or bit 0 / bit 1 = the first / second eigenproblem did not converge within the sweep limit,
+ *          bit 2 = a Gram matrix was not finite */
+typedef struct lora_amd_resize_site {
+  const float *up;     /* [N][R] row-contiguous, 16-byte aligned                          */
+  const float *down;   /* [R][K] row-contiguous, 16-byte aligned                          */
+  const float *scale;  /* [R] multipliers of up's columns, or NULL                        */
+  float *up_out;       /* [N][r]                                                          */
+  float *down_out;     /* [r][K]                                                          */
+  int32_t N, K;        /* rows of up, columns of down                                     */
+  int32_t R, r;        /* rank of the input, rank of the output: 1 <= r <= R <= 64        */
+  int64_t ws_offset;   /* filled by the table plan: byte offset of the site's workspace   */
+} lora_amd_resize_site;
+typedef struct lora_amd_resize_plan_t {
+  int32_t native;          /* 1: the kernels take the site                                    */
+  int32_t gram_blocks_n;   /* 256-row blocks of A   = Gram partials of the up side           */
+  int32_t gram_blocks_k;   /* 256-row blocks of D^T = Gram partials of the down side         */
+  int32_t apply_blocks_n;  /* 64-row blocks of up_out                                         */
+  int32_t apply_blocks_k;  /* 64-column blocks of down_out                                    */
+  int32_t reserved;
+  int64_t workspace_bytes; /* the site's share of the workspace (a multiple of 256)           */
+} lora_amd_resize_plan_t;
+typedef struct lora_amd_resize_table_t {
+  int64_t workspace_bytes; /* of the whole table                                              */
+  int32_t n_sites;
+  int32_t gram_grid;       /* grid.x of the Gram launch  = the largest block count of a site  */
+  int32_t apply_grid;      /* grid.x of the apply launch                                      */
+  int32_t sign_grid;       /* grid.x of the sign launch  = the largest r                      */
+} lora_amd_resize_table_t;
+/* Pure host.  native = 1 when 1 <= r <= R <= LORA_AMD_MAX_RANK, N >= 1, K >= 1, dtype == LORA_AMD_F32 and both bases are
+ * 16-byte aligned; R or r outside their range: LORA_AMD_ERANK; any other site: native = 0 (the caller's exact route). */
+int lora_amd_resize_plan(int64_t N, int64_t K, int32_t R, int32_t r, int32_t dtype, const void *up, const void *down,
+                         lora_amd_resize_plan_t *out);
+/* Pure host: checks every site as above (a site that is not native: LORA_AMD_ERANK / LORA_AMD_EINVAL, the message names
+ * it), fills ws_offset and the launch geometry.  Upload the table afterwards. */
+int lora_amd_resize_table_plan(lora_amd_resize_site *sites_host, int32_t n_sites, lora_amd_resize_table_t *out);
+/* sites_dev 16-byte aligned (LORA_AMD_EINVAL), workspace_bytes >= geo_host->workspace_bytes (LORA_AMD_EWORKSPACE). */
+int lora_amd_resize_gram(const lora_amd_resize_site *sites_dev, int32_t n_sites, const lora_amd_resize_table_t *geo_host,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int lora_amd_resize_core(const lora_amd_resize_site *sites_dev, int32_t n_sites, const lora_amd_resize_table_t *geo_host,
+                         void *workspace, size_t workspace_bytes, float tol, double *s_out, int32_t *status,
+                         void *stream);
+int lora_amd_resize_apply(const lora_amd_resize_site *sites_dev, int32_t n_sites,
+                          const lora_amd_resize_table_t *geo_host, const void *workspace, size_t workspace_bytes,
+                          void *stream);
+int lora_amd_resize_sign(const lora_amd_resize_site *sites_dev, int32_t n_sites, const lora_amd_resize_table_t *geo_host,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -272,10 +272,35 @@ class TembSite(C.Structure):
                 ("row_begin", C.c_int32), ("out_offset", C.c_int64)]
 
 
+class ResizeSite(C.Structure):
+    """lora_amd_resize_site (include/lora_amd.h): one site of a rank resize; ws_offset is filled by the table plan."""
+    c_struct = "lora_amd_resize_site"
+    __slots__ = ()
+    _fields_ = [("up", C.c_void_p), ("down", C.c_void_p), ("scale", C.c_void_p), ("up_out", C.c_void_p),
+                ("down_out", C.c_void_p), ("N", C.c_int32), ("K", C.c_int32), ("R", C.c_int32), ("r", C.c_int32),
+                ("ws_offset", C.c_int64)]
+
+
+class ResizePlan(C.Structure):
+    c_struct = "lora_amd_resize_plan_t"
+    __slots__ = ()
+    _fields_ = [("native", C.c_int32), ("gram_blocks_n", C.c_int32), ("gram_blocks_k", C.c_int32),
+                ("apply_blocks_n", C.c_int32), ("apply_blocks_k", C.c_int32), ("reserved", C.c_int32),
+                ("workspace_bytes", C.c_int64)]
+
+
+class ResizeGeometry(C.Structure):
+    c_struct = "lora_amd_resize_table_t"
+    __slots__ = ()
+    _fields_ = [("workspace_bytes", C.c_int64), ("n_sites", C.c_int32), ("gram_grid", C.c_int32),
+                ("apply_grid", C.c_int32), ("sign_grid", C.c_int32)]
+
+
 # every struct of the header: c_struct names it; empty __slots__ make a write to a non-field an AttributeError
 MIRRORS = (AttnShortPlan, FactorsSelfPlan, SelfSite, FactorsMfmaPlan, PackSite, FmSite, RaggedDesc, SubDesc,
            PlanesDesc, SplitTDesc, ResidDesc, ThinSite, ThinQSite, ThinFinishDesc, SplitDesc, MergeSite, MstepSite,
-           MergeSummary, AdamWGroup, LinearPlan, ConvPlan, Conv3NhwcPlan, Conv3PackSite, WsSite, ReduceDesc, TembSite)
+           MergeSummary, AdamWGroup, LinearPlan, ConvPlan, Conv3NhwcPlan, Conv3PackSite, WsSite, ReduceDesc, TembSite,
+           ResizeSite, ResizePlan, ResizeGeometry)
 
 
 # Every function of include/lora_amd.h, in header order: (name, restype, argtypes).  This table is the only place a
@@ -423,6 +448,12 @@ FUNCTIONS = (
     ("lora_amd_attn_short_bwd_plan", cint, (i32, i32, i64, i32, i32, P(AttnShortPlan))),
     ("lora_amd_attn_short_bwd", cint, (vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i64, i32,
         i32, f32, i32, vp, sz, vp)),
+    ("lora_amd_resize_plan", cint, (i64, i64, i32, i32, i32, vp, vp, P(ResizePlan))),
+    ("lora_amd_resize_table_plan", cint, (P(ResizeSite), i32, P(ResizeGeometry))),
+    ("lora_amd_resize_gram", cint, (vp, i32, P(ResizeGeometry), vp, sz, vp)),
+    ("lora_amd_resize_core", cint, (vp, i32, P(ResizeGeometry), vp, sz, f32, vp, vp, vp)),
+    ("lora_amd_resize_apply", cint, (vp, i32, P(ResizeGeometry), vp, sz, vp)),
+    ("lora_amd_resize_sign", cint, (vp, i32, P(ResizeGeometry), vp)),
 )
 SYMBOLS = tuple(name for name, _, _ in FUNCTIONS)
 
@@ -2618,3 +2649,116 @@ def attn_short_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dout: torc
         _ptr(dk), st[5] if need_kv else None, _ptr(dv), st[6] if need_kv else None, B, H, Sq, Sk, D, float(scale),
         dtype_code(q.dtype), _ptr(workspace) if need_kv else None, have, _stream()), "lora_amd_attn_short_bwd")
     return dq, dk, dv
+
+
+# ----------------------------------------------------------------------------- rank resize from the factors (csrc/lora_resize.hip)
+RESIZE_TOL = 1e-13   # eigenvalues (squared singular values) at or below this fraction of the largest count as zero
+RESIZE_STATUS = {1: "the eigenproblem of up^T up did not converge", 2: "the eigenproblem of the core did not converge",
+                 4: "a Gram matrix is not finite"}
+
+
+def resize_plan(N: int, K: int, R: int, r: int, dtype: torch.dtype = torch.float32, up_ptr: int = 0,
+                down_ptr: int = 0) -> ResizePlan:
+    """Host arithmetic: does ``lora_amd_resize_*`` take a site (``native``), and its block counts and workspace share.
+    R or r out of range raise ValueError (LORA_AMD_ERANK)."""
+    pl = ResizePlan()
+    _check(require().lora_amd_resize_plan(int(N), int(K), int(R), int(r), _DT.get(dtype, -1), up_ptr or None,
+                                          down_ptr or None, C.byref(pl)), "lora_amd_resize_plan")
+    return pl
+
+
+def resize_native(up: torch.Tensor, down: torch.Tensor, r: int) -> bool:
+    """Do the kernels take this (up [N, R], down [R, K]) pair as it stands?"""
+    if not (up.is_cuda and down.is_cuda and up.dtype == down.dtype == torch.float32 and up.dim() == 2 and down.dim() == 2
+            and up.is_contiguous() and down.is_contiguous() and up.shape[1] == down.shape[0]):
+        return False
+    R = up.shape[1]
+    if not 1 <= r <= R <= MAX_RANK:
+        return False
+    return resize_plan(up.shape[0], down.shape[1], R, r, up.dtype, up.data_ptr(), down.data_ptr()).native == 1
+
+
+class ResizeTable:
+    """Planned device table of one rank resize: ``sites`` = [(up [N, R], down [R, K], scale [R] or None, r)], f32 device
+    tensors.  Outputs (``outs`` = [(up_out [N, r], down_out [r, K])], allocated here when None), the workspace, the
+    singular values ``s`` [n, 64] f64 and the per-site ``status`` words live as long as the table."""
+
+    def __init__(self, sites, outs=None):
+        lib = require()
+        if not sites:
+            raise ValueError("ResizeTable: no sites")
+        if outs is not None and len(outs) != len(sites):
+            raise ValueError("ResizeTable: one (up_out, down_out) pair per site expected")
+        self.device = sites[0][0].device
+        arr = (ResizeSite * len(sites))()
+        self.keep, self.outs = [], []
+        if outs is None:   # every output of the table in one allocation
+            total = sum((int(up.shape[0]) + int(down.shape[-1])) * int(r) for up, down, _, r in sites if up.dim() == 2 and down.dim() == 2)
+            flat, at = torch.empty(max(total, 1), dtype=torch.float32, device=self.device), 0
+        for i, (q, (up, down, scale, r)) in enumerate(zip(arr, sites)):
+            _dev_check(up, down, scale)
+            if up.dtype != torch.float32 or down.dtype != torch.float32 or (scale is not None and scale.dtype != torch.float32):
+                raise ValueError(f"ResizeTable: site {i}: f32 factors and scales expected")
+            if up.dim() != 2 or down.dim() != 2 or up.shape[1] != down.shape[0] or not up.is_contiguous() or \
+                    not down.is_contiguous():
+                raise ValueError(f"ResizeTable: site {i}: contiguous up [N, R] and down [R, K] expected, got "
+                                 f"{tuple(up.shape)} and {tuple(down.shape)}")
+            (N, R), K = up.shape, down.shape[1]
+            if scale is not None and (scale.numel() != R or not scale.is_contiguous()):
+                raise ValueError(f"ResizeTable: site {i}: scale must hold {R} contiguous values")
+            if up.data_ptr() % 16 or down.data_ptr() % 16:
+                raise ValueError(f"ResizeTable: site {i}: factors must be 16-byte aligned")
+            if outs is None:
+                r = max(int(r), 0)
+                uo = flat[at:at + N * r].view(N, r)
+                do = flat[at + N * r:at + (N + K) * r].view(r, K)
+                at += (N + K) * r
+            else:
+                uo, do = outs[i]
+                _dev_check(uo, do)
+                if uo.dtype != torch.float32 or do.dtype != torch.float32 or tuple(uo.shape) != (N, r) or \
+                        tuple(do.shape) != (r, K) or not uo.is_contiguous() or not do.is_contiguous():
+                    raise ValueError(f"ResizeTable: site {i}: contiguous f32 outputs [{N}, {r}] and [{r}, {K}] expected")
+            q.up, q.down, q.up_out, q.down_out = up.data_ptr(), down.data_ptr(), uo.data_ptr(), do.data_ptr()
+            q.scale = scale.data_ptr() if scale is not None else None
+            q.N, q.K, q.R, q.r = N, K, R, int(r)
+            self.keep.append((up, down, scale))
+            self.outs.append((uo, do))
+        self.geo = ResizeGeometry()
+        _check(lib.lora_amd_resize_table_plan(arr, len(sites), C.byref(self.geo)), "lora_amd_resize_table_plan")
+        self.n, self.host = len(sites), arr
+        self.table = table_to_device(arr, self.device)
+        self.ws = torch.empty(self.geo.workspace_bytes, dtype=torch.uint8, device=self.device)
+        self.s = torch.zeros(self.n, MAX_RANK, dtype=torch.float64, device=self.device)
+        self.status = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+
+    def _args(self):
+        return self.table.data_ptr(), self.n, C.byref(self.geo)
+
+    def gram(self) -> None:
+        _check(require().lora_amd_resize_gram(*self._args(), self.ws.data_ptr(), self.ws.numel(), _stream()),
+               "lora_amd_resize_gram")
+
+    def core(self, tol: float = RESIZE_TOL) -> None:
+        _check(require().lora_amd_resize_core(*self._args(), self.ws.data_ptr(), self.ws.numel(), float(tol),
+                                              self.s.data_ptr(), self.status.data_ptr(), _stream()), "lora_amd_resize_core")
+
+    def apply(self) -> None:
+        _check(require().lora_amd_resize_apply(*self._args(), self.ws.data_ptr(), self.ws.numel(), _stream()),
+               "lora_amd_resize_apply")
+
+    def sign(self) -> None:
+        _check(require().lora_amd_resize_sign(*self._args(), _stream()), "lora_amd_resize_sign")
+
+    def run(self, tol: float = RESIZE_TOL):
+        """The four launches; returns the outputs.  A site whose eigenproblem did not converge raises."""
+        self.gram()
+        self.core(tol)
+        self.apply()
+        self.sign()
+        bad = self.status.nonzero().flatten().tolist()      # one host sync per resize
+        if bad:
+            st = int(self.status[bad[0]])
+            raise RuntimeError(f"lora_amd_resize_core: site {bad[0]}: " +
+                               "; ".join(msg for bit, msg in RESIZE_STATUS.items() if st & bit))
+        return self.outs

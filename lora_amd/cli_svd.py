@@ -38,6 +38,12 @@ through ``lora_amd_chol_inverse_batched`` (l <= 80), one batched l x l core SVD;
 narrower than the sketch: one exact SVD on the device.  ``ROUTES`` counts the sites per route.
 
 CPU tensors take the reference's exact full-SVD path (plumbing).
+
+Rank resize (``resize_pairs`` / ``svd_resize``; ``csrc/lora_resize.hip``): when the residual already is a
+product ``up diag(scale) down`` of rank R <= 64 — a trained file, a ``lora_join`` of members — its best rank-r approximation
+follows from the factors alone: two R x R Gram matrices, two symmetric eigenproblems in f64, two thin products; one table
+and four launches per model, no base model, nothing dense.  Separate from everything above: ``ROUTES`` and the K5 entry
+points are untouched, ``RESIZE_ROUTES`` counts its sites.
 """
 from __future__ import annotations
 
@@ -701,6 +707,129 @@ def overwrite_base(base_model, tuned_model, rank, clamp_quantile, seed: int = 0,
             lor_base.lora_down.weight.data = down.to(device=dev, dtype=dtype)
 
 
+# ----------------------------------------------------------------------------- rank resize from the factors alone
+# the kernels of csrc/lora_resize.hip for device sites inside lora_amd_resize_plan's `native`; False = the exact host route
+# for every site (tests run both)
+RESIZE_NATIVE = True
+# sites resized since import, by route: "native" = the four launches over one table, "exact" = f64 SVD of the dense product
+RESIZE_ROUTES = {"native": 0, "exact": 0}
+
+
+def _resize_exact(up2: torch.Tensor, down2: torch.Tensor, scale, r: int, tol: float):
+    """(up' [N, r], down' [r, K], S [R] f64) of one site by ``torch.linalg.svd`` of the dense f64 product on the host:
+    up' = U S, down' = V^T (``distill_pair``'s convention), ``_fix_signs``' sign rule, and the kernels' zero rule — a
+    squared singular value at or below tol times the largest counts as zero, its row and column are zero."""
+    a = up2.detach().to("cpu", torch.float64)
+    if scale is not None:
+        a = a * scale.detach().to("cpu", torch.float64)[None, :]
+    d = down2.detach().to("cpu", torch.float64)
+    R = a.shape[1]
+    U, S, Vh = torch.linalg.svd(a @ d, full_matrices=False)
+    live = (S * S > tol * S[0] * S[0]) & (S > 0) if S.numel() else S > 0
+    S = torch.where(live, S, torch.zeros_like(S))
+    m = min(S.numel(), r)
+    up = torch.zeros(a.shape[0], r, dtype=torch.float64)
+    down = torch.zeros(r, d.shape[1], dtype=torch.float64)
+    up[:, :m] = U[:, :m] * S[:m]
+    down[:m] = Vh[:m] * live[:m, None]
+    up, down = _fix_signs(up, down)
+    s_full = torch.zeros(R, dtype=torch.float64)
+    s_full[:min(R, S.numel())] = S[:R]
+    return up.float().to(up2.device), down.float().to(up2.device), s_full
+
+
+def resize_pairs(ups, downs, rank: int, scales=None, clamp_quantile: Optional[float] = None, *, return_s: bool = False,
+                 tol: float = _C.RESIZE_TOL):
+    """The best rank-``rank`` approximation of every ``up_i diag(scales_i) down_i`` from the factors alone: a list of
+    (up' , down') in f32 with ``up' down'`` the truncated SVD of the product, ``up' = U S`` and ``down' = V^T`` as
+    ``distill_pair`` returns them, the largest-|.| entry of every ``down'`` row positive.
+
+    ``ups[i]`` [N, R] / ``downs[i]`` [R, K] in f16, bf16 or f32 (computed in f32); conv factors ([O, R, 1, 1] /
+    [R, C, kh, kw]) are flattened from dim 1 and the results shaped back.  ``scales[i]``: R multipliers of the columns of
+    ``ups[i]`` (the selector of a joined LoRA), or None.  A site of rank R <= ``rank`` is resized to R (re-factored, not padded).
+    Device sites of rank <= 64 take the kernels of ``csrc/lora_resize.hip`` — Gram matrices of both factors, two R x R
+    symmetric eigenproblems in f64, two thin products; one table and four launches for the whole list, nothing dense is
+    formed.  CPU tensors, R > 64 and any other site ``lora_amd_resize_plan`` does not call native: f64
+    ``torch.linalg.svd`` of the dense product on the host.  Rank-deficient products are normal input: singular values
+    whose square is at or below ``tol`` times the largest count as zero and give zero rows / columns.
+    ``clamp_quantile``: ``distill_pair``'s clamp (None: no clamp).  ``return_s``: also the singular values per site ([R] f64)."""
+    ups, downs = list(ups), list(downs)
+    if len(ups) != len(downs) or (scales is not None and len(scales) != len(ups)):
+        raise ValueError("resize_pairs: ups, downs and scales must have one entry per site")
+    n = len(ups)
+    flat, out, svals = [], [None] * n, [None] * n
+    native = []
+    for i, (up, down) in enumerate(zip(ups, downs)):
+        if up.dim() not in (2, 4) or down.dim() != up.dim() or up.shape[1] != down.shape[0]:
+            raise ValueError(f"resize_pairs: site {i}: up {tuple(up.shape)} and down {tuple(down.shape)} are no LoRA pair")
+        up2 = up.detach().float().reshape(up.shape[0], -1).contiguous()
+        down2 = down.detach().float().flatten(start_dim=1).contiguous()
+        R = down2.shape[0]
+        if up2.shape[1] != R:
+            raise ValueError(f"resize_pairs: site {i}: up {tuple(up.shape)} is not [N, R] / [N, R, 1, 1]")
+        sc = None if scales is None or scales[i] is None else \
+            torch.as_tensor(scales[i], dtype=torch.float32).to(up2.device).reshape(-1).contiguous()
+        if sc is not None and sc.numel() != R:
+            raise ValueError(f"resize_pairs: site {i}: {sc.numel()} scales for rank {R}")
+        r = min(int(rank), R)
+        if r < 1:
+            raise ValueError(f"resize_pairs: rank {rank}")
+        flat.append((up2, down2, sc, r))
+        if RESIZE_NATIVE and up2.is_cuda and _C.resize_native(up2, down2, r):
+            native.append(i)
+    if native:
+        tab = _C.ResizeTable([flat[i] for i in native])
+        for i, (uo, do), s in zip(native, tab.run(tol), tab.s):
+            out[i], svals[i] = (uo, do), s[:flat[i][0].shape[1]]
+        RESIZE_ROUTES["native"] += len(native)
+    for i in range(n):
+        if out[i] is None:
+            up2, down2, sc, r = flat[i]
+            uo, do, svals[i] = _resize_exact(up2, down2, sc, r, tol)
+            out[i] = (uo, do)
+            RESIZE_ROUTES["exact"] += 1
+    res = []
+    for (uo, do), up, down in zip(out, ups, downs):
+        if clamp_quantile is not None:
+            cu, cd = _clamp_pairs(uo[None], do[None], clamp_quantile)
+            uo, do = cu[0], cd[0]
+        if up.dim() == 4:
+            uo = uo.reshape(uo.shape[0], uo.shape[1], 1, 1)
+            do = do.reshape(do.shape[0], *down.shape[1:])
+        res.append((uo, do))
+    return (res, svals) if return_s else res
+
+
+def svd_resize(lora_path: str, rank: int, output_path: str, scales=None, device: Optional[str] = None):
+    """Resize a ``.safetensors`` LoRA to ``rank`` from its factors (no base model, no tuned checkpoint): every site of
+    every model of the file (unet, text_encoder) through ``resize_pairs``; a site whose rank is already <= ``rank`` is
+    copied.  Same keys, index layout and dtypes, ``{model}:{i}:rank`` updated; embeddings and other metadata carried over.
+    ``scales``: {"{model}:{i}": R multipliers} for the sites that want their rank columns weighted first.
+    ``device``: where the factors are resized (default: cuda:0 when there is one)."""
+    from .lora import EMBED_FLAG, safe_open, safe_save
+
+    if device is None:
+        device = "cuda:0" if torch.cuda.is_available() and _C.available() else "cpu"
+    f = safe_open(lora_path, framework="pt", device="cpu")
+    metadata = dict(f.metadata())
+    tensors = {k: f.get_tensor(k) for k in f.keys()}
+    sites = []
+    for key in tensors:
+        if metadata.get(key) == EMBED_FLAG or not key.endswith(":up"):
+            continue
+        stem = key[:-len(":up")]
+        if int(metadata[stem + ":rank"]) > rank:
+            sites.append(stem)
+    if sites:
+        pairs = resize_pairs([tensors[s + ":up"].to(device) for s in sites], [tensors[s + ":down"].to(device) for s in sites],
+                             rank, scales=None if scales is None else [scales.get(s) for s in sites])
+        for s, (up, down) in zip(sites, pairs):
+            dt = tensors[s + ":up"].dtype
+            tensors[s + ":up"], tensors[s + ":down"] = up.to("cpu", dt), down.to("cpu", dt)
+            metadata[s + ":rank"] = str(down.shape[0])
+    safe_save({k: v.contiguous() for k, v in tensors.items()}, output_path, metadata)
+
+
 def _load_pipe(path: str, device: str):
     """(unet, text_encoder) of a checkpoint; ``standin[:seed]`` builds random-init stand-ins (no diffusers here)."""
     if path.startswith("standin"):
@@ -733,6 +862,9 @@ def svd_distill(target_model: str, base_model: str, rank: int = 4, clamp_quantil
 def main():
     from .cli_lora_pti import _parse_cli
 
+    if len(sys.argv) > 1 and sys.argv[1] == "resize":   # lora_distill resize --lora_path=... --rank=8 --output_path=...
+        svd_resize(**_parse_cli(sys.argv[2:]))
+        return
     svd_distill(**_parse_cli(sys.argv[1:]))
 
 

@@ -111,6 +111,30 @@ class LoRAManager:
         diags = torch.repeat_interleave(s, torch.as_tensor(self.ranklist), dim=1)
         set_lora_diag_per_sample(self.pipe.unet, diags)
 
+    def compress(self, scales, rank: int, device=None):
+        """Fold the members, weighted as ``tune(scales)`` weights them, into ONE rank-``rank`` LoRA: ``(tensors, metadata)``
+        in the layout of ``lora_join``.  At every UNet site ``up' down'`` is the best rank-``rank`` approximation of
+        ``sum_i scales[i] up_i down_i`` — ``cli_svd.resize_pairs`` on the joined factors with the selector of ``tune`` as
+        the scale vector; text-encoder sites take scale 1, as ``tune`` leaves them.  ``rank = sum(ranklist)`` is lossless.
+        The pair loads through ``DummySafeTensorObject`` / ``monkeypatch_or_replace_safeloras``.  ``device``: where the
+        factors are resized (default: where the joined tensors live)."""
+        from .cli_svd import resize_pairs
+
+        assert len(scales) == len(self.ranklist), "Scale list should be the same length as ranklist"
+        diag = torch.repeat_interleave(torch.as_tensor(scales, dtype=torch.float32), torch.as_tensor(self.ranklist))
+        src = self.total_safelora
+        metadata = dict(src.metadata())
+        tensors = {key: src.get_tensor(key) for key in src.keys()}
+        stems = [key[:-len(":up")] for key in tensors if key.startswith(("unet", "text_encoder")) and key.endswith(":up")]
+        move = (lambda t: t) if device is None else (lambda t: t.to(device))
+        pairs = resize_pairs([move(tensors[s + ":up"]) for s in stems], [move(tensors[s + ":down"]) for s in stems], rank,
+                             scales=[diag if s.startswith("unet") else None for s in stems])
+        for s, (up, down) in zip(stems, pairs):
+            was = tensors[s + ":up"]
+            tensors[s + ":up"], tensors[s + ":down"] = up.to(was.device), down.to(was.device)   # f32: the caller casts
+            metadata[s + ":rank"] = str(down.shape[0])
+        return tensors, metadata
+
     def prompt(self, prompt):
         """``<1>``, ``<2>``, ... expand to the renamed learned tokens of member 1, 2, ..."""
         if prompt is None:
