@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LORA_AMD_ABI_VERSION 7
+#define LORA_AMD_ABI_VERSION 8
 
 /* status codes */
 #define LORA_AMD_OK 0
@@ -154,9 +154,9 @@ int lora_amd_merge_step(const lora_amd_mstep_site *sites_dev, int32_t n, int64_t
 /* Tuning hook (scripts/kbench.py): tile geometry 0..3 = 128x64 | 64x128 | 128x128 | 256x64 (rows x columns; applies to
  * tables planned after the call), dither form 1 = one hash per element, 2 = one hash chain per 16-byte chunk.  < 0 keeps. */
 int lora_amd_merge_step_set_tuning(int32_t tile, int32_t dither);
-/* Ranks 9..16 on bf16 activations with f32 factors: rowdot / rowdot_masked / rank_update / linear_fwd / linear_bwd_g run
+/* Ranks 9..16 on bf16 activations with f32 factors: rowdot / rank_update / linear_fwd / linear_bwd_g run
  * their matrix-core forms (csrc/rank16_mfma.hip; same arguments, outputs and partial-buffer geometry); ranks 17..64:
- * rowdot / rowdot_masked / rank_update run the wide forms of the same kernels (ceil(r / 16) rank-16 slices in one launch).
+ * rowdot / rank_update run the wide forms of the same kernels (ceil(r / 16) rank-16 slices in one launch).
  * enable = 0 routes all of them back to the VALU kernels (parity tests compare the two), 1 = default, < 0 only reads.
  * Returns the previous value. */
 int lora_amd_rank16_mfma(int32_t enable);
@@ -164,7 +164,7 @@ int lora_amd_rank16_mfma(int32_t enable);
  * whatever lora_amd_rank16_mfma says, 1 = default (the matrix-core form where lora_amd_rank16_mfma is on too), < 0 only
  * reads.  Returns the previous value. */
 int lora_amd_colreduce_mfma(int32_t enable);
-/* Pure host arithmetic: 1 exactly when lora_amd_rowdot[_masked] (op 0; cols = K, rows = x, ld = ldx) or lora_amd_rank_update
+/* Pure host arithmetic: 1 exactly when lora_amd_rowdot (op 0; cols = K, rows = x, ld = ldx) or lora_amd_rank_update
  * (op 1; cols = N, rows = y, ld = ldy) would run its matrix-core form on these arguments under the current hook setting —
  * the predicate the launchers themselves call.  rows is inspected for alignment only; has_selector: sel != NULL.  Any other
  * op: 0. */
@@ -196,21 +196,24 @@ int lora_amd_merge_set_tuning(int64_t tile_elems, int64_t blocks_per_cu);
  *     dX  = rank_update(G @ W, Gt, down, 1)
  * ---------------------------------------------------------------------- */
 
-/* T[M, r] (f32) = scale * X[M, K] @ F^T, F given as [r,K] or [K,r];
+/* T[M, r] (f32) = scale * (mask * X[M, K]) @ F^T, F given as [r,K] or [K,r];
  * optional selector S [r, r] (f32): T <- T @ S^T (sel_transposed=0, forward,
  * lora.py:56,63-70) or T <- T @ S (sel_transposed=1, backward).  sel may be NULL.
+ * mask: the dropout mask of (seed, offset, offset_dev, dropout_p) that lora_amd_rank_update applied to the same
+ * elements (the backward of a dropped-out rank_update); dropout_p = 0: no mask.
  * 1 <= r <= LORA_AMD_MAX_RANK.  bf16 rows with f32 factors, 9 <= r <= 64, no selector, K % 32 == 0, 16-byte aligned rows
  * (x, ldx % 8): the matrix-core form (ranks above 16 as ceil(r / 16) rank-16 slices in the same launch); anything else the
  * VALU kernel.  lora_amd_rank16_mfma_takes(0, ...) tells which. */
 int lora_amd_rowdot(const void *x, int64_t ldx, const void *factor, void *t_out,
                     int64_t M, int32_t K, int32_t r, int32_t x_dtype,
                     int32_t factor_dtype, int32_t factor_layout, float scale,
-                    const float *sel, int32_t sel_transposed, void *stream);
+                    const float *sel, int32_t sel_transposed, float dropout_p,
+                    uint64_t seed, uint64_t offset, const uint64_t *offset_dev, void *stream);
 
 /* Y[M, N] (y_dtype, in place) += scale * mask * T[M, r] (f32) @ F, F given as
  * [r,N] or [N,r].  Dropout (lora.py:45,56): keep-probability 1-p with inverted
  * scaling, generated in-kernel from Philox(seed, offset, offset_dev, element index); p = 0
- * disables it.  The same (seed, offset, offset_dev) reproduces the same mask in rowdot_masked.
+ * disables it.  The same (seed, offset, offset_dev) reproduces the same mask in lora_amd_rowdot.
  * 1 <= r <= LORA_AMD_MAX_RANK.  bf16 rows with f32 factors, 9 <= r <= 64, N % 8 == 0, 16-byte aligned rows (y, ldy % 8): the
  * matrix-core form (ranks above 16: the rank-16 slices chain into one sum, masked once — Y is read and written once, the mask
  * is the VALU kernel's); anything else the VALU kernel.  lora_amd_rank16_mfma_takes(1, ...) tells which. */
@@ -232,15 +235,6 @@ int lora_amd_rank_update_rowscale(void *y, int64_t ldy, const float *t, const vo
                                   int32_t r, int32_t y_dtype, int32_t factor_dtype, int32_t factor_layout, float scale,
                                   const float *row_scale, int32_t nsel, int64_t rows_per_sample, float dropout_p,
                                   uint64_t seed, uint64_t offset, void *stream);
-
-/* As lora_amd_rowdot but X is first multiplied elementwise by the dropout mask
- * of (seed, offset, offset_dev, p): the backward of a dropped-out rank_update. */
-int lora_amd_rowdot_masked(const void *x, int64_t ldx, const void *factor,
-                           void *t_out, int64_t M, int32_t K, int32_t r,
-                           int32_t x_dtype, int32_t factor_dtype,
-                           int32_t factor_layout, float scale, const float *sel,
-                           int32_t sel_transposed, float dropout_p,
-                           uint64_t seed, uint64_t offset, const uint64_t *offset_dev, void *stream);
 
 /* D (f32) = beta * D + scale * sum_m T[m, j] * mask * X[m, k]; D is [r,K] or
  * [K,r] per out_layout.  Two-stage reduction through `workspace` (bytes given
@@ -474,24 +468,17 @@ int lora_amd_linear_bwd_x(const void *x, int64_t ldx, void *dx, int64_t lddx, co
 
 /* Both factor-gradient partials in ONE launch, for sites whose input gradient and Gt [M, r] came out of
  * lora_amd_linear_gemm_fwd (factor_layout 3): up_part as in lora_amd_linear_bwd_g (with T scaled by `scale`),
- * down_part as in lora_amd_linear_bwd_x with dx = NULL and one Gt part (`sel` [r, r] or NULL).  No dropout. */
+ * down_part as in lora_amd_linear_bwd_x with dx = NULL and one Gt part (`sel` [r, r] or NULL).
+ * G and / or X rows may be head-padded (see lora_amd_linear_gemm_fwd): g_head_* describe G [M, heads*D], x_head_*
+ * describe X, 0 = dense; the partials stay dense.
+ * dropout_p > 0: a site whose branch had nn.Dropout (lora.py:45, 56): the G pass sees mask * G, the mask regenerated
+ * from (seed, offset [+ *offset_dev]) as lora_amd_linear_fwd indexed it.  Pairs with the dropout fields of
+ * lora_amd_ws_site (forward and input-gradient calls).  Dense G rows only (g_head_dim = 0). */
 int lora_amd_linear_bwd_factors(const void *g, int64_t ldg, const float *t, float *up_part, const void *x,
                                 int64_t ldx, const float *gt, const float *sel, float *down_part, int64_t M,
-                                int32_t K, int32_t N, int32_t r, int32_t act_dtype, float scale, void *stream);
-/* The same for a site whose branch had nn.Dropout (lora.py:45, 56): the G pass sees mask * G, the mask regenerated
- * from (seed, offset [+ *offset_dev]) as lora_amd_linear_fwd indexed it.  Pairs with the dropout fields of
- * lora_amd_ws_site (forward and input-gradient calls). */
-int lora_amd_linear_bwd_factors_drop(const void *g, int64_t ldg, const float *t, float *up_part, const void *x,
-                                     int64_t ldx, const float *gt, const float *sel, float *down_part, int64_t M,
-                                     int32_t K, int32_t N, int32_t r, int32_t act_dtype, float scale, float dropout_p,
-                                     uint64_t seed, uint64_t offset, const uint64_t *offset_dev, void *stream);
-/* The same for head-padded G and / or X rows (see lora_amd_linear_gemm_fwd_heads): g_head_* describe G [M, heads*D],
- * x_head_* describe X; the partials stay dense. */
-int lora_amd_linear_bwd_factors_heads(const void *g, int64_t ldg, const float *t, float *up_part, const void *x,
-                                      int64_t ldx, const float *gt, const float *sel, float *down_part, int64_t M,
-                                      int32_t K, int32_t N, int32_t r, int32_t act_dtype, float scale,
-                                      int32_t g_head_dim, int32_t g_head_pad, int32_t x_head_dim, int32_t x_head_pad,
-                                      void *stream);
+                                int32_t K, int32_t N, int32_t r, int32_t act_dtype, float scale, int32_t g_head_dim,
+                                int32_t g_head_pad, int32_t x_head_dim, int32_t x_head_pad, float dropout_p,
+                                uint64_t seed, uint64_t offset, const uint64_t *offset_dev, void *stream);
 
 /* K1 fully fused on the matrix cores: Y[M,N] = X[M,K] W[N,K]^T + bias + scale * (X down^T) up^T, and
  * t_out[M,r] (f32) = t_scale * X down^T for the backward.  ONE launch replaces the frozen addmm AND the low-rank branch
@@ -502,12 +489,19 @@ int lora_amd_linear_bwd_factors_heads(const void *g, int64_t ldg, const float *t
  *     dX[M,K] = G[M,N] W[N,K] + scale * (G up) down,   Gt = scale * G up,
  * when called as (x = G, w = W^T [K,N], y = dX, down = up [N,r], up = down [r,K], K <-> N swapped, t_scale = scale).
  * tile = 10 * stages + shape (shape 1: 64x320, 2: 64x160, 3: 32x160, 4: 128x160 outputs per workgroup; stages 2|3 LDS
- * ring slots); 0 = pick by grid size. */
+ * ring slots); 0 = pick by grid size.
+ * Head-padded activations: a row of `heads` runs of d elements stored with every run padded to D (d, D multiples of 8;
+ * the layout attention kernels want for head sizes 40 / 80).  x_head_dim/x_head_pad describe the X operand (logical
+ * K = heads * d, physical row length heads * D, pad never read), y_head_dim/y_head_pad the output (pad written as
+ * zeros; needs 160 % d == 0 so that an output tile owns whole heads).  0 = dense.  Removes the pad / slice copies around
+ * the attention core: q, k, v projections write the padded layout, the output projection reads it, and the
+ * input-gradient call (factor_layout 3) does the same in the other direction. */
 int lora_amd_linear_gemm_supported(int64_t M, int32_t K, int32_t N, int32_t r, int32_t act_dtype);
 int lora_amd_linear_gemm_fwd(const void *x, int64_t ldx, const void *w, int64_t ldw, const void *bias, void *y,
                              int64_t ldy, const float *down, const float *up, float *t_out, int64_t M, int32_t K,
                              int32_t N, int32_t r, int32_t act_dtype, float scale, float t_scale,
-                             int32_t factor_layout, int32_t tile, void *stream);
+                             int32_t factor_layout, int32_t tile, int32_t x_head_dim, int32_t x_head_pad,
+                             int32_t y_head_dim, int32_t y_head_pad, void *stream);
 
 /* K1/K2 weight-stationary form (csrc/gemm_ws.hip): one launch for up to LORA_AMD_WS_MAX_SITES sites that read the SAME
  * input X[M,K] (lora.py:53-58 called on to_q / to_k / to_v with one tensor): per site
@@ -549,28 +543,14 @@ int64_t lora_amd_ws_packed_elems(int32_t N, int32_t K);
 /* Pack B (element (n, k) at w[n * stride_n + k * stride_k], n < N, k < K) into fragment order (zero-padded panels). */
 int lora_amd_ws_pack(const void *w, int64_t stride_n, int64_t stride_k, int32_t N, int32_t K, int32_t dtype, void *out,
                      void *stream);
-int lora_amd_linear_ws(const void *x, int64_t ldx, int64_t M, int32_t K, int32_t act_dtype,
-                       const lora_amd_ws_site *sites /* host array */, int32_t nsites, int32_t row_groups, void *stream);
-/* lora_amd_linear_ws on a head-padded INPUT (ABI 7; the dropout sites around the attention core, lora.py:53-58 called by
- * CrossAttention.to_q / to_k / to_v / to_out): x rows hold K / x_head_dim heads of x_head_dim columns in slots of x_head_pad
- * (multiples of 8; pad never read); 0, 0 = dense.  A site's y_heads does the same for its output.  With both, the pad /
- * slice copies around the kernel disappear in either direction (forward: to_out reads the attention output as it is, q / k / v
- * leave padded; input-gradient call: G of q / k / v arrives padded, dX of to_out leaves padded). */
-int lora_amd_linear_ws_heads(const void *x, int64_t ldx, int64_t M, int32_t K, int32_t x_head_dim, int32_t x_head_pad,
-                             int32_t act_dtype, const lora_amd_ws_site *sites /* host array */, int32_t nsites,
-                             int32_t row_groups, void *stream);
-
-/* lora_amd_linear_gemm_fwd with head-padded activations: a row of `heads` runs of d elements stored with every run padded to D
- * (d, D multiples of 8; the layout attention kernels want for head sizes 40 / 80).  x_head_dim/x_head_pad describe
- * the X operand (logical K = heads * d, physical row length heads * D, pad never read), y_head_dim/y_head_pad the
- * output (pad written as zeros; needs 160 % d == 0 so that an output tile owns whole heads).  0 = dense.  Removes
- * the pad / slice copies around the attention core: q, k, v projections write the padded layout, the output
- * projection reads it, and the input-gradient call (factor_layout 3) does the same in the other direction. */
-int lora_amd_linear_gemm_fwd_heads(const void *x, int64_t ldx, const void *w, int64_t ldw, const void *bias, void *y,
-                                   int64_t ldy, const float *down, const float *up, float *t_out, int64_t M,
-                                   int32_t K, int32_t N, int32_t r, int32_t act_dtype, float scale, float t_scale,
-                                   int32_t factor_layout, int32_t tile, int32_t x_head_dim, int32_t x_head_pad,
-                                   int32_t y_head_dim, int32_t y_head_pad, void *stream);
+/* A head-padded INPUT (the dropout sites around the attention core, lora.py:53-58 called by CrossAttention.to_q / to_k /
+ * to_v / to_out): x rows hold K / x_head_dim heads of x_head_dim columns in slots of x_head_pad (multiples of 8; pad never
+ * read); 0, 0 = dense.  A site's y_heads does the same for its output.  With both, the pad / slice copies around the kernel
+ * disappear in either direction (forward: to_out reads the attention output as it is, q / k / v leave padded;
+ * input-gradient call: G of q / k / v arrives padded, dX of to_out leaves padded). */
+int lora_amd_linear_ws(const void *x, int64_t ldx, int64_t M, int32_t K, int32_t x_head_dim, int32_t x_head_pad,
+                       int32_t act_dtype, const lora_amd_ws_site *sites /* host array */, int32_t nsites,
+                       int32_t row_groups, void *stream);
 
 /* lora_amd_linear_gemm_fwd (dense rows, down [r,K], up [N,r]) with per-sample multipliers: row m's T row is multiplied by
  * row_scale[((m / rows_per_sample) % nsel) * r + j] (f32 [nsel, r], device) where T is rounded to the activation dtype;
@@ -599,17 +579,16 @@ typedef struct lora_amd_reduce_desc {
 /* The parameter gradients of a site on the merged-weight path (no T, no Gt saved or produced by another launch):
  * up_part[rb][RT][N] = sum_m (s X down^T)[m, j] G[m, n],  down_part[rb][RT][K] = sum_m (s G up)[m, j] X[m, k] per row
  * block rb, in ONE launch (each row block of G and X is read twice: row-dot phase, column-sum phase; replaces the autograd of lora.py:53-58 for dA, dB when the
- * forward ran on W + s up down).  f32 factors; G / X rows may be head-padded (d, D as in linear_bwd_factors_heads).
+ * forward ran on W + s up down).  f32 factors; G / X rows may be head-padded (d, D as in lora_amd_linear_bwd_factors).
  * The plan sizes the partial slabs: `nparts` row blocks, folded by lora_amd_reduce_batched. */
 typedef struct lora_amd_factors_self_plan_t {
   int32_t supported, rank_tile, nparts, reserved;
   int64_t up_part_floats, down_part_floats;
 } lora_amd_factors_self_plan_t;
-int lora_amd_linear_factors_self_plan(int64_t M, int32_t K, int32_t N, int32_t r, lora_amd_factors_self_plan_t *out);
-/* the same with the rows of a block chosen by the caller (0: as above); the one-launch pass takes `rows_per_block` of
- * lora_amd_self_site as that choice, so a site's slabs must be sized with the same value */
-int lora_amd_linear_factors_self_plan_rows(int64_t M, int32_t K, int32_t N, int32_t r, int32_t rows,
-                                           lora_amd_factors_self_plan_t *out);
+/* rows: the rows of a block chosen by the caller (0: the launcher's own choice); the one-launch pass takes
+ * `rows_per_block` of lora_amd_self_site as that choice, so a site's slabs must be sized with the same value */
+int lora_amd_linear_factors_self_plan(int64_t M, int32_t K, int32_t N, int32_t r, int32_t rows,
+                                      lora_amd_factors_self_plan_t *out);
 int lora_amd_linear_bwd_factors_self(const void *g, int64_t ldg, const void *x, int64_t ldx, const float *down,
                                      const float *up, float *up_part, float *down_part, int64_t M, int32_t K,
                                      int32_t N, int32_t r, int32_t act_dtype, float scale, int32_t g_head_dim,
@@ -666,8 +645,8 @@ typedef struct lora_amd_factors_mfma_plan_t {
 #define LORA_AMD_FM_PLAN_WIDE 2
 int lora_amd_factors_mfma_plan(int64_t M, int32_t K, int32_t N, int32_t r, int32_t act_dtype, int32_t rows, int32_t flags,
                                lora_amd_factors_mfma_plan_t *out);
-/* f32 masters -> fragment packs: pk[split][c/8][RT][8] in the activation dtype (RT = the rank tile 4 / 8 / 16 of r; ABI 7 — it was
- * [16] whatever the rank: a rank-4 pack is a quarter of the bytes now), split 0 = rounded value, split 1 = the remainder, ranks
+/* f32 masters -> fragment packs: pk[split][c/8][RT][8] in the activation dtype (RT = the rank tile 4 / 8 / 16 of r:
+ * a rank-4 pack is a quarter of the bytes of a rank-16 one), split 0 = rounded value, split 1 = the remainder, ranks
  * r .. RT - 1 zero; pk_down from down [r, K], pk_up from up [N, r]; sizes from lora_amd_factors_mfma_plan (pack_*_elems =
  * 2 C RT + 8).  `begin` is filled by the plan (host).
  * Ranks 17..64: ns = ceil(r / 16) consecutive rank-16 packs [slice][split][c/8][16][8], EACH followed by its own 16-byte tail
@@ -706,46 +685,32 @@ typedef struct lora_amd_fm_site {
   const uint64_t *offset_dev;
 } lora_amd_fm_site;
 /* A table is narrow (every rank <= 16, one rank tile) or WIDE (every rank in 17..64, any mix of slice counts): a mixed one is
- * LORA_AMD_ERANK.  This entry answers LORA_AMD_EUNSUPPORTED for a wide site with dropout_p > 0: such a table is planned by
- * lora_amd_factors_mfma_ragged_plan_masked below.  A wide site owns nrb * ns consecutive blocks of the
- * grid (nrb = ceil(M / rows_per_block)) and its slabs are [nparts][16 ns][C] (lora_amd_factors_mfma_plan, LORA_AMD_FM_PLAN_WIDE). */
+ * LORA_AMD_ERANK, and so is a rank above 64.  A wide site owns nrb * ns consecutive blocks of the grid (nrb = ceil(M /
+ * rows_per_block)) and its slabs are [nparts][16 ns][C] (lora_amd_factors_mfma_plan, LORA_AMD_FM_PLAN_WIDE).
+ * Sites of either kind may carry dropout_p > 0, and a table may mix masked and maskless sites.  The mask of a site is indexed by
+ * G's own row and 8-column chunk, so the ns slice workgroups of a row block regenerate the same mask and the masked wide pass is
+ * ns masked rank-16 passes; `scale` arrives with 1 / (1 - p) folded in at every rank. */
 int lora_amd_factors_mfma_ragged_plan(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype, int32_t lds_class,
                                       int64_t *grid);
-/* The same plan (arguments, results, checks: one implementation) that also takes dropout_p > 0 at ranks 17..64 (ABI 7, additive).
- * The mask of a site is indexed by G's own row and 8-column chunk, so the ns slice workgroups of a row block regenerate the same
- * mask and the masked wide pass is ns masked rank-16 passes; `scale` arrives with 1 / (1 - p) folded in, as at rank <= 16.  A wide
- * table may mix masked and maskless sites and any slice counts; wide and narrow sites stay apart (LORA_AMD_ERANK), and so does a
- * rank above 64.  A table with a masked site of rank 17..64 is launched by lora_amd_linear_bwd_factors_mfma_wide_masked. */
-int lora_amd_factors_mfma_ragged_plan_masked(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype, int32_t lds_class,
-                                             int64_t *grid);
-/* masked: a flags word.  Bit 0 (LORA_AMD_FM_TABLE_MASKED): 0 = no site of the table has dropout_p > 0; 1 = the kernel that
- * regenerates the dropout mask on G (sites with dropout_p = 0 in such a table run unmasked).  Bit 1 (LORA_AMD_FM_TABLE_WIDE):
- * the table was planned from sites of rank 17..64 (a workgroup is one (row block, 16-rank slice) of its site) — the caller's
- * promise: the launcher cannot see the device table, and a wide table launched without the bit reads past its rows.  Both
- * bits: LORA_AMD_EUNSUPPORTED from the two entries that take this word — a masked wide table has its own entry,
- * lora_amd_linear_bwd_factors_mfma_wide_masked. */
+/* The plan's block -> site map (grid int32 entries, filled on the host from a planned table).  With it on the device a
+ * workgroup finds its site with ONE scalar load instead of copying the table's block prefix to LDS and searching it (1.2 us of a
+ * 12.8 us block of the 320-wide sites). */
+int lora_amd_factors_mfma_block_map(const lora_amd_fm_site *sites /* host, planned */, int32_t n, int64_t grid, int32_t *map);
+/* flags.  Bit 0 (LORA_AMD_FM_TABLE_MASKED): 0 = no site of the table has dropout_p > 0; 1 = the kernel that regenerates the
+ * dropout mask on G (sites with dropout_p = 0 in such a table run unmasked).  Bit 1 (LORA_AMD_FM_TABLE_WIDE): the table was
+ * planned from sites of rank 17..64 (a workgroup is one (row block, 16-rank slice) of its site) — the caller's promise: the
+ * launcher cannot see the device table, and a wide table launched without the bit reads past its rows.  Both bits: the masked
+ * instantiation of the wide kernel of (lds_class, rows_per_block).  Any other bit: LORA_AMD_EINVAL. */
 #define LORA_AMD_FM_TABLE_MASKED 1
 #define LORA_AMD_FM_TABLE_WIDE 2
-/* rows_per_block (ABI 6): the block height (32 / 64) every site of the table was planned with — a compile-time constant of
+/* rows_per_block: the block height (32 / 64) every site of the table was planned with — a compile-time constant of
  * the kernel — or 0 for a class-2 table that holds sites of both heights (one launch, the workgroup enters its site's
- * instantiation); a class-1 table has one height (lora_amd_factors_mfma_ragged_plan refuses a mixed one). */
-int lora_amd_linear_bwd_factors_mfma_ragged(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid, int32_t lds_class,
-                                            int32_t rows_per_block, int32_t act_dtype, int32_t masked, void *stream);
-/* ABI 7: the same launch with the plan's block -> site map on the device (grid int32 entries, filled on the host by
- * lora_amd_factors_mfma_block_map from a planned table): a workgroup finds its site with ONE scalar load instead of copying the
- * table's block prefix to LDS and searching it (1.2 us of a 12.8 us block of the 320-wide sites).  block_map_dev = NULL is the
- * entry above. */
-int lora_amd_factors_mfma_block_map(const lora_amd_fm_site *sites /* host, planned */, int32_t n, int64_t grid, int32_t *map);
-int lora_amd_linear_bwd_factors_mfma_ragged_mapped(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid,
-                                                   const int32_t *block_map_dev, int32_t lds_class, int32_t rows_per_block,
-                                                   int32_t act_dtype, int32_t masked, void *stream);
-/* A WIDE table (ranks 17..64) in which sites carry dropout_p > 0, planned by lora_amd_factors_mfma_ragged_plan_masked (ABI 7,
- * additive): the arguments of the _mapped entry without the flag word (block_map_dev may be NULL), the same argument checks
- * before any launch, the masked instantiation of the wide kernel of (lds_class, rows_per_block).  Sites with dropout_p = 0 in
- * such a table run unmasked. */
-int lora_amd_linear_bwd_factors_mfma_wide_masked(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid,
-                                                 const int32_t *block_map_dev, int32_t lds_class, int32_t rows_per_block,
-                                                 int32_t act_dtype, void *stream);
+ * instantiation); a class-1 table has one height (lora_amd_factors_mfma_ragged_plan refuses a mixed one).
+ * block_map_dev: lora_amd_factors_mfma_block_map's array on the device, or NULL (the workgroup searches the table).  Every
+ * argument is checked before any launch. */
+int lora_amd_linear_bwd_factors_mfma_ragged(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid,
+                                            const int32_t *block_map_dev, int32_t lds_class, int32_t rows_per_block,
+                                            int32_t act_dtype, int32_t flags, void *stream);
 /* Tuning / test hook: which kernel a table of class 1 (64-row blocks) runs — 0 = the 10-pair kernel every class can take (two
  * workgroups per CU, two column groups in flight per wave), 1 / 2 = the 6-pair kernel at three workgroups per CU with 1 / 2
  * groups in flight, 3 / 4 / 5 = the 6-pair kernel at two per CU with 2 / 3 / 4 groups in flight; < 0 only reads.  Returns the
@@ -939,29 +904,23 @@ typedef struct lora_amd_adamw_group {
  * (torch.nn.utils.clip_grad_norm_ of grad_scale * g, the reference's reduce ->
  * average -> clip order); max_norm <= 0 disables clipping.  The update uses
  * grad_scale * c * g (grad_scale = 1/world_size after a SUM all-reduce).
- * `step` is the 1-based optimiser step (bias correction).  zero_grad != 0
- * writes zeros back to g (optimizer.zero_grad, train_lora_dreambooth.py:888). */
+ * `step` is the 1-based optimiser step (bias correction).  step_dev != NULL: the step is read from device memory
+ * instead and `step` is ignored, so a captured launch is identical from step to step (hipGraph replay);
+ * lora_amd_step_advance does step_dev[0] += 1.
+ * `scaler` (NULL = off): the 4-float loss-scaling state lora_amd_loss_scale_update maintains; the gradient is
+ * additionally multiplied by scaler[2] and the whole update is skipped (grads still zeroed) when scaler[3] == 0.
+ * zero_grad != 0 writes zeros back to g (optimizer.zero_grad, train_lora_dreambooth.py:888). */
 int lora_amd_clip_adamw(float *p, float *g, float *exp_avg, float *exp_avg_sq,
                         int64_t n, const lora_amd_adamw_group *groups_dev,
                         int32_t n_groups, const float *sumsq, float grad_scale,
-                        float max_norm, float beta1, float beta2, float eps,
-                        int64_t step, int32_t zero_grad, void *stream);
-
-/* hipGraph-replayable form: the 1-based step is read from device memory, so a captured
- * launch is identical from step to step; lora_amd_step_advance does step_dev[0] += 1.
- * `scaler` (NULL = off): the 4-float loss-scaling state lora_amd_loss_scale_update maintains; the gradient is
- * additionally multiplied by scaler[2] and the whole update is skipped (grads still zeroed) when scaler[3] == 0. */
-int lora_amd_clip_adamw_dev(float *p, float *g, float *exp_avg, float *exp_avg_sq,
-                            int64_t n, const lora_amd_adamw_group *groups_dev,
-                            int32_t n_groups, const float *sumsq, float grad_scale,
-                            float max_norm, float beta1, float beta2, float eps,
-                            const int64_t *step_dev, const float *scaler, int32_t zero_grad, void *stream);
+                        float max_norm, float beta1, float beta2, float eps, int64_t step,
+                        const int64_t *step_dev, const float *scaler, int32_t zero_grad, void *stream);
 int lora_amd_step_advance(int64_t *step_dev, void *stream);
 
 /* Dynamic fp16 loss scaling on the device (the GradScaler accelerate wraps around the reference's step when
  * mixed_precision="fp16", train_lora_dreambooth.py:489-494).  state = {scale for the next backward, finite-step
  * count, 1/scale of the step being applied, finite flag}.  Call after lora_amd_sumsq of the scaled (all-reduced)
- * gradient and before lora_amd_clip_adamw_dev: inf/nan -> scale *= backoff_factor and the update is skipped;
+ * gradient and before lora_amd_clip_adamw: inf/nan -> scale *= backoff_factor and the update is skipped;
  * growth_interval finite steps in a row -> scale *= growth_factor.  step_dev (may be NULL) advances only on
  * applied steps. */
 int lora_amd_loss_scale_update(float *state, const float *sumsq, int64_t *step_dev, float growth_factor,
@@ -1006,29 +965,26 @@ size_t lora_amd_groupnorm_nhwc_workspace(int32_t B, int32_t C, int32_t HW, int32
 int lora_amd_groupnorm_nhwc_fwd(const void *x, const void *gamma, const void *beta, const float *addend, void *y,
                                 float *aff, void *workspace, size_t workspace_bytes, int32_t B, int32_t C, int32_t HW,
                                 int32_t groups, float eps, int32_t act, int32_t dtype, void *stream);
-int lora_amd_groupnorm_nhwc_bwd(const void *x, const void *gout, const void *gamma, const float *aff, void *dx,
-                                void *workspace, size_t workspace_bytes, int32_t B, int32_t C, int32_t HW,
-                                int32_t groups, int32_t act, int32_t dtype, void *stream);
+/* The backward takes a second gradient: dx = rn(rn(d groupnorm / d x) + gsum), rn = rounding to the activation dtype, i.e. the
+ * bits of the backward followed by a separate add of gsum (the gradient that reaches x past the norm: the shortcut of a
+ * ResnetBlock2D, the closing residual of a Transformer2DModel).  gsum is [B * HW] rows of C channels, ld_gsum elements
+ * apart (ld_gsum = C: dx's layout; larger: a channel slice of a wider channels_last gradient, as the backward of a
+ * concatenation hands it out; a multiple of 8), aligned like dx, and may be dx itself; NULL: dx = rn(d groupnorm / d x)
+ * and ld_gsum is ignored.  The statistics launches are the same either way. */
+int lora_amd_groupnorm_nhwc_bwd(const void *x, const void *gout, const void *gsum, int64_t ld_gsum, const void *gamma,
+                                const float *aff, void *dx, void *workspace, size_t workspace_bytes, int32_t B,
+                                int32_t C, int32_t HW, int32_t groups, int32_t act, int32_t dtype, void *stream);
 /* Where a bundle of lcm(C / groups, 8) channels of one sample fits in one workgroup's registers (maps up to 32x32 forward,
  * 16x16 backward at SD1.5's widths), the two entry points above run ONE resident launch instead of three; same arguments,
  * same aff, the workspace is then left untouched.  The choice depends on the geometry only.  Host-only hooks:
  * lora_amd_groupnorm_nhwc_resident: 0 sends every geometry to the streaming kernels (the parity twin), 1 (default) routes by
  * geometry, < 0 only reads; returns the previous value.  lora_amd_groupnorm_nhwc_route: 1 if that launch would run resident
- * under the current setting, 0 for streaming, LORA_AMD_EINVAL for a geometry the entry points refuse. */
+ * under the current setting, 0 for streaming, LORA_AMD_EINVAL for a geometry the entry points refuse.  backward != 0 asks for
+ * lora_amd_groupnorm_nhwc_bwd; add != 0 for that call with gsum given (the resident launch then holds one operand more in
+ * registers, so fewer geometries fit it); add != 0 with backward == 0 is LORA_AMD_EINVAL. */
 int lora_amd_groupnorm_nhwc_resident(int32_t enable);
-int lora_amd_groupnorm_nhwc_route(int32_t B, int32_t C, int32_t HW, int32_t groups, int32_t dtype, int32_t backward);
-/* The backward with a second gradient: dx = rn(rn(d groupnorm / d x) + gsum), rn = rounding to the activation dtype, i.e. the
- * bits of lora_amd_groupnorm_nhwc_bwd followed by a separate add of gsum (the gradient that reaches x past the norm: the
- * shortcut of a ResnetBlock2D, the closing residual of a Transformer2DModel).  gsum is [B * HW] rows of C channels, ld_gsum
- * elements apart (ld_gsum = C: dx's layout; larger: a channel slice of a wider channels_last gradient, as the backward of a
- * concatenation hands it out; a multiple of 8), aligned like dx, and may be dx itself; NULL: exactly
- * lora_amd_groupnorm_nhwc_bwd.  The statistics launches are the same; the resident
- * launch holds one operand more in registers, so fewer geometries fit it: lora_amd_groupnorm_nhwc_route_add answers
- * like lora_amd_groupnorm_nhwc_route (backward) for a call with gsum given. */
-int lora_amd_groupnorm_nhwc_bwd_add(const void *x, const void *gout, const void *gsum, int64_t ld_gsum, const void *gamma,
-                                    const float *aff, void *dx, void *workspace, size_t workspace_bytes, int32_t B,
-                                    int32_t C, int32_t HW, int32_t groups, int32_t act, int32_t dtype, void *stream);
-int lora_amd_groupnorm_nhwc_route_add(int32_t B, int32_t C, int32_t HW, int32_t groups, int32_t dtype);
+int lora_amd_groupnorm_nhwc_route(int32_t B, int32_t C, int32_t HW, int32_t groups, int32_t dtype, int32_t backward,
+                                  int32_t add);
 
 /* The tail of a ResnetBlock2D in one launch, on dense channels_last rows ([rows][C], C % 8 == 0, row strides in elements,
  * multiples of 8): out = rn(rn(h + b2) + (bs ? rn(r + bs) : r)) with rn = rounding to the activation dtype, the bits of
@@ -1059,19 +1015,16 @@ int lora_amd_temb_addends(const lora_amd_temb_site *sites_dev, int32_t n_sites, 
                           float *out, int32_t B, int32_t K, int32_t dtype, void *stream);
 
 /* LayerNorm over the last dimension of row-contiguous x [M, K] (K % 8 == 0, K <= 2560; gamma / beta in the activation
- * dtype, frozen).  stats [M][2] f32 = (mean, rstd).  One launch each way. */
+ * dtype, frozen).  stats [M][2] f32 = (mean, rstd).  One launch each way.
+ * res / sum_out (both given or both NULL): the residual add in front of the norm in the same pass: sum_out = x + res
+ * (rounded to the activation dtype, what the residual stream carries on), y = layernorm(sum_out).  Backward: dx =
+ * d layernorm / d x (given gout; after a forward with res, evaluated at x = sum_out) + gsum, the gradient arriving through
+ * the residual stream (NULL: none); it is the gradient of both addends. */
 int lora_amd_layernorm_supported(int32_t K);
-int lora_amd_layernorm_fwd(const void *x, const void *gamma, const void *beta, void *y, float *stats, int64_t M,
-                           int32_t K, float eps, int32_t dtype, void *stream);
-int lora_amd_layernorm_bwd(const void *x, const void *gout, const void *gamma, const float *stats, void *dx,
-                           int64_t M, int32_t K, int32_t dtype, void *stream);
-/* The residual add in front of the norm in the same pass: sum_out = x + res (rounded to the activation dtype, what the
- * residual stream carries on), y = layernorm(sum_out).  Backward: dx = d layernorm / d sum (given gout, evaluated at
- * x = sum_out) + gsum, the gradient arriving through the residual stream; it is the gradient of both addends. */
-int lora_amd_add_layernorm_fwd(const void *x, const void *res, const void *gamma, const void *beta, void *sum_out,
-                               void *y, float *stats, int64_t M, int32_t K, float eps, int32_t dtype, void *stream);
-int lora_amd_add_layernorm_bwd(const void *x, const void *gout, const void *gsum, const void *gamma,
-                               const float *stats, void *dx, int64_t M, int32_t K, int32_t dtype, void *stream);
+int lora_amd_layernorm_fwd(const void *x, const void *res, const void *gamma, const void *beta, void *sum_out, void *y,
+                           float *stats, int64_t M, int32_t K, float eps, int32_t dtype, void *stream);
+int lora_amd_layernorm_bwd(const void *x, const void *gout, const void *gsum, const void *gamma, const float *stats,
+                           void *dx, int64_t M, int32_t K, int32_t dtype, void *stream);
 
 /* GEGLU gate behind the adapted projection: y [M, 2*inner] = [h | gate]; out [M, inner] = h * gelu(gate) (erf form).
  * Backward writes gy [M, 2*inner] = [gout * gelu(gate) | gout * h * gelu'(gate)] in one pass (no cat). */

@@ -20,7 +20,7 @@ F32, F16, BF16 = 0, 1, 2
 FACTOR_RK, FACTOR_KR = 0, 1
 ROUND_REFERENCE, ROUND_ONCE, ROUND_DITHER = 0, 1, 2
 MAX_RANK = 64
-ABI_VERSION = 7
+ABI_VERSION = 8
 # the matrix-core factor pass at ranks 17..64: the plan's flag (lora_amd_factors_mfma_plan) and the launchers' flags word
 FM_PLAN_WIDE = 2
 FM_TABLE_MASKED, FM_TABLE_WIDE = 1, 2
@@ -322,12 +322,10 @@ FUNCTIONS = (
     ("lora_amd_colreduce_mfma_takes", cint, (vp, i64, i64, i32, i32, i32)),
     ("lora_amd_rank_update_rowscale_mfma_takes", cint, (vp, i64, i64, i32, i32, i32, i32)),
     ("lora_amd_merge_set_tuning", cint, (i64, i64)),
-    ("lora_amd_rowdot", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32, vp)),
+    ("lora_amd_rowdot", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32, f32, u64, u64, vp, vp)),
     ("lora_amd_rank_update", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, f32, u64, u64, vp, vp)),
     ("lora_amd_rank_update_rowscale", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32, i64, f32,
         u64, u64, vp)),
-    ("lora_amd_rowdot_masked", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, i32, f32, vp, i32, f32, u64, u64,
-        vp, vp)),
     ("lora_amd_colreduce_workspace", sz, (i64, i32, i32)),
     ("lora_amd_colreduce", cint, (vp, i64, vp, vp, i64, i32, i32, i32, i32, f32, f32, f32, u64, u64, vp, vp, sz, vp)),
     ("lora_amd_rowdot_batched", cint, (vp, i64, i64, vp, i64, vp, i64, i32, i64, i32, i32, i32, i32, i32, f32, vp)),
@@ -358,25 +356,18 @@ FUNCTIONS = (
     ("lora_amd_linear_bwd_g_folded", cint, (vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, f32, u64,
         u64, vp, vp)),
     ("lora_amd_linear_bwd_x", cint, (vp, i64, vp, i64, vp, i32, vp, vp, vp, i64, i32, i32, i32, i32, vp)),
-    ("lora_amd_linear_bwd_factors", cint, (vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32, vp)),
-    ("lora_amd_linear_bwd_factors_drop", cint, (vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32,
-        f32, u64, u64, vp, vp)),
-    ("lora_amd_linear_bwd_factors_heads", cint, (vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32,
-        i32, i32, i32, i32, vp)),
+    ("lora_amd_linear_bwd_factors", cint, (vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32,
+        i32, i32, i32, f32, u64, u64, vp, vp)),
     ("lora_amd_linear_gemm_supported", cint, (i64, i32, i32, i32, i32)),
     ("lora_amd_linear_gemm_fwd", cint, (vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, f32,
-        f32, i32, i32, vp)),
+        f32, i32, i32, i32, i32, i32, i32, vp)),
     ("lora_amd_ws_config", cint, (i32, P(i32), P(i32))),
     ("lora_amd_ws_packed_elems", i64, (i32, i32)),
     ("lora_amd_ws_pack", cint, (vp, i64, i64, i32, i32, i32, vp, vp)),
-    ("lora_amd_linear_ws", cint, (vp, i64, i64, i32, i32, P(WsSite), i32, i32, vp)),
-    ("lora_amd_linear_ws_heads", cint, (vp, i64, i64, i32, i32, i32, i32, P(WsSite), i32, i32, vp)),
-    ("lora_amd_linear_gemm_fwd_heads", cint, (vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32,
-        f32, f32, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_linear_ws", cint, (vp, i64, i64, i32, i32, i32, i32, P(WsSite), i32, i32, vp)),
     ("lora_amd_linear_gemm_fwd_rowscale", cint, (vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32,
         f32, vp, i32, i64, i32, vp)),
-    ("lora_amd_linear_factors_self_plan", cint, (i64, i32, i32, i32, P(FactorsSelfPlan))),
-    ("lora_amd_linear_factors_self_plan_rows", cint, (i64, i32, i32, i32, i32, P(FactorsSelfPlan))),
+    ("lora_amd_linear_factors_self_plan", cint, (i64, i32, i32, i32, i32, P(FactorsSelfPlan))),
     ("lora_amd_linear_bwd_factors_self", cint, (vp, i64, vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32,
         i32, i32, i32, vp)),
     ("lora_amd_linear_factors_self_ragged_plan", cint, (vp, i32, i32, P(i64))),
@@ -386,11 +377,8 @@ FUNCTIONS = (
     ("lora_amd_factor_pack_plan", cint, (P(PackSite), i32, P(i64))),
     ("lora_amd_factor_pack", cint, (vp, i32, i64, i32, vp)),
     ("lora_amd_factors_mfma_ragged_plan", cint, (P(FmSite), i32, i32, i32, P(i64))),
-    ("lora_amd_factors_mfma_ragged_plan_masked", cint, (P(FmSite), i32, i32, i32, P(i64))),
-    ("lora_amd_linear_bwd_factors_mfma_ragged", cint, (vp, i32, i64, i32, i32, i32, i32, vp)),
     ("lora_amd_factors_mfma_block_map", cint, (P(FmSite), i32, i64, P(i32))),
-    ("lora_amd_linear_bwd_factors_mfma_ragged_mapped", cint, (vp, i32, i64, vp, i32, i32, i32, i32, vp)),
-    ("lora_amd_linear_bwd_factors_mfma_wide_masked", cint, (vp, i32, i64, vp, i32, i32, i32, vp)),
+    ("lora_amd_linear_bwd_factors_mfma_ragged", cint, (vp, i32, i64, vp, i32, i32, i32, i32, vp)),
     ("lora_amd_factors_mfma_set_tuning", cint, (i32,)),
     ("lora_amd_conv_plan", cint, (i32, i32, i32, i32, i32, i32, i32, P(ConvPlan))),
     ("lora_amd_conv_down_fwd", cint, (vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp)),
@@ -417,8 +405,7 @@ FUNCTIONS = (
     ("lora_amd_sum_parts", cint, (vp, i32, i64, vp, i64, vp)),
     ("lora_amd_sumsq_workspace", sz, (i64,)),
     ("lora_amd_sumsq", cint, (vp, i64, vp, vp, sz, vp)),
-    ("lora_amd_clip_adamw", cint, (vp, vp, vp, vp, i64, vp, i32, vp, f32, f32, f32, f32, f32, i64, i32, vp)),
-    ("lora_amd_clip_adamw_dev", cint, (vp, vp, vp, vp, i64, vp, i32, vp, f32, f32, f32, f32, f32, vp, vp, i32, vp)),
+    ("lora_amd_clip_adamw", cint, (vp, vp, vp, vp, i64, vp, i32, vp, f32, f32, f32, f32, f32, i64, vp, vp, i32, vp)),
     ("lora_amd_step_advance", cint, (vp, vp)),
     ("lora_amd_loss_scale_update", cint, (vp, vp, vp, f32, f32, i32, vp)),
     ("lora_amd_ti_rows_step", cint, (vp, vp, vp, i32, i32, i32, vp, vp, vp, f32, f32, f32, f32, f32, f32, i64, f32,
@@ -429,19 +416,15 @@ FUNCTIONS = (
     ("lora_amd_groupnorm_bwd", cint, (vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp)),
     ("lora_amd_groupnorm_nhwc_workspace", sz, (i32, i32, i32, i32)),
     ("lora_amd_groupnorm_nhwc_fwd", cint, (vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, f32, i32, i32, vp)),
-    ("lora_amd_groupnorm_nhwc_bwd", cint, (vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp)),
+    ("lora_amd_groupnorm_nhwc_bwd", cint, (vp, vp, vp, i64, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp)),
     ("lora_amd_groupnorm_nhwc_resident", cint, (i32,)),
-    ("lora_amd_groupnorm_nhwc_route", cint, (i32, i32, i32, i32, i32, i32)),
-    ("lora_amd_groupnorm_nhwc_bwd_add", cint, (vp, vp, vp, i64, vp, vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp)),
-    ("lora_amd_groupnorm_nhwc_route_add", cint, (i32, i32, i32, i32, i32)),
+    ("lora_amd_groupnorm_nhwc_route", cint, (i32, i32, i32, i32, i32, i32, i32)),
     ("lora_amd_resnet_tail", cint, (vp, i64, vp, i64, vp, vp, vp, i64, i64, i32, i32, vp)),
     ("lora_amd_temb_addends_supported", cint, (i32, i32, i32)),
     ("lora_amd_temb_addends", cint, (vp, i32, i64, vp, vp, i32, i32, i32, vp)),
     ("lora_amd_layernorm_supported", cint, (i32,)),
-    ("lora_amd_layernorm_fwd", cint, (vp, vp, vp, vp, vp, i64, i32, f32, i32, vp)),
-    ("lora_amd_layernorm_bwd", cint, (vp, vp, vp, vp, vp, i64, i32, i32, vp)),
-    ("lora_amd_add_layernorm_fwd", cint, (vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp)),
-    ("lora_amd_add_layernorm_bwd", cint, (vp, vp, vp, vp, vp, vp, i64, i32, i32, vp)),
+    ("lora_amd_layernorm_fwd", cint, (vp, vp, vp, vp, vp, vp, vp, i64, i32, f32, i32, vp)),
+    ("lora_amd_layernorm_bwd", cint, (vp, vp, vp, vp, vp, vp, i64, i32, i32, vp)),
     ("lora_amd_geglu_fwd", cint, (vp, i64, vp, i64, i64, i32, i32, vp)),
     ("lora_amd_geglu_bwd", cint, (vp, i64, vp, i64, vp, i64, i64, i32, i32, vp)),
     ("lora_amd_attn_short_bwd_supported", cint, (i64, i32, i32, i32, vp, i32)),
@@ -731,10 +714,10 @@ def rowdot(x: torch.Tensor, factor: torch.Tensor, layout: int, scale: float = 1.
         raise ValueError(f"rowdot: out must be a contiguous f32 [{M}, {r}] tensor on {x.device}")
     else:
         t = out
-    _check(lib.lora_amd_rowdot_masked(x.data_ptr(), x.stride(0), factor.data_ptr(), t.data_ptr(), M, K, r,
-                                      dtype_code(x.dtype), dtype_code(factor.dtype), layout, float(scale),
-                                      sel.data_ptr() if sel is not None else None, int(bool(sel_transposed)),
-                                      float(dropout_p), int(seed), *_off(offset), _stream()), "lora_amd_rowdot")
+    _check(lib.lora_amd_rowdot(x.data_ptr(), x.stride(0), factor.data_ptr(), t.data_ptr(), M, K, r,
+                               dtype_code(x.dtype), dtype_code(factor.dtype), layout, float(scale),
+                               sel.data_ptr() if sel is not None else None, int(bool(sel_transposed)),
+                               float(dropout_p), int(seed), *_off(offset), _stream()), "lora_amd_rowdot")
     return t
 
 
@@ -1163,21 +1146,16 @@ def clip_adamw(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
     for t in (p, g, m, v):
         if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel():
             raise ValueError("clip_adamw: flat contiguous f32 buffers of equal length expected")
-    if torch.is_tensor(step):
-        if step.dtype != torch.int64 or not step.is_cuda:
-            raise ValueError("clip_adamw: device step must be an int64 device tensor")
-        _check(lib.lora_amd_clip_adamw_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
-                                           groups_dev.data_ptr(), int(n_groups),
-                                           sumsq_t.data_ptr() if sumsq_t is not None else None, float(grad_scale),
-                                           float(max_norm), float(beta1), float(beta2), float(eps), step.data_ptr(),
-                                           _ptr(scaler), int(bool(zero_grad)), _stream()), "lora_amd_clip_adamw_dev")
-        return
-    if scaler is not None:
+    step_dev = step if torch.is_tensor(step) else None
+    if step_dev is not None and (step_dev.dtype != torch.int64 or not step_dev.is_cuda):
+        raise ValueError("clip_adamw: device step must be an int64 device tensor")
+    if step_dev is None and scaler is not None:
         raise ValueError("clip_adamw: loss scaling needs the device step counter")
     _check(lib.lora_amd_clip_adamw(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(),
                                    groups_dev.data_ptr(), int(n_groups),
                                    sumsq_t.data_ptr() if sumsq_t is not None else None, float(grad_scale),
-                                   float(max_norm), float(beta1), float(beta2), float(eps), int(step),
+                                   float(max_norm), float(beta1), float(beta2), float(eps),
+                                   0 if step_dev is not None else int(step), _ptr(step_dev), _ptr(scaler),
                                    int(bool(zero_grad)), _stream()), "lora_amd_clip_adamw")
 
 
@@ -1265,24 +1243,18 @@ def linear_bwd_factors(g: torch.Tensor, t: torch.Tensor, up_part: torch.Tensor, 
     ``g_heads`` / ``x_heads`` = (heads, d, D) when G / X rows are head-padded (logical N / K = heads * d);
     ``dropout`` = (p, seed, off) of the forward when the branch had nn.Dropout (dense rows only)."""
     _dev_check(g, t, up_part, x, gt, down_part, sel)
-    if dropout is not None and dropout[0] > 0.0:
-        if g_heads or x_heads:
-            raise ValueError("linear_bwd_factors: dropout with head-padded rows is not supported")
-        _check(require().lora_amd_linear_bwd_factors_drop(g.data_ptr(), g.stride(0), t.data_ptr(), up_part.data_ptr(),
-                                                          x.data_ptr(), x.stride(0), gt.data_ptr(), _ptr(sel),
-                                                          down_part.data_ptr(), g.shape[0], x.shape[1], g.shape[1], r,
-                                                          dtype_code(g.dtype), float(scale), float(dropout[0]),
-                                                          int(dropout[1]), *_off(dropout[2]), _stream()),
-               "lora_amd_linear_bwd_factors_drop")
-        return
+    drop = dropout is not None and dropout[0] > 0.0
+    if drop and (g_heads or x_heads):
+        raise ValueError("linear_bwd_factors: dropout with head-padded rows is not supported")
     N = g_heads[0] * g_heads[1] if g_heads else g.shape[1]
     K = x_heads[0] * x_heads[1] if x_heads else x.shape[1]
     gd, gD = (g_heads[1], g_heads[2]) if g_heads else (0, 0)
     xd, xD = (x_heads[1], x_heads[2]) if x_heads else (0, 0)
-    _check(require().lora_amd_linear_bwd_factors_heads(g.data_ptr(), g.stride(0), t.data_ptr(), up_part.data_ptr(),
-                                                       x.data_ptr(), x.stride(0), gt.data_ptr(), _ptr(sel),
-                                                       down_part.data_ptr(), g.shape[0], K, N, r,
-                                                       dtype_code(g.dtype), float(scale), gd, gD, xd, xD, _stream()),
+    p, seed, off = (float(dropout[0]), int(dropout[1]), _off(dropout[2])) if drop else (0.0, 0, (0, None))
+    _check(require().lora_amd_linear_bwd_factors(g.data_ptr(), g.stride(0), t.data_ptr(), up_part.data_ptr(),
+                                                 x.data_ptr(), x.stride(0), gt.data_ptr(), _ptr(sel),
+                                                 down_part.data_ptr(), g.shape[0], K, N, r, dtype_code(g.dtype),
+                                                 float(scale), gd, gD, xd, xD, p, seed, *off, _stream()),
            "lora_amd_linear_bwd_factors")
 
 
@@ -1295,7 +1267,7 @@ def factors_self_plan(M: int, K: int, N: int, r: int, rows: int = 0) -> FactorsS
     pl = _self_plan_cache.get(key)
     if pl is None:
         pl = FactorsSelfPlan()
-        _check(require().lora_amd_linear_factors_self_plan_rows(M, K, N, r, rows, C.byref(pl)),
+        _check(require().lora_amd_linear_factors_self_plan(M, K, N, r, rows, C.byref(pl)),
                "lora_amd_linear_factors_self_plan")
         _self_plan_cache[key] = pl
     return pl
@@ -1406,11 +1378,9 @@ def factors_mfma_table(sites, act_dtype: torch.dtype, lds_class: int):
     x_heads, r, plan[, (p, seed, offset)])] of one LDS class and rank tile (``plan`` = the site's ``factors_mfma_plan``;
     the optional last item = nn.Dropout on the branch: ``scale`` is then multiplied by 1 / (1 - p) here) -> (planned ctypes
     table, grid).  Sites of rank 17..64 (``plan`` taken with ``wide=True``) make a WIDE table: any mix of slice counts, no
-    site of rank <= 16 beside them; it is launched with ``wide=True``.  A wide site with a dropout triple sends the table
-    through ``lora_amd_factors_mfma_ragged_plan_masked`` (the older entry keeps refusing it); such a table may hold maskless
-    sites too and is launched with ``masked=True, wide=True``."""
+    site of rank <= 16 beside them; it is launched with ``wide=True``.  A wide table with a dropout triple in it may hold
+    maskless sites too and is launched with ``masked=True, wide=True``."""
     arr = (FmSite * len(sites))()
-    wide_masked = False
     for q, site in zip(arr, sites):
         g, x, pk_down, pk_up, up_part, down_part, scale, g_heads, x_heads, r, plan = site[:11]
         drop = site[11] if len(site) > 11 else None
@@ -1418,7 +1388,6 @@ def factors_mfma_table(sites, act_dtype: torch.dtype, lds_class: int):
             p, seed, off = drop
             q.dropout_p, q.seed = float(p), int(seed)
             scale = float(scale) / (1.0 - float(p))
-            wide_masked = wide_masked or int(r) > 16
             if torch.is_tensor(off):
                 q.offset, q.offset_dev = 0, off.data_ptr()
             else:
@@ -1433,8 +1402,8 @@ def factors_mfma_table(sites, act_dtype: torch.dtype, lds_class: int):
         q.g_head_dim, q.g_head_pad = (g_heads[1], g_heads[2]) if g_heads else (0, 0)
         q.x_head_dim, q.x_head_pad = (x_heads[1], x_heads[2]) if x_heads else (0, 0)
     grid = C.c_int64(0)
-    name = "lora_amd_factors_mfma_ragged_plan" + ("_masked" if wide_masked else "")
-    _check(getattr(require(), name)(arr, len(sites), dtype_code(act_dtype), lds_class, C.byref(grid)), name)
+    _check(require().lora_amd_factors_mfma_ragged_plan(arr, len(sites), dtype_code(act_dtype), lds_class, C.byref(grid)),
+           "lora_amd_factors_mfma_ragged_plan")
     return arr, grid.value
 
 
@@ -1456,24 +1425,13 @@ def factors_mfma_table_bytes(arr, grid: int) -> Tuple[bytes, int]:
 def linear_bwd_factors_mfma_ragged(table_dev: torch.Tensor, n: int, grid: int, lds_class: int,
                                    act_dtype: torch.dtype, masked: bool = False, rows: int = 64, map_offset: int = 0,
                                    wide: bool = False) -> None:
-    """``rows``: the block height (``plan.rows_per_block``) of EVERY site of the table (one per table, ABI 6).
+    """``rows``: the block height (``plan.rows_per_block``) of EVERY site of the table (one per table).
     ``map_offset`` > 0: the table buffer holds the block -> site map at that byte offset (``factors_mfma_table_bytes``).
-    ``wide``: the table was planned from sites of rank 17..64 (``FM_TABLE_WIDE``).  ``masked`` and ``wide`` together: the
-    table's own entry, ``lora_amd_linear_bwd_factors_mfma_wide_masked`` (the flag word of the other two refuses the pair)."""
-    if masked and wide:
-        bmap = table_dev.data_ptr() + int(map_offset) if map_offset else None
-        _check(require().lora_amd_linear_bwd_factors_mfma_wide_masked(table_dev.data_ptr(), n, grid, bmap, lds_class, int(rows),
-                                                                      dtype_code(act_dtype), _stream()),
-               "lora_amd_linear_bwd_factors_mfma_wide_masked")
-        return
+    ``wide``: the table was planned from sites of rank 17..64 (``FM_TABLE_WIDE``); ``masked``: a site of the table has
+    dropout (``FM_TABLE_MASKED``)."""
     flags = (FM_TABLE_MASKED if masked else 0) | (FM_TABLE_WIDE if wide else 0)
-    if map_offset:
-        _check(require().lora_amd_linear_bwd_factors_mfma_ragged_mapped(table_dev.data_ptr(), n, grid,
-                                                                        table_dev.data_ptr() + int(map_offset), lds_class,
-                                                                        int(rows), dtype_code(act_dtype), flags, _stream()),
-               "lora_amd_linear_bwd_factors_mfma_ragged_mapped")
-        return
-    _check(require().lora_amd_linear_bwd_factors_mfma_ragged(table_dev.data_ptr(), n, grid, lds_class, int(rows),
+    bmap = table_dev.data_ptr() + int(map_offset) if map_offset else None
+    _check(require().lora_amd_linear_bwd_factors_mfma_ragged(table_dev.data_ptr(), n, grid, bmap, lds_class, int(rows),
                                                              dtype_code(act_dtype), flags, _stream()),
            "lora_amd_linear_bwd_factors_mfma_ragged")
 
@@ -1779,11 +1737,11 @@ def linear_gemm_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.
     t = torch.empty((M, r), dtype=torch.float32, device=x.device)
     xd, xD = (x_heads[1], x_heads[2]) if x_heads else (0, 0)
     yd, yD = (y_heads[1], y_heads[2]) if y_heads else (0, 0)
-    _check(require().lora_amd_linear_gemm_fwd_heads(x.data_ptr(), x.stride(0), weight.data_ptr(), weight.stride(0),
-                                                    _ptr(bias), y.data_ptr(), y.stride(0), down.data_ptr(),
-                                                    up.data_ptr(), t.data_ptr(), M, K, N, r, dtype_code(x.dtype),
-                                                    float(scale), float(t_scale), int(factor_layout), int(tile),
-                                                    xd, xD, yd, yD, _stream()), "lora_amd_linear_gemm_fwd")
+    _check(require().lora_amd_linear_gemm_fwd(x.data_ptr(), x.stride(0), weight.data_ptr(), weight.stride(0),
+                                              _ptr(bias), y.data_ptr(), y.stride(0), down.data_ptr(),
+                                              up.data_ptr(), t.data_ptr(), M, K, N, r, dtype_code(x.dtype),
+                                              float(scale), float(t_scale), int(factor_layout), int(tile),
+                                              xd, xD, yd, yD, _stream()), "lora_amd_linear_gemm_fwd")
     return y, t
 
 
@@ -2168,8 +2126,8 @@ def linear_ws(x: torch.Tensor, sites, row_groups: int = 0, x_heads: Heads = None
         outs.append((y, t))
         keep.append((down, up, bias))
     xd, xD = (x_heads[1], x_heads[2]) if x_heads else (0, 0)
-    _check(lib.lora_amd_linear_ws_heads(x.data_ptr(), x.stride(0), M, K, xd, xD, dtype_code(x.dtype), arr, len(sites),
-                                        int(row_groups), _stream()), "lora_amd_linear_ws")
+    _check(lib.lora_amd_linear_ws(x.data_ptr(), x.stride(0), M, K, xd, xD, dtype_code(x.dtype), arr, len(sites),
+                                  int(row_groups), _stream()), "lora_amd_linear_ws")
     return outs
 
 
@@ -2350,7 +2308,7 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps:
         stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
     elif stats.dtype != torch.float32 or tuple(stats.shape) != (M, 2) or not stats.is_contiguous():
         raise ValueError(f"layernorm_fwd: stats must be a contiguous f32 [{M}, 2] tensor")
-    _check(require().lora_amd_layernorm_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
+    _check(require().lora_amd_layernorm_fwd(x.data_ptr(), None, gamma.data_ptr(), beta.data_ptr(), None, y.data_ptr(),
                                             stats.data_ptr(), M, K, eps, dtype_code(x.dtype), _stream()),
            "lora_amd_layernorm_fwd")
     return y, stats
@@ -2360,7 +2318,7 @@ def layernorm_bwd(x: torch.Tensor, gout: torch.Tensor, gamma: torch.Tensor, stat
     _dev_check(x, gout, gamma, stats)
     K = x.shape[-1]
     dx = torch.empty_like(x)
-    _check(require().lora_amd_layernorm_bwd(x.data_ptr(), gout.data_ptr(), gamma.data_ptr(), stats.data_ptr(),
+    _check(require().lora_amd_layernorm_bwd(x.data_ptr(), gout.data_ptr(), None, gamma.data_ptr(), stats.data_ptr(),
                                             dx.data_ptr(), x.numel() // K, K, dtype_code(x.dtype), _stream()),
            "lora_amd_layernorm_bwd")
     return dx
@@ -2410,19 +2368,13 @@ def groupnorm_nhwc_bwd(x: torch.Tensor, gout: torch.Tensor, gamma: torch.Tensor,
     nbytes = groupnorm_nhwc_workspace(B, C_, HW, groups)
     dx = torch.empty_like(x)
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
-    if gsum is None:
-        _check(require().lora_amd_groupnorm_nhwc_bwd(x.data_ptr(), gout.data_ptr(), gamma.data_ptr(), aff.data_ptr(),
-                                                     dx.data_ptr(), ws.data_ptr(), nbytes, B, C_, HW, groups,
-                                                     1 if act else 0, dtype_code(x.dtype), _stream()),
-               "lora_amd_groupnorm_nhwc_bwd")
-        return dx
-    if not gsum_takes(x, gsum):
+    if gsum is not None and not gsum_takes(x, gsum):
         raise ValueError("groupnorm_nhwc_bwd: gsum must have x's shape and dtype, in aligned channels_last rows")
-    _check(require().lora_amd_groupnorm_nhwc_bwd_add(x.data_ptr(), gout.data_ptr(), gsum.data_ptr(), _nhwc_rows(gsum),
-                                                     gamma.data_ptr(),
-                                                     aff.data_ptr(), dx.data_ptr(), ws.data_ptr(), nbytes, B, C_, HW,
-                                                     groups, 1 if act else 0, dtype_code(x.dtype), _stream()),
-           "lora_amd_groupnorm_nhwc_bwd_add")
+    _check(require().lora_amd_groupnorm_nhwc_bwd(x.data_ptr(), gout.data_ptr(), _ptr(gsum),
+                                                 _nhwc_rows(gsum) if gsum is not None else C_, gamma.data_ptr(),
+                                                 aff.data_ptr(), dx.data_ptr(), ws.data_ptr(), nbytes, B, C_, HW,
+                                                 groups, 1 if act else 0, dtype_code(x.dtype), _stream()),
+           "lora_amd_groupnorm_nhwc_bwd")
     return dx
 
 
@@ -2433,7 +2385,7 @@ def groupnorm_nhwc_resident(enable: int = -1) -> int:
 
 def groupnorm_nhwc_route(B: int, C_: int, HW: int, groups: int, dtype: torch.dtype, backward: bool) -> bool:
     """True if ``groupnorm_nhwc_fwd`` / ``_bwd`` of this geometry runs the resident kernel under the current setting."""
-    rc = int(require().lora_amd_groupnorm_nhwc_route(B, C_, HW, groups, dtype_code(dtype), 1 if backward else 0))
+    rc = int(require().lora_amd_groupnorm_nhwc_route(B, C_, HW, groups, dtype_code(dtype), 1 if backward else 0, 0))
     if rc < 0:
         _check(rc, "lora_amd_groupnorm_nhwc_route")
     return rc == 1
@@ -2441,9 +2393,9 @@ def groupnorm_nhwc_route(B: int, C_: int, HW: int, groups: int, dtype: torch.dty
 
 def groupnorm_nhwc_route_add(B: int, C_: int, HW: int, groups: int, dtype: torch.dtype) -> bool:
     """``groupnorm_nhwc_route`` of a backward call that is given ``gsum``."""
-    rc = int(require().lora_amd_groupnorm_nhwc_route_add(B, C_, HW, groups, dtype_code(dtype)))
+    rc = int(require().lora_amd_groupnorm_nhwc_route(B, C_, HW, groups, dtype_code(dtype), 1, 1))
     if rc < 0:
-        _check(rc, "lora_amd_groupnorm_nhwc_route_add")
+        _check(rc, "lora_amd_groupnorm_nhwc_route")
     return rc == 1
 
 
@@ -2561,9 +2513,9 @@ def add_layernorm_fwd(x: torch.Tensor, res: torch.Tensor, gamma: torch.Tensor, b
     M = x.numel() // K
     s, y = torch.empty_like(x), torch.empty_like(x)
     stats = torch.empty(M, 2, dtype=torch.float32, device=x.device)
-    _check(require().lora_amd_add_layernorm_fwd(x.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                                s.data_ptr(), y.data_ptr(), stats.data_ptr(), M, K, eps,
-                                                dtype_code(x.dtype), _stream()), "lora_amd_add_layernorm_fwd")
+    _check(require().lora_amd_layernorm_fwd(x.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                            s.data_ptr(), y.data_ptr(), stats.data_ptr(), M, K, eps,
+                                            dtype_code(x.dtype), _stream()), "lora_amd_layernorm_fwd")
     return s, y, stats
 
 
@@ -2573,9 +2525,9 @@ def add_layernorm_bwd(s: torch.Tensor, gout: torch.Tensor, gsum: Optional[torch.
     _dev_check(s, gout, gsum, gamma, stats)
     K = s.shape[-1]
     dx = torch.empty_like(s)
-    _check(require().lora_amd_add_layernorm_bwd(s.data_ptr(), gout.data_ptr(), _ptr(gsum), gamma.data_ptr(),
-                                                stats.data_ptr(), dx.data_ptr(), s.numel() // K, K,
-                                                dtype_code(s.dtype), _stream()), "lora_amd_add_layernorm_bwd")
+    _check(require().lora_amd_layernorm_bwd(s.data_ptr(), gout.data_ptr(), _ptr(gsum), gamma.data_ptr(),
+                                            stats.data_ptr(), dx.data_ptr(), s.numel() // K, K,
+                                            dtype_code(s.dtype), _stream()), "lora_amd_layernorm_bwd")
     return dx
 
 

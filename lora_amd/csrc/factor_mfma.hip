@@ -808,10 +808,8 @@ extern "C" int lora_amd_factor_pack(const lora_amd_pack_site *sites_dev, int32_t
   return check_launch("lora_amd_factor_pack");
 }
 
-// both ragged-plan entries; wide_dropout: a site of rank 17..64 may carry dropout_p > 0 (the table is then launched with
-// lora_amd_linear_bwd_factors_mfma_wide_masked)
-static int fm_ragged_plan(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype, int32_t lds_class, int64_t *grid,
-                          bool wide_dropout) {
+extern "C" int lora_amd_factors_mfma_ragged_plan(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype, int32_t lds_class,
+                                                 int64_t *grid) {
   LORA_AMD_CHECK(sites && n >= 1 && grid && (lds_class == 1 || lds_class == 2), LORA_AMD_EINVAL,
                  "factors_mfma_ragged_plan: bad argument");
   LORA_AMD_CHECK(act_dtype == LORA_AMD_F16 || act_dtype == LORA_AMD_BF16, LORA_AMD_EINVAL,
@@ -832,9 +830,6 @@ static int fm_ragged_plan(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype,
     LORA_AMD_CHECK(q.r >= 1 && q.r <= (wide ? 64 : 16) && (q.r > 16) == wide && (q.r <= 4 ? 4 : q.r <= 8 ? 8 : 16) == rt0,
                    LORA_AMD_ERANK, "factors_mfma_ragged_plan: site %d: rank %d (one rank tile per table; ranks 17..64 in a table of "
                    "their own)", i, q.r);
-    LORA_AMD_CHECK(!wide || wide_dropout || !(q.dropout_p > 0.f), LORA_AMD_EUNSUPPORTED,
-                   "factors_mfma_ragged_plan: site %d: rank %d with dropout (lora_amd_factors_mfma_ragged_plan_masked plans it)", i,
-                   q.r);
     LORA_AMD_CHECK(q.g && q.x && q.pk_up && q.pk_down && q.up_part && q.down_part, LORA_AMD_EINVAL,
                    "factors_mfma_ragged_plan: site %d: null pointer", i);
     const bool ok = fm_fit(q.M, q.K, q.N, std::min(q.r, 16), act_dtype, q.rows_per_block,
@@ -868,16 +863,6 @@ static int fm_ragged_plan(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype,
   return LORA_AMD_OK;
 }
 
-extern "C" int lora_amd_factors_mfma_ragged_plan(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype, int32_t lds_class,
-                                                 int64_t *grid) {
-  return fm_ragged_plan(sites, n, act_dtype, lds_class, grid, false);
-}
-
-extern "C" int lora_amd_factors_mfma_ragged_plan_masked(lora_amd_fm_site *sites, int32_t n, int32_t act_dtype, int32_t lds_class,
-                                                        int64_t *grid) {
-  return fm_ragged_plan(sites, n, act_dtype, lds_class, grid, true);
-}
-
 extern "C" int lora_amd_factors_mfma_block_map(const lora_amd_fm_site *sites, int32_t n, int64_t grid, int32_t *map) {
   LORA_AMD_CHECK(sites && map && n >= 1 && grid >= 1, LORA_AMD_EINVAL, "factors_mfma_block_map: bad argument");
   int64_t b = 0;
@@ -893,18 +878,11 @@ extern "C" int lora_amd_factors_mfma_block_map(const lora_amd_fm_site *sites, in
   return LORA_AMD_OK;
 }
 
+// the one launch entry of the pass: the argument checks, then the kernel of (dtype, masked, wide, class, height)
 extern "C" int lora_amd_linear_bwd_factors_mfma_ragged(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid,
-                                                       int32_t lds_class, int32_t rows_per_block, int32_t act_dtype,
-                                                       int32_t masked, void *stream) {
-  return lora_amd_linear_bwd_factors_mfma_ragged_mapped(sites_dev, n, grid, nullptr, lds_class, rows_per_block, act_dtype, masked,
-                                                        stream);
-}
-
-// every launch entry of the pass: the argument checks, then the kernel of (dtype, masked, wide, class, height).  Masked AND wide
-// is lora_amd_linear_bwd_factors_mfma_wide_masked's alone (wide_masked); the flag word of the older entries keeps refusing it
-static int fm_launch_table(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid, const int32_t *block_map_dev,
-                           int32_t lds_class, int32_t rows_per_block, int32_t act_dtype, int32_t masked, void *stream,
-                           bool wide_masked) {
+                                                       const int32_t *block_map_dev, int32_t lds_class,
+                                                       int32_t rows_per_block, int32_t act_dtype, int32_t flags,
+                                                       void *stream) {
   LORA_AMD_CHECK(((uintptr_t)block_map_dev % 4) == 0, LORA_AMD_EINVAL, "linear_bwd_factors_mfma_ragged: block map not aligned");
   LORA_AMD_CHECK(sites_dev && n >= 1 && grid >= 1 && grid < (1ll << 31) && (lds_class == 1 || lds_class == 2),
                  LORA_AMD_EINVAL, "linear_bwd_factors_mfma_ragged: bad argument");
@@ -915,14 +893,11 @@ static int fm_launch_table(const lora_amd_fm_site *sites_dev, int32_t n, int64_t
                  "linear_bwd_factors_mfma_ragged: a class-1 table has one block height");
   LORA_AMD_CHECK(act_dtype == LORA_AMD_F16 || act_dtype == LORA_AMD_BF16, LORA_AMD_EINVAL,
                  "linear_bwd_factors_mfma_ragged: f16 / bf16 activations only");
-  LORA_AMD_CHECK((masked & ~(LORA_AMD_FM_TABLE_MASKED | LORA_AMD_FM_TABLE_WIDE)) == 0, LORA_AMD_EINVAL,
-                 "linear_bwd_factors_mfma_ragged: unknown flag bits %d", masked);
-  LORA_AMD_CHECK(wide_masked || masked != (LORA_AMD_FM_TABLE_MASKED | LORA_AMD_FM_TABLE_WIDE), LORA_AMD_EUNSUPPORTED,
-                 "linear_bwd_factors_mfma_ragged: a masked table of ranks 17..64 is launched by "
-                 "lora_amd_linear_bwd_factors_mfma_wide_masked");
+  LORA_AMD_CHECK((flags & ~(LORA_AMD_FM_TABLE_MASKED | LORA_AMD_FM_TABLE_WIDE)) == 0, LORA_AMD_EINVAL,
+                 "linear_bwd_factors_mfma_ragged: unknown flag bits %d", flags);
   hipStream_t st = (hipStream_t)stream;
-  const bool drop = (masked & LORA_AMD_FM_TABLE_MASKED) != 0;  // a table of dropout sites: the kernel with the Philox mask on G (straight-line, no per-site branch)
-  const bool wide = (masked & LORA_AMD_FM_TABLE_WIDE) != 0;    // a table of ranks 17..64: a workgroup per (row block, rank slice)
+  const bool drop = (flags & LORA_AMD_FM_TABLE_MASKED) != 0;  // a table of dropout sites: the kernel with the Philox mask on G (straight-line, no per-site branch)
+  const bool wide = (flags & LORA_AMD_FM_TABLE_WIDE) != 0;     // a table of ranks 17..64: a workgroup per (row block, rank slice)
   // register class 1 with 64-row blocks (<= 3 resident column groups per wave): the 6-pair kernels, chosen by
   // lora_amd_factors_mfma_set_tuning; everything else: the 10-pair kernel of its block height
   const int narrow = (lds_class == 1 && rows_per_block == 64) ? g_fm_narrow : 0;
@@ -974,18 +949,4 @@ static int fm_launch_table(const lora_amd_fm_site *sites_dev, int32_t n, int64_t
     });
   }
   return check_launch("lora_amd_linear_bwd_factors_mfma_ragged");
-}
-
-extern "C" int lora_amd_linear_bwd_factors_mfma_ragged_mapped(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid,
-                                                              const int32_t *block_map_dev, int32_t lds_class,
-                                                              int32_t rows_per_block, int32_t act_dtype, int32_t masked,
-                                                              void *stream) {
-  return fm_launch_table(sites_dev, n, grid, block_map_dev, lds_class, rows_per_block, act_dtype, masked, stream, false);
-}
-
-extern "C" int lora_amd_linear_bwd_factors_mfma_wide_masked(const lora_amd_fm_site *sites_dev, int32_t n, int64_t grid,
-                                                            const int32_t *block_map_dev, int32_t lds_class,
-                                                            int32_t rows_per_block, int32_t act_dtype, void *stream) {
-  return fm_launch_table(sites_dev, n, grid, block_map_dev, lds_class, rows_per_block, act_dtype,
-                         LORA_AMD_FM_TABLE_MASKED | LORA_AMD_FM_TABLE_WIDE, stream, true);
 }

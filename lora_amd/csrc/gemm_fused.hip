@@ -385,18 +385,8 @@ extern "C" int lora_amd_linear_gemm_supported(int64_t M, int32_t K, int32_t N, i
 extern "C" int lora_amd_linear_gemm_fwd(const void *x, int64_t ldx, const void *w, int64_t ldw, const void *bias,
                                         void *y, int64_t ldy, const float *down, const float *up, float *t_out,
                                         int64_t M, int32_t K, int32_t N, int32_t r, int32_t act_dtype, float scale,
-                                        float t_scale, int32_t factor_layout, int32_t tile, void *stream) {
-  return lora_amd_linear_gemm_fwd_heads(x, ldx, w, ldw, bias, y, ldy, down, up, t_out, M, K, N, r, act_dtype, scale,
-                                        t_scale, factor_layout, tile, 0, 0, 0, 0, stream);
-}
-
-extern "C" int lora_amd_linear_gemm_fwd_heads(const void *x, int64_t ldx, const void *w, int64_t ldw,
-                                              const void *bias, void *y, int64_t ldy, const float *down,
-                                              const float *up, float *t_out, int64_t M, int32_t K, int32_t N,
-                                              int32_t r, int32_t act_dtype, float scale, float t_scale,
-                                              int32_t factor_layout, int32_t tile, int32_t x_head_dim,
-                                              int32_t x_head_pad, int32_t y_head_dim, int32_t y_head_pad,
-                                              void *stream) {
+                                        float t_scale, int32_t factor_layout, int32_t tile, int32_t x_head_dim,
+                                        int32_t x_head_pad, int32_t y_head_dim, int32_t y_head_pad, void *stream) {
   LORA_AMD_CHECK(lora_amd_linear_gemm_supported(M, K, N, r, act_dtype), LORA_AMD_EINVAL,
                  "linear_gemm_fwd: needs bf16/f16 activations, K %% 64 == 0, N %% 8 == 0, rank <= 16");
   auto heads_ok = [](int d, int D, int cols, int64_t ld) {

@@ -558,18 +558,13 @@ extern "C" int lora_amd_ws_pack(const void *w, int64_t stride_n, int64_t stride_
   return check_launch("lora_amd_ws_pack");
 }
 
-extern "C" int lora_amd_linear_ws(const void *x, int64_t ldx, int64_t M, int32_t K, int32_t act_dtype,
-                                  const lora_amd_ws_site *sites, int32_t nsites, int32_t row_groups, void *stream) {
-  return lora_amd_linear_ws_heads(x, ldx, M, K, 0, 0, act_dtype, sites, nsites, row_groups, stream);
-}
-
 // may a site's output (heads of d columns in slots of D) go through the padded epilogue: 8-byte groups, one pad group per live
 // group at most, at most two live groups per pad group
 static inline bool ws_y_heads_ok(int d, int D) { return d > 0 && d % 4 == 0 && D % 4 == 0 && D > d && D - d <= d && d <= 2 * (D - d) && D < 65536; }
 
-extern "C" int lora_amd_linear_ws_heads(const void *x, int64_t ldx, int64_t M, int32_t K, int32_t x_head_dim, int32_t x_head_pad,
-                                        int32_t act_dtype, const lora_amd_ws_site *sites, int32_t nsites, int32_t row_groups,
-                                        void *stream) {
+extern "C" int lora_amd_linear_ws(const void *x, int64_t ldx, int64_t M, int32_t K, int32_t x_head_dim, int32_t x_head_pad,
+                                  int32_t act_dtype, const lora_amd_ws_site *sites, int32_t nsites, int32_t row_groups,
+                                  void *stream) {
   WsCfg c;
   LORA_AMD_CHECK(ws_cfg(K, &c), LORA_AMD_EINVAL, "linear_ws: contraction length %d has no weight-stationary kernel", K);
   LORA_AMD_CHECK(act_dtype == LORA_AMD_BF16 || act_dtype == LORA_AMD_F16, LORA_AMD_EINVAL, "linear_ws: bf16/f16 only");
@@ -602,7 +597,7 @@ extern "C" int lora_amd_linear_ws_heads(const void *x, int64_t ldx, int64_t M, i
   }
   LORA_AMD_CHECK(hd == 0 || drop, LORA_AMD_EINVAL,
                  "linear_ws: head-padded activations are built for the dropout sites (p > 0) only; p = 0 sites with heads take "
-                 "lora_amd_linear_gemm_fwd_heads");
+                 "lora_amd_linear_gemm_fwd");
   // ... and with head layouts in either direction (their address arithmetic costs ~28 registers)
   const bool half_rows = drop && K == 320 && ((sites[0].flayout & 3) == 0 || hd != 0);
   if (half_rows) c.RS = 2;

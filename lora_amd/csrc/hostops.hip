@@ -1479,14 +1479,9 @@ extern "C" int lora_amd_layernorm_supported(int32_t K) { return K > 0 && K % 8 =
   const int rows_per_block = kHT >> logL;                                                                        \
   const dim3 grid((unsigned)((M + rows_per_block - 1) / rows_per_block)), block(kHT)
 
-extern "C" int lora_amd_layernorm_fwd(const void *x, const void *gamma, const void *beta, void *y, float *stats,
-                                      int64_t M, int32_t K, float eps, int32_t dtype, void *stream) {
-  return lora_amd_add_layernorm_fwd(x, nullptr, gamma, beta, nullptr, y, stats, M, K, eps, dtype, stream);
-}
-
-extern "C" int lora_amd_add_layernorm_fwd(const void *x, const void *res, const void *gamma, const void *beta,
-                                          void *sum_out, void *y, float *stats, int64_t M, int32_t K, float eps,
-                                          int32_t dtype, void *stream) {
+extern "C" int lora_amd_layernorm_fwd(const void *x, const void *res, const void *gamma, const void *beta, void *sum_out,
+                                      void *y, float *stats, int64_t M, int32_t K, float eps, int32_t dtype,
+                                      void *stream) {
   LN_CHECKS("layernorm_fwd");
   LORA_AMD_CHECK(x && gamma && beta && y && stats, LORA_AMD_EINVAL, "layernorm_fwd: null pointer");
   LORA_AMD_CHECK((res == nullptr) == (sum_out == nullptr), LORA_AMD_EINVAL,
@@ -1505,14 +1500,8 @@ extern "C" int lora_amd_add_layernorm_fwd(const void *x, const void *res, const 
   return check_launch("lora_amd_layernorm_fwd");
 }
 
-extern "C" int lora_amd_layernorm_bwd(const void *x, const void *gout, const void *gamma, const float *stats,
-                                      void *dx, int64_t M, int32_t K, int32_t dtype, void *stream) {
-  return lora_amd_add_layernorm_bwd(x, gout, nullptr, gamma, stats, dx, M, K, dtype, stream);
-}
-
-extern "C" int lora_amd_add_layernorm_bwd(const void *x, const void *gout, const void *gsum, const void *gamma,
-                                          const float *stats, void *dx, int64_t M, int32_t K, int32_t dtype,
-                                          void *stream) {
+extern "C" int lora_amd_layernorm_bwd(const void *x, const void *gout, const void *gsum, const void *gamma,
+                                      const float *stats, void *dx, int64_t M, int32_t K, int32_t dtype, void *stream) {
   LN_CHECKS("layernorm_bwd");
   LORA_AMD_CHECK(x && gout && gamma && stats && dx, LORA_AMD_EINVAL, "layernorm_bwd: null pointer");
   LORA_AMD_CHECK(aligned_for(x, dtype) && aligned_for(gout, dtype) && aligned_for(dx, dtype) && aligned_for(gamma, dtype) &&
@@ -1599,18 +1588,12 @@ extern "C" int lora_amd_groupnorm_nhwc_resident(int32_t enable) {
 }
 
 extern "C" int lora_amd_groupnorm_nhwc_route(int32_t B, int32_t C, int32_t HW, int32_t groups, int32_t dtype,
-                                             int32_t backward) {
+                                             int32_t backward, int32_t add) {
   LORA_AMD_CHECK(gn_nhwc_geo(B, C, HW, groups).ok, LORA_AMD_EINVAL,
                  "groupnorm_nhwc_route: geometry B=%d C=%d HW=%d groups=%d not supported", B, C, HW, groups);
   LORA_AMD_CHECK(dtype_ok(dtype), LORA_AMD_EINVAL, "groupnorm_nhwc_route: bad dtype %d", dtype);
-  return gn_nhwc_route(B, C, HW, groups, dtype, backward);
-}
-
-extern "C" int lora_amd_groupnorm_nhwc_route_add(int32_t B, int32_t C, int32_t HW, int32_t groups, int32_t dtype) {
-  LORA_AMD_CHECK(gn_nhwc_geo(B, C, HW, groups).ok, LORA_AMD_EINVAL,
-                 "groupnorm_nhwc_route_add: geometry B=%d C=%d HW=%d groups=%d not supported", B, C, HW, groups);
-  LORA_AMD_CHECK(dtype_ok(dtype), LORA_AMD_EINVAL, "groupnorm_nhwc_route_add: bad dtype %d", dtype);
-  return gn_nhwc_route(B, C, HW, groups, dtype, 1, true);
+  LORA_AMD_CHECK(!add || backward, LORA_AMD_EINVAL, "groupnorm_nhwc_route: only the backward takes a gradient addend");
+  return gn_nhwc_route(B, C, HW, groups, dtype, backward, add != 0);
 }
 
 // f(int_c<form>) for the plan's form
@@ -1671,18 +1654,10 @@ extern "C" int lora_amd_groupnorm_nhwc_fwd(const void *x, const void *gamma, con
   return check_launch("lora_amd_groupnorm_nhwc_fwd");
 }
 
-extern "C" int lora_amd_groupnorm_nhwc_bwd(const void *x, const void *gout, const void *gamma, const float *aff,
-                                           void *dx, void *workspace, size_t workspace_bytes, int32_t B, int32_t C,
-                                           int32_t HW, int32_t groups, int32_t act, int32_t dtype, void *stream) {
-  return lora_amd_groupnorm_nhwc_bwd_add(x, gout, nullptr, C, gamma, aff, dx, workspace, workspace_bytes, B, C, HW, groups, act,
-                                         dtype, stream);
-}
-
-extern "C" int lora_amd_groupnorm_nhwc_bwd_add(const void *x, const void *gout, const void *gsum, int64_t ld_gsum,
-                                               const void *gamma, const float *aff, void *dx, void *workspace,
-                                               size_t workspace_bytes,
-                                               int32_t B, int32_t C, int32_t HW, int32_t groups, int32_t act,
-                                               int32_t dtype, void *stream) {
+extern "C" int lora_amd_groupnorm_nhwc_bwd(const void *x, const void *gout, const void *gsum, int64_t ld_gsum,
+                                           const void *gamma, const float *aff, void *dx, void *workspace,
+                                           size_t workspace_bytes, int32_t B, int32_t C, int32_t HW, int32_t groups,
+                                           int32_t act, int32_t dtype, void *stream) {
   GN_NHWC_CHECKS("groupnorm_nhwc_bwd");
   LORA_AMD_CHECK(x && gout && gamma && aff && dx && workspace, LORA_AMD_EINVAL, "groupnorm_nhwc_bwd: null pointer");
   LORA_AMD_CHECK(aligned_for(x, dtype) && aligned_for(gout, dtype) && aligned_for(dx, dtype) &&

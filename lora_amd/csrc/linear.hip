@@ -691,11 +691,10 @@ using namespace lora_amd;
   LORA_AMD_CHECK(dtype_ok(dt), LORA_AMD_EINVAL, name ": bad dtype %d", (int)(dt));               \
   if ((M) == 0) return LORA_AMD_OK;
 
-extern "C" int lora_amd_rowdot_masked(const void *x, int64_t ldx, const void *factor, void *t_out, int64_t M,
-                                      int32_t K, int32_t r, int32_t x_dtype, int32_t factor_dtype,
-                                      int32_t factor_layout, float scale, const float *sel,
-                                      int32_t sel_transposed, float dropout_p, uint64_t seed, uint64_t offset, const uint64_t *offset_dev,
-                                      void *stream) {
+extern "C" int lora_amd_rowdot(const void *x, int64_t ldx, const void *factor, void *t_out, int64_t M, int32_t K,
+                               int32_t r, int32_t x_dtype, int32_t factor_dtype, int32_t factor_layout, float scale,
+                               const float *sel, int32_t sel_transposed, float dropout_p, uint64_t seed, uint64_t offset,
+                               const uint64_t *offset_dev, void *stream) {
   COMMON_CHECKS("rowdot", M, K, r, x_dtype);
   LORA_AMD_CHECK(x && factor && t_out, LORA_AMD_EINVAL, "rowdot: null pointer");
   LORA_AMD_CHECK(dtype_ok(factor_dtype), LORA_AMD_EINVAL, "rowdot: bad factor dtype %d", factor_dtype);
@@ -714,13 +713,6 @@ extern "C" int lora_amd_rowdot_masked(const void *x, int64_t ldx, const void *fa
                   : launch_rowdot<E, false>(x, ldx, factor, t_out, M, K, r, factor_dtype, factor_layout, scale, sel,
                                             sel_transposed, 0.f, 0, 0, nullptr, st);
   });
-}
-
-extern "C" int lora_amd_rowdot(const void *x, int64_t ldx, const void *factor, void *t_out, int64_t M, int32_t K,
-                               int32_t r, int32_t x_dtype, int32_t factor_dtype, int32_t factor_layout,
-                               float scale, const float *sel, int32_t sel_transposed, void *stream) {
-  return lora_amd_rowdot_masked(x, ldx, factor, t_out, M, K, r, x_dtype, factor_dtype, factor_layout, scale, sel,
-                                sel_transposed, 0.f, 0, 0, nullptr, stream);
 }
 
 extern "C" int lora_amd_rank_update(void *y, int64_t ldy, const float *t, const void *factor, int64_t M, int32_t N,

@@ -1305,44 +1305,12 @@ extern "C" int lora_amd_linear_bwd_x(const void *x, int64_t ldx, void *dx, int64
   return check_launch("lora_amd_linear_bwd_x");
 }
 
-static int bwd_factors_impl(const void *g, int64_t ldg, const float *t, float *up_part, const void *x, int64_t ldx,
-                            const float *gt, const float *sel, float *down_part, int64_t M, int32_t K, int32_t N,
-                            int32_t r, int32_t act_dtype, float scale, int32_t g_head_dim, int32_t g_head_pad,
-                            int32_t x_head_dim, int32_t x_head_pad, float dropout_p, uint64_t seed, uint64_t offset,
-                            const uint64_t *offset_dev, void *stream);
-
 extern "C" int lora_amd_linear_bwd_factors(const void *g, int64_t ldg, const float *t, float *up_part, const void *x,
                                            int64_t ldx, const float *gt, const float *sel, float *down_part,
                                            int64_t M, int32_t K, int32_t N, int32_t r, int32_t act_dtype, float scale,
-                                           void *stream) {
-  return bwd_factors_impl(g, ldg, t, up_part, x, ldx, gt, sel, down_part, M, K, N, r, act_dtype, scale, 0, 0, 0, 0,
-                          0.f, 0, 0, nullptr, stream);
-}
-
-extern "C" int lora_amd_linear_bwd_factors_drop(const void *g, int64_t ldg, const float *t, float *up_part,
-                                                const void *x, int64_t ldx, const float *gt, const float *sel,
-                                                float *down_part, int64_t M, int32_t K, int32_t N, int32_t r,
-                                                int32_t act_dtype, float scale, float dropout_p, uint64_t seed,
-                                                uint64_t offset, const uint64_t *offset_dev, void *stream) {
-  return bwd_factors_impl(g, ldg, t, up_part, x, ldx, gt, sel, down_part, M, K, N, r, act_dtype, scale, 0, 0, 0, 0,
-                          dropout_p, seed, offset, offset_dev, stream);
-}
-
-extern "C" int lora_amd_linear_bwd_factors_heads(const void *g, int64_t ldg, const float *t, float *up_part,
-                                                 const void *x, int64_t ldx, const float *gt, const float *sel,
-                                                 float *down_part, int64_t M, int32_t K, int32_t N, int32_t r,
-                                                 int32_t act_dtype, float scale, int32_t g_head_dim,
-                                                 int32_t g_head_pad, int32_t x_head_dim, int32_t x_head_pad,
-                                                 void *stream) {
-  return bwd_factors_impl(g, ldg, t, up_part, x, ldx, gt, sel, down_part, M, K, N, r, act_dtype, scale, g_head_dim,
-                          g_head_pad, x_head_dim, x_head_pad, 0.f, 0, 0, nullptr, stream);
-}
-
-static int bwd_factors_impl(const void *g, int64_t ldg, const float *t, float *up_part, const void *x, int64_t ldx,
-                            const float *gt, const float *sel, float *down_part, int64_t M, int32_t K, int32_t N,
-                            int32_t r, int32_t act_dtype, float scale, int32_t g_head_dim, int32_t g_head_pad,
-                            int32_t x_head_dim, int32_t x_head_pad, float dropout_p, uint64_t seed, uint64_t offset,
-                            const uint64_t *offset_dev, void *stream) {
+                                           int32_t g_head_dim, int32_t g_head_pad, int32_t x_head_dim,
+                                           int32_t x_head_pad, float dropout_p, uint64_t seed, uint64_t offset,
+                                           const uint64_t *offset_dev, void *stream) {
   FUSED_COMMON("linear_bwd_factors", act_dtype, LORA_AMD_F32);
   LORA_AMD_CHECK(dropout_p >= 0.f && dropout_p < 1.f && (dropout_p == 0.f || g_head_dim == 0), LORA_AMD_EINVAL,
                  "linear_bwd_factors: dropout p=%f (dense G rows only)", dropout_p);
@@ -1398,13 +1366,8 @@ static bool factors_self_geom(int64_t M, int K, int N, int r, SelfArgs *a, int64
   return true;
 }
 
-extern "C" int lora_amd_linear_factors_self_plan(int64_t M, int32_t K, int32_t N, int32_t r,
+extern "C" int lora_amd_linear_factors_self_plan(int64_t M, int32_t K, int32_t N, int32_t r, int32_t rows,
                                                  lora_amd_factors_self_plan_t *out) {
-  return lora_amd_linear_factors_self_plan_rows(M, K, N, r, 0, out);
-}
-
-extern "C" int lora_amd_linear_factors_self_plan_rows(int64_t M, int32_t K, int32_t N, int32_t r, int32_t rows,
-                                                      lora_amd_factors_self_plan_t *out) {
   LORA_AMD_CHECK(out != nullptr && rows >= 0, LORA_AMD_EINVAL, "factors_self_plan: bad argument");
   memset(out, 0, sizeof(*out));
   SelfArgs a;

@@ -129,41 +129,23 @@ extern "C" int lora_amd_sumsq(const float *g, int64_t n, float *out_sumsq, void 
   return check_launch("lora_amd_sumsq");
 }
 
-static int clip_adamw_impl(float *p, float *g, float *exp_avg, float *exp_avg_sq, int64_t n,
-                           const lora_amd_adamw_group *groups_dev, int32_t n_groups, const float *sumsq,
-                           float grad_scale, float max_norm, float beta1, float beta2, float eps, int64_t step,
-                           const int64_t *step_dev, const float *scaler, int32_t zero_grad, void *stream) {
+extern "C" int lora_amd_clip_adamw(float *p, float *g, float *exp_avg, float *exp_avg_sq, int64_t n,
+                                   const lora_amd_adamw_group *groups_dev, int32_t n_groups, const float *sumsq,
+                                   float grad_scale, float max_norm, float beta1, float beta2, float eps, int64_t step,
+                                   const int64_t *step_dev, const float *scaler, int32_t zero_grad, void *stream) {
   LORA_AMD_CHECK(p && g && exp_avg && exp_avg_sq && groups_dev, LORA_AMD_EINVAL, "clip_adamw: null pointer");
   LORA_AMD_CHECK(n >= 0 && n_groups >= 1 && n_groups <= 16, LORA_AMD_EINVAL, "clip_adamw: n=%lld n_groups=%d",
                  (long long)n, n_groups);
   LORA_AMD_CHECK(step_dev != nullptr || step >= 1, LORA_AMD_EINVAL, "clip_adamw: step must be >= 1 (got %lld)",
                  (long long)step);
   LORA_AMD_CHECK(max_norm <= 0.f || sumsq != nullptr, LORA_AMD_EINVAL, "clip_adamw: clipping needs sumsq");
+  LORA_AMD_CHECK(scaler == nullptr || sumsq != nullptr, LORA_AMD_EINVAL, "clip_adamw: loss scaling needs sumsq");
   if (n == 0) return LORA_AMD_OK;
   hipStream_t st = (hipStream_t)stream;
   int grid = (int)std::min<int64_t>((n + kOptThreads - 1) / kOptThreads, 2048);
   hipLaunchKernelGGL(clip_adamw_kernel, dim3(grid), dim3(kOptThreads), 0, st, p, g, exp_avg, exp_avg_sq, n,
                      groups_dev, n_groups, sumsq, grad_scale, max_norm, beta1, beta2, eps, step, step_dev, scaler, zero_grad);
   return check_launch("lora_amd_clip_adamw");
-}
-
-extern "C" int lora_amd_clip_adamw(float *p, float *g, float *exp_avg, float *exp_avg_sq, int64_t n,
-                                   const lora_amd_adamw_group *groups_dev, int32_t n_groups, const float *sumsq,
-                                   float grad_scale, float max_norm, float beta1, float beta2, float eps,
-                                   int64_t step, int32_t zero_grad, void *stream) {
-  return clip_adamw_impl(p, g, exp_avg, exp_avg_sq, n, groups_dev, n_groups, sumsq, grad_scale, max_norm, beta1,
-                         beta2, eps, step, nullptr, nullptr, zero_grad, stream);
-}
-
-extern "C" int lora_amd_clip_adamw_dev(float *p, float *g, float *exp_avg, float *exp_avg_sq, int64_t n,
-                                       const lora_amd_adamw_group *groups_dev, int32_t n_groups,
-                                       const float *sumsq, float grad_scale, float max_norm, float beta1,
-                                       float beta2, float eps, const int64_t *step_dev, const float *scaler,
-                                       int32_t zero_grad, void *stream) {
-  LORA_AMD_CHECK(step_dev != nullptr, LORA_AMD_EINVAL, "clip_adamw_dev: null step pointer");
-  LORA_AMD_CHECK(scaler == nullptr || sumsq != nullptr, LORA_AMD_EINVAL, "clip_adamw_dev: loss scaling needs sumsq");
-  return clip_adamw_impl(p, g, exp_avg, exp_avg_sq, n, groups_dev, n_groups, sumsq, grad_scale, max_norm, beta1,
-                         beta2, eps, 0, step_dev, scaler, zero_grad, stream);
 }
 
 // Dynamic loss scaling for fp16 training (what accelerate's GradScaler does around the reference's step,

@@ -1243,7 +1243,7 @@ extern "C" int lora_amd_rank_update_rowscale_mfma_takes(const void *y, int64_t l
   return lora_amd::r16_takes(1, y, ldy, M, N, r, y_dtype, factor_dtype, false) ? 1 : 0;
 }
 
-// Pure host: 1 when lora_amd_rowdot[_masked] (op 0) / lora_amd_rank_update (op 1) would run the matrix-core form on these
+// Pure host: 1 when lora_amd_rowdot (op 0) / lora_amd_rank_update (op 1) would run the matrix-core form on these
 // arguments under the current hook setting — the launchers' own predicate, not a restatement of it.  Any other op: 0.
 extern "C" int lora_amd_rank16_mfma_takes(int32_t op, const void *rows, int64_t ld, int64_t M, int32_t cols, int32_t r,
                                           int32_t act_dtype, int32_t factor_dtype, int32_t has_selector) {

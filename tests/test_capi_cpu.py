@@ -165,7 +165,7 @@ def test_library_loads_and_exports_header_symbols():
     missing = [s for s in declared if not hasattr(lib, s)]
     assert not missing, f"declared in include/lora_amd.h but not exported: {missing}"
     assert sorted(_C.SYMBOLS) == declared, "lora_amd/_C.py SYMBOLS out of sync with the header"
-    assert lib.lora_amd_abi_version() == _C.ABI_VERSION == 7 and lib.lora_amd_target_arch() == b"gfx950"
+    assert lib.lora_amd_abi_version() == _C.ABI_VERSION == 8 and lib.lora_amd_target_arch() == b"gfx950"
 
 
 def test_struct_layout_matches_header():
@@ -269,7 +269,7 @@ def test_host_pass_geometry_is_pure_host_arithmetic():
     # argument checks of the compute entry points run before any launch: no GPU needed to see them
     assert lib.lora_amd_geglu_fwd(None, 16, None, 8, 4, 10, _C.BF16, None) != 0
     assert b"inner" in lib.lora_amd_last_error()
-    assert lib.lora_amd_layernorm_fwd(None, None, None, None, None, 4, 100, 1e-5, _C.BF16, None) != 0
+    assert lib.lora_amd_layernorm_fwd(None, None, None, None, None, None, None, 4, 100, 1e-5, _C.BF16, None) != 0
 
 
 def test_conv3_nhwc_plan_is_pure_host_arithmetic():
@@ -346,7 +346,7 @@ def test_round3_planners_are_pure_host_arithmetic():
 
 
 def test_factor_pass_planner_invariants_over_random_shapes():
-    """lora_amd_linear_factors_self_plan_rows / lora_amd_linear_factors_self_ragged_plan (host arithmetic): for random
+    """lora_amd_linear_factors_self_plan / lora_amd_linear_factors_self_ragged_plan (host arithmetic): for random
     (M, K, N, r) the row blocks cover the rows, the column tiles cover the row, LDS limits hold, and the ragged table's block
     ranges are the running sum of the per-site block counts."""
     import random
@@ -432,7 +432,7 @@ def test_matrix_core_factor_plan_prefers_64_row_blocks_for_the_register_kernel()
 
 
 def test_block_map_of_a_planned_factor_pass_table_is_host_arithmetic():
-    """ABI 7: lora_amd_factors_mfma_block_map fills block -> site for a table lora_amd_factors_mfma_ragged_plan planned (no GPU
+    """lora_amd_factors_mfma_block_map fills block -> site for a table lora_amd_factors_mfma_ragged_plan planned (no GPU
     involved); an unplanned table is refused; the bytes helper puts the map behind the table at a 16-byte boundary."""
     import torch
 
@@ -457,7 +457,7 @@ def test_block_map_of_a_planned_factor_pass_table_is_host_arithmetic():
 
 
 def test_ws_head_layout_rules():
-    """ABI 7: which head layouts the weight-stationary kernel's dropout instantiations take (lora_amd_linear_ws_heads /
+    """Which head layouts the weight-stationary kernel's dropout instantiations take (x_head_* of lora_amd_linear_ws /
     lora_amd_ws_site.y_heads): input heads in 16-byte chunks, output pad no wider than the head and at least half of it, whole
     panels, never both."""
     assert _C.ws_heads_ok(320, 320, (8, 40, 64), None) and _C.ws_heads_ok(320, 320, None, (8, 40, 64))
@@ -468,6 +468,27 @@ def test_ws_head_layout_rules():
     assert not _C.ws_heads_ok(320, 320, None, (10, 32, 40))                # head more than twice the pad
     assert not _C.ws_heads_ok(320, 320, (8, 36, 64), None) and not _C.ws_heads_ok(320, 320, (4, 40, 64), None)
     assert C.sizeof(_C.WsSite) == 112 and _C.WsSite.y_heads.offset == 84
+
+
+ABI8_REMOVED = (
+    "lora_amd_rowdot_masked", "lora_amd_linear_bwd_factors_drop", "lora_amd_linear_bwd_factors_heads",
+    "lora_amd_linear_factors_self_plan_rows", "lora_amd_linear_ws_heads", "lora_amd_linear_gemm_fwd_heads",
+    "lora_amd_clip_adamw_dev", "lora_amd_add_layernorm_fwd", "lora_amd_add_layernorm_bwd", "lora_amd_groupnorm_nhwc_bwd_add",
+    "lora_amd_groupnorm_nhwc_route_add", "lora_amd_factors_mfma_ragged_plan_masked",
+    "lora_amd_linear_bwd_factors_mfma_ragged_mapped", "lora_amd_linear_bwd_factors_mfma_wide_masked")
+
+
+def test_abi8_has_one_entry_point_per_launcher():
+    """ABI 8 dropped the 14 second names of launchers that already had one: none is bound, declared or exported."""
+    lib = _C.require()
+    header = open(os.path.join(REPO, "include", "lora_amd.h")).read()
+    assert len(set(ABI8_REMOVED)) == 14
+    for name in ABI8_REMOVED:
+        assert name not in _C.SYMBOLS, name
+        assert name not in header, f"{name} is still in the header"
+        assert not hasattr(lib, name), f"{name} is still exported"
+    assert len(_C.FUNCTIONS) == 116
+    assert lib.lora_amd_abi_version() == _C.ABI_VERSION == 8
 
 
 def _header_launchers():

@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.join(H.REPO, "scripts"))
 import fm_model  # noqa: E402
 
 needs_lib = pytest.mark.skipif(not _C.available(), reason="C-ABI library not built")
-ERANK, EUNSUPPORTED = -2, -5
+EINVAL, ERANK = -1, -2
 BF = torch.bfloat16
 
 
@@ -97,22 +97,39 @@ def test_ragged_plan_of_wide_tables():
     for specs in ([(70, 64, 96, 33, 0.0), (70, 64, 96, 16, 0.0)], [(70, 64, 96, 16, 0.0), (70, 64, 96, 17, 0.0)]):
         assert lib.lora_amd_factors_mfma_ragged_plan(_fm_sites(specs), 2, _C.BF16, 1, C.byref(grid)) == ERANK
     assert lib.lora_amd_factors_mfma_ragged_plan(_fm_sites([(70, 64, 96, 65, 0.0)]), 1, _C.BF16, 1, C.byref(grid)) == ERANK
-    # no masked kernel at these ranks
-    assert lib.lora_amd_factors_mfma_ragged_plan(_fm_sites([(70, 64, 96, 33, 0.1)]), 1, _C.BF16, 1, C.byref(grid)) == EUNSUPPORTED
+    # dropout at these ranks changes no geometry: the two row blocks x three slices of the maskless site above
+    assert lib.lora_amd_factors_mfma_ragged_plan(_fm_sites([(70, 64, 96, 33, 0.1)]), 1, _C.BF16, 1, C.byref(grid)) == 0
+    assert grid.value == 6
     # a narrow table reads as before
     arr = _fm_sites([(70, 64, 96, 16, 0.1), (200, 96, 64, 9, 0.0)])
     assert lib.lora_amd_factors_mfma_ragged_plan(arr, 2, _C.BF16, 1, C.byref(grid)) == 0 and grid.value == 2 + 4
     assert [q.reserved for q in arr] == [0, 0]
 
 
+def launch_refusals(flags):
+    """The argument checks of lora_amd_linear_bwd_factors_mfma_ragged under the flag word ``flags``: every call is refused
+    before any launch, so no device is touched."""
+    def fn(table, n, grid, block_map, lds_class, rows, act_dtype):
+        return _C.require().lora_amd_linear_bwd_factors_mfma_ragged(table, n, grid, block_map, lds_class, rows, act_dtype, flags, None)
+
+    assert fn(4096, 1, 1, None, 3, 64, _C.BF16) == EINVAL      # lds_class outside {1, 2}
+    assert fn(4096, 1, 1, None, 0, 64, _C.BF16) == EINVAL
+    assert fn(4096, 1, 1, None, 1, 48, _C.BF16) == EINVAL      # rows_per_block outside {0, 32, 64}
+    assert fn(4096, 1, 1, None, 1, 0, _C.BF16) == EINVAL       # a class-1 table has one block height
+    assert fn(4096, 1, 1, None, 1, 64, _C.F32) == EINVAL       # 16-bit activations only
+    assert fn(None, 1, 1, None, 1, 64, _C.BF16) == EINVAL      # no table
+    assert fn(4096, 1, 0, None, 1, 64, _C.BF16) == EINVAL      # empty grid
+    assert fn(4096, 1, 1, 4098, 1, 64, _C.BF16) == EINVAL      # misaligned block map
+
+
 @needs_lib
 def test_launch_flags_refuse_masked_and_wide_together():
-    """Argument checks come before the launch: no device is touched."""
+    """The pair of flag bits is a launch like any other: its argument checks come before the launch (no device is touched);
+    a bit outside the two is refused."""
     assert (_C.FM_TABLE_MASKED, _C.FM_TABLE_WIDE) == (1, 2)
     lib = _C.require()
-    rc = lib.lora_amd_linear_bwd_factors_mfma_ragged(4096, 1, 1, 1, 64, _C.BF16, _C.FM_TABLE_MASKED | _C.FM_TABLE_WIDE, None)
-    assert rc == EUNSUPPORTED
-    assert lib.lora_amd_linear_bwd_factors_mfma_ragged(4096, 1, 1, 1, 64, _C.BF16, 4, None) != 0
+    launch_refusals(_C.FM_TABLE_MASKED | _C.FM_TABLE_WIDE)
+    assert lib.lora_amd_linear_bwd_factors_mfma_ragged(4096, 1, 1, None, 1, 64, _C.BF16, 4, None) != 0
 
 
 @pytest.mark.parametrize("args", [dict(M=70, K=64, N=96, r=33, R=64), dict(M=40, K=320, N=96, r=17, R=32),

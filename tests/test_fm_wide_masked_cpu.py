@@ -1,23 +1,24 @@
 """CPU checks of the masked matrix-core factor pass at ranks 17..64 (csrc/factor_mfma.hip, DROP and WIDE together;
-``ops.WIDE_DROPOUT``): the ragged-plan entry that admits dropout at these ranks (same arithmetic as the maskless plan of
+``ops.WIDE_DROPOUT``): the ragged plan with dropout at these ranks (same arithmetic as the maskless plan of
 tests/test_fm_wide_cpu.py: grid, block begins, block map, wide and narrow tables kept apart), the launch entry's argument
-checks (they come before any launch), the binding's choice of plan entry, and the switch.  Needs the built library, no GPU."""
+checks under both flag bits (they come before any launch), the table the binding plans, and the switch.  Needs the built
+library, no GPU."""
 import ctypes as C
 
 import pytest
 import torch
 
 from lora_amd import _C, ops
-from tests.test_fm_wide_cpu import _fm_sites
+from tests.test_fm_wide_cpu import _fm_sites, launch_refusals
 
 needs_lib = pytest.mark.skipif(not _C.available(), reason="C-ABI library not built")
-EINVAL, ERANK, EUNSUPPORTED = -1, -2, -5
+EINVAL, ERANK = -1, -2
 BF = torch.bfloat16
 
 
 def _plan(specs, cls=1, rows=64):
     arr, grid = _fm_sites(specs, rows), C.c_int64(-1)
-    return _C.require().lora_amd_factors_mfma_ragged_plan_masked(arr, len(specs), _C.BF16, cls, C.byref(grid)), arr, grid.value
+    return _C.require().lora_amd_factors_mfma_ragged_plan(arr, len(specs), _C.BF16, cls, C.byref(grid)), arr, grid.value
 
 
 @needs_lib
@@ -26,9 +27,10 @@ def test_masked_plan_of_one_wide_dropout_site():
     rc, arr, grid = _plan([(70, 64, 96, 33, 0.1)])
     assert rc == 0 and grid == 6
     assert list(_C.factors_mfma_block_map(arr, grid)) == [0] * 6
-    # the older entry keeps its answer for the same table
+    # the same table by a raw call
     g = C.c_int64(0)
-    assert _C.require().lora_amd_factors_mfma_ragged_plan(_fm_sites([(70, 64, 96, 33, 0.1)]), 1, _C.BF16, 1, C.byref(g)) == EUNSUPPORTED
+    assert _C.require().lora_amd_factors_mfma_ragged_plan(_fm_sites([(70, 64, 96, 33, 0.1)]), 1, _C.BF16, 1, C.byref(g)) == 0
+    assert g.value == 6
 
 
 @needs_lib
@@ -52,32 +54,26 @@ def test_masked_plan_keeps_wide_and_narrow_apart():
     for specs in ([(70, 64, 96, 33, 0.1), (70, 64, 96, 16, 0.1)], [(70, 64, 96, 16, 0.0), (70, 64, 96, 17, 0.1)]):
         assert _plan(specs)[0] == ERANK
     assert _plan([(70, 64, 96, 65, 0.1)])[0] == ERANK
-    # a narrow table reads as through the older entry
+    # a narrow table with a dropout site
     rc, arr, grid = _plan([(70, 64, 96, 16, 0.1), (200, 96, 64, 9, 0.0)])
     assert rc == 0 and grid == 2 + 4 and [q.reserved for q in arr] == [0, 0]
-    # and its argument checks are the older entry's
+    # the argument checks of the plan
     g = C.c_int64(0)
     lib = _C.require()
-    assert lib.lora_amd_factors_mfma_ragged_plan_masked(_fm_sites([(70, 64, 96, 33, 0.1)]), 1, _C.BF16, 3, C.byref(g)) == EINVAL
-    assert lib.lora_amd_factors_mfma_ragged_plan_masked(_fm_sites([(70, 64, 96, 33, 0.1)]), 1, _C.F32, 1, C.byref(g)) == EINVAL
-    assert lib.lora_amd_factors_mfma_ragged_plan_masked(_fm_sites([(70, 60, 96, 33, 0.1)]), 1, _C.BF16, 1, C.byref(g)) == EINVAL
+    assert lib.lora_amd_factors_mfma_ragged_plan(_fm_sites([(70, 64, 96, 33, 0.1)]), 1, _C.BF16, 3, C.byref(g)) == EINVAL
+    assert lib.lora_amd_factors_mfma_ragged_plan(_fm_sites([(70, 64, 96, 33, 0.1)]), 1, _C.F32, 1, C.byref(g)) == EINVAL
+    assert lib.lora_amd_factors_mfma_ragged_plan(_fm_sites([(70, 60, 96, 33, 0.1)]), 1, _C.BF16, 1, C.byref(g)) == EINVAL
 
 
 @needs_lib
 def test_wide_masked_launch_checks_its_arguments_before_any_launch():
     """No device is touched: every call below is refused by the argument checks."""
-    fn = _C.require().lora_amd_linear_bwd_factors_mfma_wide_masked
-    assert fn(4096, 1, 1, None, 3, 64, _C.BF16, None) == EINVAL      # lds_class outside {1, 2}
-    assert fn(4096, 1, 1, None, 0, 64, _C.BF16, None) == EINVAL
-    assert fn(4096, 1, 1, None, 1, 48, _C.BF16, None) == EINVAL      # rows_per_block outside {0, 32, 64}
-    assert fn(4096, 1, 1, None, 1, 0, _C.BF16, None) == EINVAL       # a class-1 table has one block height
-    assert fn(4096, 1, 1, None, 1, 64, _C.F32, None) == EINVAL       # 16-bit activations only
-    assert fn(None, 1, 1, None, 1, 64, _C.BF16, None) == EINVAL      # no table
-    assert fn(4096, 1, 0, None, 1, 64, _C.BF16, None) == EINVAL      # empty grid
-    assert fn(4096, 1, 1, 4098, 1, 64, _C.BF16, None) == EINVAL      # misaligned block map
-    # the flag word of the older entries still refuses the pair
-    old = _C.require().lora_amd_linear_bwd_factors_mfma_ragged_mapped
-    assert old(4096, 1, 1, None, 1, 64, _C.BF16, _C.FM_TABLE_MASKED | _C.FM_TABLE_WIDE, None) == EUNSUPPORTED
+    launch_refusals(_C.FM_TABLE_MASKED | _C.FM_TABLE_WIDE)
+    # the same checks whatever the flag word, and a bit outside it next to the pair is refused
+    for flags in (0, _C.FM_TABLE_MASKED, _C.FM_TABLE_WIDE):
+        launch_refusals(flags)
+    fn = _C.require().lora_amd_linear_bwd_factors_mfma_ragged
+    assert fn(4096, 1, 1, None, 1, 64, _C.BF16, _C.FM_TABLE_MASKED | _C.FM_TABLE_WIDE | 4, None) == EINVAL
 
 
 class _T:
@@ -105,7 +101,7 @@ def test_binding_takes_the_masked_plan_only_for_a_wide_dropout_site():
     assert grid == 6 + 16 and [q.block_begin for q in arr] == [0, 6]
     assert arr[0].dropout_p == pytest.approx(0.1) and arr[0].scale == pytest.approx(0.5 / 0.9) and (arr[0].seed, arr[0].offset) == (7, 3)
     assert arr[1].dropout_p == 0.0 and arr[1].scale == 0.5
-    arr, grid = _C.factors_mfma_table([site(70, 64, 96, 33, (0.0, 7, 3))], BF, 1)   # p = 0: a maskless site, the older entry
+    arr, grid = _C.factors_mfma_table([site(70, 64, 96, 33, (0.0, 7, 3))], BF, 1)   # p = 0: a maskless site
     assert grid == 6 and arr[0].dropout_p == 0.0
 
 

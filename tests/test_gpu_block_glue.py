@@ -114,15 +114,15 @@ def _gn_case(B, C, H, W, G, dt, act, resident, want_route=None):
     _, aff = _C.groupnorm_nhwc_fwd(x, gamma, beta, G, 1e-5, act, add)
     base = _C.groupnorm_nhwc_bwd(x, gout, gamma, aff, G, act)
     tag = f"{(B, C, H, W, G)} {dt} act={act} resident={resident} (route {route})"
-    # null gsum through the new entry point: the old entry point's bits
+    # null gsum by a raw call, whatever row stride comes with it: the wrapper's bits
     lib = _C.require()
     nbytes = _C.groupnorm_nhwc_workspace(B, C, H * W, G)
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=DEV)
     dx0 = torch.empty_like(x)
-    _C._check(lib.lora_amd_groupnorm_nhwc_bwd_add(x.data_ptr(), gout.data_ptr(), None, 0, gamma.data_ptr(), aff.data_ptr(),
-                                                  dx0.data_ptr(), ws.data_ptr(), nbytes, B, C, H * W, G, 1 if act else 0,
-                                                  _C.dtype_code(dt), torch.cuda.current_stream().cuda_stream), tag)
-    assert torch.equal(dx0, base), f"{tag}: gsum null differs from the old entry"
+    _C._check(lib.lora_amd_groupnorm_nhwc_bwd(x.data_ptr(), gout.data_ptr(), None, 0, gamma.data_ptr(), aff.data_ptr(),
+                                              dx0.data_ptr(), ws.data_ptr(), nbytes, B, C, H * W, G, 1 if act else 0,
+                                              _C.dtype_code(dt), torch.cuda.current_stream().cuda_stream), tag)
+    assert torch.equal(dx0, base), f"{tag}: gsum null with row stride 0 differs from the wrapper's call"
     got = _C.groupnorm_nhwc_bwd(x, gout, gamma, aff, G, act, gsum)
     want = base + gsum
     assert torch.equal(got, want), f"{tag}: {int((got != want).sum())} of {want.numel()} elements differ from bwd + gsum"
@@ -163,7 +163,7 @@ def _foot_inputs(B, Cc, Hh, Ww, dt):
     return mk((B, Hh, Ww, Cc), 1.5), mk((B, Hh, Ww, Cc)), mk((B, Hh, Ww, Cc)), mk((Cc,), 0.5), mk((Cc,), 0.3)
 
 
-@FP.case("lora_amd_groupnorm_nhwc_bwd_add")
+@FP.case("lora_amd_groupnorm_nhwc_bwd")
 def case_groupnorm_nhwc_bwd_add():
     """dx and the workspace between guards, x, gout, gsum and gamma inside poison, streaming and resident; the resident
     launch leaves the workspace alone; values bit-equal to the unguarded backward + gsum."""
@@ -182,9 +182,9 @@ def case_groupnorm_nhwc_bwd_add():
                     _, aff = _C.groupnorm_nhwc_fwd(x4, gamma, beta, G, 1e-5, True, None)
                     wsb = _C.groupnorm_nhwc_workspace(B, Cc, HW, G)
                     ws, dx = MG.Guarded(wsb // 4, torch.float32, DEV), MG.Guarded((B, Hh, Ww, Cc), dt, DEV)
-                    _C._check(lib.lora_amd_groupnorm_nhwc_bwd_add(xl.data_ptr(), gl_.data_ptr(), sl.data_ptr(), Cc,
-                                                                  gamma.data_ptr(), aff.data_ptr(), dx.ptr, ws.ptr, wsb, B, Cc,
-                                                                  HW, G, 1, _C.dtype_code(dt), st), what)
+                    _C._check(lib.lora_amd_groupnorm_nhwc_bwd(xl.data_ptr(), gl_.data_ptr(), sl.data_ptr(), Cc,
+                                                              gamma.data_ptr(), aff.data_ptr(), dx.ptr, ws.ptr, wsb, B, Cc,
+                                                              HW, G, 1, _C.dtype_code(dt), st), what)
                     torch.cuda.synchronize()
                     dx.check(what + " dx")
                     ws.check(what + " workspace")
@@ -223,7 +223,7 @@ def case_resnet_tail():
 
 @pytest.mark.parametrize("case", [case_groupnorm_nhwc_bwd_add, case_resnet_tail])
 def test_footprint_cases(case):
-    assert {"lora_amd_groupnorm_nhwc_bwd_add", "lora_amd_resnet_tail"} <= FP.covered()
+    assert {"lora_amd_groupnorm_nhwc_bwd", "lora_amd_resnet_tail"} <= FP.covered()
     torch.cuda.synchronize()
     case()
     torch.cuda.synchronize()

@@ -5,8 +5,8 @@ where every (row block, 16-rank slice) workgroup regenerates the forward's mask 
 chunk, so the slices of a row block see the same mask: (a) every slice's slab rows are bit for bit the masked rank-16 pass on
 that slice; (b) the fold against ``oracle.lora_numpy.lora_linear_backward`` under the restated Philox mask; (c) the offset
 held on the device; (d) masked and maskless sites of four slice counts in one launch; (e) the memory footprint (the case of
-``lora_amd_linear_bwd_factors_mfma_wide_masked`` in tests/test_gpu_footprint.py's registry: it registers when this module is
-imported, which a run of the whole suite does at collection); (f) the route of one adapter on a trainer's sink; (g) an eager step
+``lora_amd_linear_bwd_factors_mfma_ragged`` with both flag bits in tests/test_gpu_footprint.py's registry: it registers when this
+module is imported, which a run of the whole suite does at collection); (f) the route of one adapter on a trainer's sink; (g) an eager step
 and (h) a captured step of a small stand-in UNet with dropout on every site.
 
 Shapes, geometry and helpers are tests/test_gpu_factors_wide.py's.  What (g) and (h) build is released when they are done."""
@@ -184,7 +184,7 @@ def test_masked_and_maskless_sites_of_four_slice_counts_share_one_launch(dt):
 
 
 # ----------------------------------------------------------------------------- (e) footprint
-@FP.case("lora_amd_linear_bwd_factors_mfma_wide_masked")
+@FP.case("lora_amd_linear_bwd_factors_mfma_ragged")
 def case_factors_wide_masked():
     """W.WIDE_TABLE (ranks 17 / 33 / 64 / 33: M = 1, one row past a block, head-padded G and X, a 64 x 96 site) with dropout on
     every site but the last, bf16 and f16, with the block map: the pass writes exactly the 16 ns rows of every block's slab;
@@ -218,7 +218,7 @@ def case_factors_wide_masked():
 
 
 def test_footprint_case():
-    assert "factors_wide_masked" in FP.CASES and "lora_amd_linear_bwd_factors_mfma_wide_masked" in FP.covered()
+    assert "factors_wide_masked" in FP.CASES and "lora_amd_linear_bwd_factors_mfma_ragged" in FP.covered()
     torch.cuda.synchronize()
     case_factors_wide_masked()
     torch.cuda.synchronize()

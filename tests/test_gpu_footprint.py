@@ -288,7 +288,7 @@ FM_TABLES = [  # one table per (rank tile, LDS class): M = 1, M = k * rows_per_b
 ]
 
 
-@case("lora_amd_factor_pack", "lora_amd_linear_bwd_factors_mfma_ragged", "lora_amd_linear_bwd_factors_mfma_ragged_mapped")
+@case("lora_amd_factor_pack", "lora_amd_linear_bwd_factors_mfma_ragged")
 def case_factors_mfma_ragged():
     """Every site of a table in one launch, slabs exactly as the plan sizes them with guards behind them, both LDS classes,
     ranks 1, 3, 5, 9, 13 and 16, with and without the block map."""
@@ -476,7 +476,7 @@ def _owned(n):
     return own
 
 
-@case("lora_amd_clip_adamw", "lora_amd_clip_adamw_dev", "lora_amd_step_advance", "lora_amd_loss_scale_update")
+@case("lora_amd_clip_adamw", "lora_amd_step_advance", "lora_amd_loss_scale_update")
 def case_clip_adamw():
     """Groups with gaps: p, g, m, v outside every group stay bit-unchanged; the device-step form with the loss-scaling
     flag set and not set; step_advance and loss_scale_update on guarded words."""
@@ -491,15 +491,16 @@ def case_clip_adamw():
         P, G, Mm, V = (MG.guarded_like(t) for t in (p0, g0, m0, v0))
         if form == "host":
             ok(lib().lora_amd_clip_adamw(P.ptr, G.ptr, Mm.ptr, V.ptr, n, groups.data_ptr(), len(ADAMW_GROUPS),
-                                         sumsq.data_ptr(), 1.0, max_norm, 0.9, 0.999, 1e-8, 3, 1, stream()), "clip_adamw")
+                                         sumsq.data_ptr(), 1.0, max_norm, 0.9, 0.999, 1e-8, 3, None, None, 1, stream()),
+               "clip_adamw")
             c = coef
         else:
             step = out(1, torch.int64, fill=torch.tensor([3], device=DEV))
             scaler = inp(torch.tensor([1024.0, 0.0, 0.5, 0.0 if form == "dev_skip" else 1.0], device=DEV))
-            ok(lib().lora_amd_clip_adamw_dev(P.ptr, G.ptr, Mm.ptr, V.ptr, n, groups.data_ptr(), len(ADAMW_GROUPS),
-                                             sumsq.data_ptr(), 1.0, max_norm, 0.9, 0.999, 1e-8, step.ptr, scaler.data_ptr(),
-                                             1, stream()), "clip_adamw_dev")
-            check(step, what="clip_adamw_dev step")
+            ok(lib().lora_amd_clip_adamw(P.ptr, G.ptr, Mm.ptr, V.ptr, n, groups.data_ptr(), len(ADAMW_GROUPS),
+                                         sumsq.data_ptr(), 1.0, max_norm, 0.9, 0.999, 1e-8, 0, step.ptr, scaler.data_ptr(),
+                                         1, stream()), "clip_adamw device step")
+            check(step, what="clip_adamw device step")
             c = 0.5 * min(1.0, max_norm / (math.sqrt(float(sumsq)) * 0.5 + 1e-6))
         check(P, G, Mm, V, what=f"clip_adamw {form}")
         for got, base in ((P, p0), (G, g0), (Mm, m0), (V, v0)):
@@ -518,7 +519,7 @@ def case_clip_adamw():
     g1 = _C.make_adamw_groups([(0, 1, 1e-3, 0.01)], DEV)
     ss1 = inp((g0[:1].double() ** 2).float())
     ok(lib().lora_amd_clip_adamw(P1.ptr, G1.ptr, M1.ptr, V1.ptr, 1, g1.data_ptr(), 1, ss1.data_ptr(), 1.0, 0.0, 0.9, 0.999,
-                                 1e-8, 1, 1, stream()), "clip_adamw n=1")
+                                 1e-8, 1, None, None, 1, stream()), "clip_adamw n=1")
     check(P1, G1, M1, V1, what="clip_adamw n=1")
     gg, bc2 = float(g0[0]), math.sqrt(1 - 0.999)
     mw, vw = 0.9 * float(m0[0]) + 0.1 * gg, 0.999 * float(v0[0]) + 0.001 * gg * gg
@@ -569,7 +570,7 @@ def case_ti_rows_step():
 
 
 # ----------------------------------------------------------------------------- host passes
-@case("lora_amd_layernorm_fwd", "lora_amd_layernorm_bwd", "lora_amd_add_layernorm_fwd", "lora_amd_add_layernorm_bwd")
+@case("lora_amd_layernorm_fwd", "lora_amd_layernorm_bwd")
 def case_layernorm():
     """The smallest and odd supported widths (K = 8, 72, 2560), M = 1 and odd; stats guarded."""
     for M, K in ((1, 8), (5, 72), (3, 2560)):
@@ -578,16 +579,16 @@ def case_layernorm():
             gamma, beta = inp(rnd((K,), dt, 0.5, seed=3) + 1), inp(rnd((K,), dt, 0.3, seed=4))
             gout, gsum = inp(rnd((M, K), dt, seed=5)), inp(rnd((M, K), dt, seed=6))
             y, st = out((M, K), dt), out((M, 2))
-            ok(lib().lora_amd_layernorm_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.ptr, st.ptr, M, K, 1e-5,
-                                            _C.dtype_code(dt), stream()), "layernorm_fwd")
+            ok(lib().lora_amd_layernorm_fwd(x.data_ptr(), None, gamma.data_ptr(), beta.data_ptr(), None, y.ptr, st.ptr, M, K,
+                                            1e-5, _C.dtype_code(dt), stream()), "layernorm_fwd")
             dx = out((M, K), dt)
-            ok(lib().lora_amd_layernorm_bwd(x.data_ptr(), gout.data_ptr(), gamma.data_ptr(), st.ptr, dx.ptr, M, K,
+            ok(lib().lora_amd_layernorm_bwd(x.data_ptr(), gout.data_ptr(), None, gamma.data_ptr(), st.ptr, dx.ptr, M, K,
                                             _C.dtype_code(dt), stream()), "layernorm_bwd")
             s2, y2, st2, dx2 = out((M, K), dt), out((M, K), dt), out((M, 2)), out((M, K), dt)
-            ok(lib().lora_amd_add_layernorm_fwd(x.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(), s2.ptr,
-                                                y2.ptr, st2.ptr, M, K, 1e-5, _C.dtype_code(dt), stream()), "add_layernorm_fwd")
-            ok(lib().lora_amd_add_layernorm_bwd(s2.ptr, gout.data_ptr(), gsum.data_ptr(), gamma.data_ptr(), st2.ptr, dx2.ptr,
-                                                M, K, _C.dtype_code(dt), stream()), "add_layernorm_bwd")
+            ok(lib().lora_amd_layernorm_fwd(x.data_ptr(), res.data_ptr(), gamma.data_ptr(), beta.data_ptr(), s2.ptr,
+                                            y2.ptr, st2.ptr, M, K, 1e-5, _C.dtype_code(dt), stream()), "layernorm_fwd with res")
+            ok(lib().lora_amd_layernorm_bwd(s2.ptr, gout.data_ptr(), gsum.data_ptr(), gamma.data_ptr(), st2.ptr, dx2.ptr,
+                                            M, K, _C.dtype_code(dt), stream()), "layernorm_bwd with gsum")
             check(y, st, dx, s2, y2, st2, dx2, what=f"layernorm M={M} K={K}")
             y3, st3 = out((M, K), dt), out((M, 2))  # the wrapper into a caller's buffers
             _C.layernorm_fwd(x, gamma, beta, 1e-5, out=y3.data, stats=st3.data)
@@ -673,8 +674,9 @@ def case_groupnorm():
             ok(lib().lora_amd_groupnorm_nhwc_fwd(xl.data_ptr(), gamma.data_ptr(), beta.data_ptr(), None, y.ptr, aff.ptr,
                                                  ws.ptr, wsb, B, Cc, HW, G, 1e-5, 1, _C.dtype_code(dt), stream()),
                "groupnorm_nhwc_fwd")
-            ok(lib().lora_amd_groupnorm_nhwc_bwd(xl.data_ptr(), gl_.data_ptr(), gamma.data_ptr(), aff.ptr, dx.ptr, ws.ptr,
-                                                 wsb, B, Cc, HW, G, 1, _C.dtype_code(dt), stream()), "groupnorm_nhwc_bwd")
+            ok(lib().lora_amd_groupnorm_nhwc_bwd(xl.data_ptr(), gl_.data_ptr(), None, Cc, gamma.data_ptr(), aff.ptr, dx.ptr,
+                                                 ws.ptr, wsb, B, Cc, HW, G, 1, _C.dtype_code(dt), stream()),
+               "groupnorm_nhwc_bwd")
             check(y, aff, ws, dx, what="groupnorm_nhwc")
             torch.testing.assert_close(y.data.permute(0, 3, 1, 2).float(), yr.detach(), **tol)
             torch.testing.assert_close(dx.data.permute(0, 3, 1, 2).float(), xr.grad, rtol=tol["rtol"], atol=tol["atol"] * gscale)
@@ -693,8 +695,7 @@ STREAM_SHAPES = [  # M, K, N, r, x dtype: M = 1, K / N not multiples of a wave's
     (1, 8, 8, 1, BF), (33, 77, 41, 5, F32), (130, 1288, 320, 16, BF), (257, 328, 2568, 13, BF), (64, 320, 648, 9, BF)]
 
 
-@case("lora_amd_rowdot", "lora_amd_rowdot_masked", "lora_amd_rank_update", "lora_amd_rank_update_rowscale",
-      "lora_amd_colreduce")
+@case("lora_amd_rowdot", "lora_amd_rank_update", "lora_amd_rank_update_rowscale", "lora_amd_colreduce")
 def case_streaming():
     """Strided X / Y rows with NaN in the row gaps (Y's gaps must stay untouched), dropout, a row table that wraps."""
     s_, p, seed, off = 0.7, 0.25, 0x5EED, 11
@@ -706,12 +707,12 @@ def case_streaming():
         for masked in (False, True):
             t = out((M, r))
             if masked:
-                ok(lib().lora_amd_rowdot_masked(x.data_ptr(), K + 8, f.data_ptr(), t.ptr, M, K, r, dc, _C.F32, _C.FACTOR_RK,
-                                                s_, None, 0, p, seed, off, None, stream()), "rowdot_masked")
+                ok(lib().lora_amd_rowdot(x.data_ptr(), K + 8, f.data_ptr(), t.ptr, M, K, r, dc, _C.F32, _C.FACTOR_RK, s_,
+                                         None, 0, p, seed, off, None, stream()), "rowdot masked")
                 Xm = X * _mask(M, K, p, seed, off)
             else:
                 ok(lib().lora_amd_rowdot(x.data_ptr(), K + 8, f.data_ptr(), t.ptr, M, K, r, dc, _C.F32, _C.FACTOR_RK, s_,
-                                         None, 0, stream()), "rowdot")
+                                         None, 0, 0.0, 0, 0, None, stream()), "rowdot")
                 Xm = X
             check(t, what="rowdot")
             close(t.data, s_ * Xm @ Fd.t(), s_ * Xm.abs() @ Fd.abs().t(), msg=f"rowdot masked={masked} M={M} K={K} r={r}")
@@ -798,7 +799,7 @@ def case_linear_fused():
         close(dx.data[:, :K], d64(dx0) + Gt @ A, d64(dx0).abs() + Gt.abs() @ A.abs(), BF, msg="linear_bwd_x dX")
 
 
-@case("lora_amd_linear_bwd_factors", "lora_amd_linear_bwd_factors_drop", "lora_amd_linear_bwd_factors_heads")
+@case("lora_amd_linear_bwd_factors")
 def case_linear_bwd_factors():
     """Both partial slabs in one launch for sites whose Gt came out of the GEMM: dense and strided, dropout on G, head-padded
     G and X with NaN pads."""
@@ -814,16 +815,17 @@ def case_linear_bwd_factors():
         t, gt = inp(rnd((M, r), F32, 0.5, seed=3)), inp(rnd((M, r), F32, 0.5, seed=4))
         upp, dnp = out(int(lp.up_part_floats)), out(int(lp.down_part_floats))
         if form == "drop":
-            ok(lib().lora_amd_linear_bwd_factors_drop(g.data_ptr(), gw, t.data_ptr(), upp.ptr, x.data_ptr(), xw, gt.data_ptr(),
-                                                      None, dnp.ptr, M, K, N, r, _C.BF16, s_, p, seed, off, None, stream()),
-               "linear_bwd_factors_drop")
+            ok(lib().lora_amd_linear_bwd_factors(g.data_ptr(), gw, t.data_ptr(), upp.ptr, x.data_ptr(), xw, gt.data_ptr(),
+                                                 None, dnp.ptr, M, K, N, r, _C.BF16, s_, 0, 0, 0, 0, p, seed, off, None,
+                                                 stream()), "linear_bwd_factors with dropout")
         elif form == "heads":
-            ok(lib().lora_amd_linear_bwd_factors_heads(g.data_ptr(), gw, t.data_ptr(), upp.ptr, x.data_ptr(), xw,
-                                                       gt.data_ptr(), None, dnp.ptr, M, K, N, r, _C.BF16, s_, 40, 64, 40, 64,
-                                                       stream()), "linear_bwd_factors_heads")
+            ok(lib().lora_amd_linear_bwd_factors(g.data_ptr(), gw, t.data_ptr(), upp.ptr, x.data_ptr(), xw, gt.data_ptr(),
+                                                 None, dnp.ptr, M, K, N, r, _C.BF16, s_, 40, 64, 40, 64, 0.0, 0, 0, None,
+                                                 stream()), "linear_bwd_factors with heads")
         else:
             ok(lib().lora_amd_linear_bwd_factors(g.data_ptr(), gw, t.data_ptr(), upp.ptr, x.data_ptr(), xw, gt.data_ptr(),
-                                                 None, dnp.ptr, M, K, N, r, _C.BF16, s_, stream()), "linear_bwd_factors")
+                                                 None, dnp.ptr, M, K, N, r, _C.BF16, s_, 0, 0, 0, 0, 0.0, 0, 0, None,
+                                                 stream()), "linear_bwd_factors")
         check(upp, dnp, what=f"linear_bwd_factors {form}")
         G = d64(g_log) * (_mask(M, N, p, seed, off) if form == "drop" else 1.0)
         X, T, Gt = d64(x_log), d64(t), d64(gt)
@@ -848,7 +850,7 @@ def _gemm_ref(X, W, b, A, U, s_, rs=None, mask=None):
     return T, X @ W.t() + b + mk * (T16 @ U16.t()), X.abs() @ W.abs().t() + b.abs() + mk * (T.abs() @ U16.abs().t())
 
 
-@case("lora_amd_linear_gemm_fwd", "lora_amd_linear_gemm_fwd_heads", "lora_amd_linear_gemm_fwd_rowscale")
+@case("lora_amd_linear_gemm_fwd", "lora_amd_linear_gemm_fwd_rowscale")
 def case_linear_gemm():
     """M not a multiple of any tile for every tile choice the tests pin (21-24, 31-34), N = 328 (a partial column tile),
     strided X / Y, head-padded X and Y (Y's pads written as zeros), per-sample multipliers with a row table that wraps."""
@@ -862,7 +864,7 @@ def case_linear_gemm():
     for tile in (0, 21, 22, 23, 24, 31, 32, 33, 34):
         y, t = out((M, N + 8), BF), out((M, r))
         ok(lib().lora_amd_linear_gemm_fwd(x.data_ptr(), K + 64, w.data_ptr(), K, b.data_ptr(), y.ptr, N + 8, down.data_ptr(),
-                                          up.data_ptr(), t.ptr, M, K, N, r, _C.BF16, s_, ts, 0, tile, stream()),
+                                          up.data_ptr(), t.ptr, M, K, N, r, _C.BF16, s_, ts, 0, tile, 0, 0, 0, 0, stream()),
            "linear_gemm_fwd")
         check(y, t, what=f"linear_gemm_fwd tile {tile}")
         MG.assert_untouched(y.data[:, N:], "gemm y row gaps")
@@ -890,9 +892,9 @@ def case_linear_gemm():
     cols = heads_cols(Nh, d, D)
     for tile in (22, 24, 21, 33):
         y, t = out((M, Nh // d * D), BF), out((M, r))
-        ok(lib().lora_amd_linear_gemm_fwd_heads(xh.data_ptr(), xh.stride(0), wh.data_ptr(), Kh, bh.data_ptr(), y.ptr,
-                                                Nh // d * D, dh.data_ptr(), uh.data_ptr(), t.ptr, M, Kh, Nh, r, _C.BF16, s_,
-                                                1.0, 0, tile, d, D, d, D, stream()), "linear_gemm_fwd_heads")
+        ok(lib().lora_amd_linear_gemm_fwd(xh.data_ptr(), xh.stride(0), wh.data_ptr(), Kh, bh.data_ptr(), y.ptr,
+                                          Nh // d * D, dh.data_ptr(), uh.data_ptr(), t.ptr, M, Kh, Nh, r, _C.BF16, s_,
+                                          1.0, 0, tile, d, D, d, D, stream()), "linear_gemm_fwd with heads")
         check(y, t, what=f"gemm heads tile {tile}")
         pads = torch.ones(y.data.shape[1], dtype=torch.bool, device=DEV)
         pads[cols] = False
@@ -901,7 +903,7 @@ def case_linear_gemm():
         close(y.data[:, cols], Yh, Yhabs, BF, k=2e-3, msg=f"gemm heads Y tile {tile}")
 
 
-@case("lora_amd_ws_pack", "lora_amd_linear_ws", "lora_amd_linear_ws_heads")
+@case("lora_amd_ws_pack", "lora_amd_linear_ws")
 def case_linear_ws():
     """q / k / v sharing one X, their outputs as column ranges of ONE buffer (gaps between them untouched), M one past a
     row tile; the head-padded forms (built for the dropout sites): padded outputs (q / k / v; pads written as zeros) and a
@@ -933,10 +935,10 @@ def case_linear_ws():
             q.dropout_p, q.seed, q.offset = p, 99 + i, 5
             refs.append((w, b, dn, up, t, wp, _mask(M, N, p, 99 + i, 5)))
         if heads or x_heads:
-            ok(lib().lora_amd_linear_ws_heads(x.data_ptr(), x.stride(0), M, K, d if x_heads else 0, D if x_heads else 0,
-                                              _C.BF16, sites, 3, 0, stream()), "linear_ws_heads")
+            ok(lib().lora_amd_linear_ws(x.data_ptr(), x.stride(0), M, K, d if x_heads else 0, D if x_heads else 0,
+                                        _C.BF16, sites, 3, 0, stream()), "linear_ws with heads")
         else:
-            ok(lib().lora_amd_linear_ws(x.data_ptr(), K + 8, M, K, _C.BF16, sites, 3, 0, stream()), "linear_ws")
+            ok(lib().lora_amd_linear_ws(x.data_ptr(), K + 8, M, K, 0, 0, _C.BF16, sites, 3, 0, stream()), "linear_ws")
         check(ybuf, *[g_ for ref in refs for g_ in (ref[4], ref[5])], what=f"linear_ws x_heads={x_heads} y_heads={heads}")
         cols = heads_cols(N, d, D) if heads else torch.arange(N, device=DEV)
         for i, (w, b, dn, up, t, _, mk) in enumerate(refs):

@@ -213,8 +213,8 @@ def test_footprint(resident):
             torch.cuda.synchronize()
             if resident:
                 MG.assert_untouched(ws.data, what + " workspace after the forward")
-            _C._check(lib.lora_amd_groupnorm_nhwc_bwd(xl.data_ptr(), gl_.data_ptr(), gamma.data_ptr(), aff.ptr, dx.ptr, ws.ptr,
-                                                      wsb, B, Cc, HW, G, 1, _C.dtype_code(dt), st), what)
+            _C._check(lib.lora_amd_groupnorm_nhwc_bwd(xl.data_ptr(), gl_.data_ptr(), None, Cc, gamma.data_ptr(), aff.ptr, dx.ptr,
+                                                      ws.ptr, wsb, B, Cc, HW, G, 1, _C.dtype_code(dt), st), what)
             torch.cuda.synchronize()
             for i, gd in enumerate((y, aff, ws, dx)):
                 gd.check(f"{what} operand {i}")

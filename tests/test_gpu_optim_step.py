@@ -344,7 +344,7 @@ def test_sixteen_groups_gap_empty_group_and_zero_lr():
 @pytest.mark.parametrize("n", [1027, N_BIG])
 @pytest.mark.parametrize("k", [1, 7, 1000])
 def test_device_step_gives_the_bits_of_the_host_step(n, k):
-    """§2(e): lora_amd_clip_adamw_dev with step_dev[0] == k is lora_amd_clip_adamw with step = k."""
+    """§2(e): lora_amd_clip_adamw with step_dev[0] == k is lora_amd_clip_adamw with step = k and no step_dev."""
     p, m, v = state_data(n)
     g = grad_data(n)
     groups = default_groups(n)
@@ -498,7 +498,7 @@ def feed(st, g):
 
 
 def test_graph_safe_steps_called_eagerly_equal_eager_steps():
-    """§4(a): the device-step form without a scaler (step_advance, then clip_adamw_dev) through FlatLoraState."""
+    """§4(a): the device-step form without a scaler (step_advance, then clip_adamw on the device step) through FlatLoraState."""
     (sg, p0), (se, _) = make_state(), make_state()
     ref = RefOptimiser(p0, FLAT_GROUPS, 1.0)
     for k, g in enumerate(flat_grads(5)):

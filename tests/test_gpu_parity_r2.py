@@ -318,7 +318,7 @@ def test_dropout_masks_fresh_per_graph_replay_and_stable_under_checkpoint():
 
 
 def test_loss_scaling_on_device_matches_cpu_semantics():
-    """lora_amd_loss_scale_update + the scaler operand of lora_amd_clip_adamw_dev vs the CPU restatement in
+    """lora_amd_loss_scale_update + the scaler operand of lora_amd_clip_adamw vs the CPU restatement in
     FlatLoraState.step (GradScaler semantics: unscale, skip on inf/nan, backoff / growth)."""
     def make(device):
         p = torch.nn.Parameter(torch.linspace(-1, 1, 4096, device=device))
@@ -825,7 +825,7 @@ def test_ws_kernel_dropout_forward_equals_two_launch_path(M, K, N, r, p):
 @pytest.mark.parametrize("M,K,N,r,p", [(4096, 320, 320, 16, 0.1), (2048, 1280, 640, 4, 0.25), (576, 320, 1280, 16, 0.1)])
 def test_ws_kernel_dropout_input_gradient_and_factor_partials(M, K, N, r, p):
     """Backward of the same site: Gt = s (mask*G) up and dX = G W + Gt down from the weight-stationary kernel, dUp
-    from lora_amd_linear_bwd_factors_drop — against the masked primitives (rowdot_masked / colreduce) with the same
+    from lora_amd_linear_bwd_factors with dropout — against the masked primitives (rowdot / colreduce) with the same
     (seed, offset)."""
     g, x = rnd((M, N), "bf16", seed=1), rnd((M, K), "bf16", seed=6)
     w = rnd((N, K), "bf16", 0.05, seed=2)

@@ -69,7 +69,7 @@ def test_ws_dropout_forward_vs_oracle_with_extracted_mask(M, K, N, r, p):
 @pytest.mark.parametrize("M,K,N,r,p", [(4096, 320, 320, 16, 0.1), (2048, 1280, 640, 4, 0.25), (576, 320, 1280, 16, 0.1)])
 def test_ws_dropout_backward_vs_oracle_with_extracted_mask(M, K, N, r, p):
     """Autograd of the same site: Gt / dX from the weight-stationary input-gradient launch, dUp / dDown from
-    lora_amd_linear_bwd_factors_drop, vs oracle.lora_linear_backward(mask=)."""
+    lora_amd_linear_bwd_factors with dropout_p > 0, vs oracle.lora_linear_backward(mask=)."""
     dt, s, seed, off = "bf16", 0.8, 99, 31337
     g, x = rnd((M, N), dt, seed=1), rnd((M, K), dt, seed=6)
     w = rnd((N, K), dt, 0.05, seed=2)

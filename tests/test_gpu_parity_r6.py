@@ -350,7 +350,7 @@ def test_bracket_under_the_reference_precision_policy(monkeypatch):
 
 
 def test_factor_pass_block_map_finds_the_same_sites_as_the_search():
-    """ABI 7: lora_amd_linear_bwd_factors_mfma_ragged_mapped (a workgroup reads its site index from the plan's block -> site map)
+    """lora_amd_linear_bwd_factors_mfma_ragged with block_map_dev (a workgroup reads its site index from the plan's block -> site map)
     against the launch that searches the table's block prefix: a class-2 table of four sites with both block heights and a ragged
     last block, and a class-1 table — the slabs are the same bits; a map that disagrees with the table is refused on the host."""
     dt, r = torch.bfloat16, 4

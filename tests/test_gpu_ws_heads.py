@@ -1,6 +1,6 @@
 """Round-6 device parity: the dropout sites around the attention core (lora.py:53-58 called by CrossAttention's to_q / to_k /
 to_v / to_out under ``dropout_p > 0``, the reference's default 0.1) in HEAD-PADDED rows on the weight-stationary kernel
-(``lora_amd_linear_ws_heads``, ``lora_amd_ws_site.y_heads``): rounds 3-5 unpacked the input and packed the output with copies.
+(``lora_amd_linear_ws``'s ``x_head_*``, ``lora_amd_ws_site.y_heads``): rounds 3-5 unpacked the input and packed the output with copies.
 
 * kernel level, through the C-ABI: forward and input-gradient launches with a head-padded input / output against
   ``oracle/lora_numpy`` with the restated Philox mask, AND bit-equal to the dense launch around explicit copies; the input's

@@ -25,7 +25,7 @@ GOLDEN = os.path.join(H.GOLDEN, "mini_ref.safetensors")
 
 def test_plan_is_pure_host_arithmetic():
     lib = _C.require()
-    assert lib.lora_amd_abi_version() == 7
+    assert lib.lora_amd_abi_version() == 8
     for (N, Kk, R, r), (bn, bk) in (((40, 72, 9, 4), (1, 1)), ((320, 2880, 64, 64), (2, 12)), ((1, 1, 1, 1), (1, 1))):
         pl = _C.resize_plan(N, Kk, R, r, up_ptr=4096, down_ptr=8192)
         assert pl.native == 1 and (pl.gram_blocks_n, pl.gram_blocks_k) == (bn, bk)

@@ -55,7 +55,7 @@ def test_plan_of_an_f32_source_table_has_the_same_tiles_and_sets_the_source_bit(
     tile count and geometry bits as the 16-bit table and carries a bit at or above bit 48."""
     assert _C.MstepSite.src_f32.offset == 92 and C.sizeof(_C.MstepSite) == 104 and _C.MstepSite.tile_begin.offset == 96
     lib = _C.require()
-    assert lib.lora_amd_abi_version() == 7
+    assert lib.lora_amd_abi_version() == 8
     for tile in range(4):
         vals = {}
         for f in (0, 1):

@@ -71,7 +71,7 @@ def test_rank16_mfma_takes_keeps_its_answers():
     assert lib.lora_amd_rank16_mfma_takes(0, ADDR, 320, 577, 320, 32, _C.BF16, _C.F32, 0) == 1
     assert lib.lora_amd_rank16_mfma_takes(1, ADDR, 320, 577, 320, 32, _C.BF16, _C.F32, 0) == 1
     assert lib.lora_amd_rank16_mfma_takes(0, ADDR, 320, 577, 320, 32, _C.BF16, _C.F32, 1) == 0
-    assert lib.lora_amd_abi_version() == 7
+    assert lib.lora_amd_abi_version() == 8
 
 
 def _case(r, rows, nsel, seed):
